@@ -6,7 +6,7 @@ model, MLP 4x256 (embedding 8, no conditionals), 100-step RK4 (torchdiffeq's "rk
 network evaluations per sample), batch 2^20 per GPU, random-init weights (seed 0), synthetic
 standard-normal base samples resident in HBM.  One "step" = one full solve of the batch.
 
-    python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -642,6 +642,24 @@ def streaming_helpers(device):
     return rows
 
 
+DUMP_MAX_ROWS = 1 << 19      # 32 MiB of 16-dim float32 samples
+
+
+def dump_outputs(out_dir, samples):
+    """What a caller of the timed path receives from its last step: the samples of `sample_ode_from_base`, written as
+    `out_dir/samples.npy` (float32, one row per sample).  A batch of more than DUMP_MAX_ROWS rows is cut to a fixed,
+    seeded choice of that many rows, in row order, so that two builds run with the same arguments can be compared
+    row for row (the base samples and the weights are seeded too)."""
+    import numpy as np
+    n = samples.shape[0]
+    if n > DUMP_MAX_ROWS:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(20240))[:DUMP_MAX_ROWS].sort().values
+        samples = samples[rows.to(samples.device)]
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "samples.npy", samples.detach().to("cpu", torch.float32).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -669,7 +687,11 @@ def main():
     ap.add_argument("--c3-steps", type=int, default=N_STEPS, help="N > 1: RK4 steps of configs[2]")
     ap.add_argument("--c4-steps", type=int, default=200, help="N > 1: fixed steps of configs[3] (rehearsals shorten it)")
     ap.add_argument("--c5-steps", type=int, default=1000, help="N > 1: Euler-Maruyama steps of configs[4]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # rehearsal on one GPU: take the multi-rank branch with a process group of ONE rank (RCCL refuses two ranks on one
@@ -749,6 +771,8 @@ def main():
         tmax = torch.tensor([elapsed], device=gather_dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered if multi else x)
 
     # per-launch kernel time of the timed steps themselves
     kernel_ms = sorted(s.elapsed_time(e) for s, e, _ in ev)
