@@ -28,10 +28,9 @@ import torch
 from torch import nn
 from torch.distributions import Normal
 
-from . import adaptive, device_adaptive, generic, solvers
-from . import _native
-from . import host_stepper, trace_estimators
+from . import _native, device_adaptive, generic, odeint, solvers, trace_estimators
 from .fused import FusedNet, MODE_EXACT, MODE_HUTCH, MODE_STATE, activation_spec, require_fp32, within_envelope
+from .generic import _need_gpu
 
 
 # ------------------------------------------------------------------------------------------------
@@ -284,22 +283,16 @@ class ScoreModel(nn.Module):
         key = tuple(id(l) for l in m.NN) + (repr(m.activation),)
         return within_envelope(self, key, self._net)
 
-    def _rhs_module(self, t, y):
-        """ODE right-hand side through ``self.forward`` (the reference's own RHS, diffusion.py:281-508): the user's
-        module evaluates the score; divergences come from autograd exactly as in the reference."""
-        if not self.prob:
-            return self.forward(t, (y,)), None
-        xdot, div = self.forward(t, (y, None))
-        return xdot, div.reshape(-1)
-
-    def _solve_generic(self, x, t_span, method, options, mode, atol, rtol, affine):
-        if affine.get("in_shift") is not None:
-            x = (x - affine["in_shift"]) / affine["in_scale"]
-        y, lp, stats = generic.solve(self._rhs_module, x, t_span, method, options, mode != MODE_STATE, atol, rtol)
-        self.last_solver_stats = stats
-        if affine.get("out_scale") is not None:
-            y = y * affine["out_scale"] + affine["out_shift"]
-        return y, lp
+    def _module_rhs(self, mode, cond, probe):
+        """ODE right-hand side through ``self.forward`` (the reference's own RHS, diffusion.py:281-508) for the generic
+        route (odeint.py): the user's module evaluates the score; divergences come from autograd exactly as in the
+        reference (``self.prob`` / ``self.conditional`` and the probes are set by the caller)."""
+        def rhs(t, y):
+            if not self.prob:
+                return self.forward(t, (y,)), None
+            xdot, div = self.forward(t, (y, None))
+            return xdot, div.reshape(-1)
+        return rhs
 
     # -- fused path -----------------------------------------------------------------------------
     def _net(self) -> FusedNet:
@@ -346,6 +339,11 @@ class ScoreModel(nn.Module):
         return (copy.deepcopy(self.sde).to("cpu"), m.W.detach().to("cpu", torch.float32),
                 m.pi.detach().to("cpu", torch.float32), w0, b0)
 
+    def _host_schedule(self):
+        """``(a, b, c1)`` of the probability-flow ODE for the host controller, from one set of host copies per solve."""
+        host = self._schedule_inputs()
+        return lambda tr: self._schedule(tr, "ode", host)[:3]
+
     def _schedule(self, t: torch.Tensor, sde_form: str, host=None):
         """Per-evaluation scalars (a, b) and first-layer bias c1 for real times ``t`` (fp32, CPU).
 
@@ -383,53 +381,10 @@ class ScoreModel(nn.Module):
         a, b, c1, _ = self._schedule(plan.t_eval, "ode")
         return solvers.build_table(plan, a, b, c1, self._net().width(mode))
 
-    def _solve(self, x, t_span, method, options, mode, atol, rtol, cond=None, probe=None, **affine):
-        """odeint(self, state, t_span, method=, atol=, rtol=, options=) on the fused kernels:
-        fixed-grid methods as one launch, the adaptive methods with the step control on the device.  ``affine``
-        (in_shift / in_scale / out_scale / out_shift, the PopulationModel wrappers' pre- and post-processing)
-        rides in the kernel's prologue / epilogue on fixed grids and is applied around the adaptive loop."""
-        require_fp32(self, x, cond, probe, what="an ODE solve")
-        if not self._fusable():
-            return self._solve_generic(x, t_span, method, options, mode, atol, rtol, affine)
-        net = self._net()
-        if method in solvers.ALL_ADAPTIVE:
-            if affine.get("in_shift") is not None:
-                x = (x - affine["in_shift"]) / affine["in_scale"]
-            t = t_span.detach().to("cpu", torch.float32).double()
-            sign = -1.0 if bool(t[0] > t[-1]) else 1.0
-            spec = self._device_schedule(x.device) if (x.is_cuda and method in solvers.NATIVE_ADAPTIVE) else None
-            if device_adaptive.supported(spec, x, net, mode, options):
-                # the whole loop on the device: attempts, error norms, step control, the next attempt's table rows
-                y, lp, stats = device_adaptive.solve(net, spec, sign, mode, x, float(sign * t[0]), float(sign * t[-1]),
-                                                     rtol, atol, options, method, cond=cond, probe=probe)
-                self.last_solver_stats = stats
-                if affine.get("out_scale") is not None:
-                    y = y * affine["out_scale"] + affine["out_shift"]
-                return y, lp
-            host = self._schedule_inputs()
-            sched = lambda tr: self._schedule(tr, "ode", host)[:3]
-            step = net.make_step(sched, sign, mode, x.device, cond=cond, probe=probe)
-            solver = adaptive.make_solver(step, mode != MODE_STATE, rtol, atol, options, method=method, sign=sign)
-            lp0 = torch.zeros(x.shape[0], device=x.device) if mode != MODE_STATE else None
-            y, lp = solver.integrate(float(sign * t[0]), float(sign * t[-1]),
-                                     x.detach().to(torch.float32).contiguous(), lp0)
-            self.last_solver_stats = {"attempts": solver.n_attempts, "accepted": solver.n_accepted}
-            if affine.get("out_scale") is not None:
-                y = y * affine["out_scale"] + affine["out_shift"]
-            return y, lp
-        key = ("score-ode", tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items())), mode,
-               self.no_sigma, self._schedule_key())
-        if (options or {}).get("grid_constructor") is not None:      # the grid may depend on y0: built per call
-            table = self._ode_table(t_span, method, options, mode, y0=x).to(x.device)
-        else:
-            table = net.cached_table(key, x.device, lambda: self._ode_table(t_span, method, options, mode))
-        y, lp, _ = net.integrate(x, table, mode, cond=cond, probe=probe, stage_slots=solvers.resolve_method(method).stages, **affine)
-        return y, (lp if mode != MODE_STATE else None)
-
     def _schedule_key(self):
         """Everything besides the first layer that the evaluation table depends on."""
         sde = self.sde
-        vals = [type(sde).__name__]
+        vals = [self.no_sigma, type(sde).__name__]
         for name in ("beta_min", "beta_max", "T", "epsilon", "sigma_min", "sigma_max"):
             if hasattr(sde, name):
                 vals.append(float(getattr(sde, name)))
@@ -606,8 +561,8 @@ class ScoreModel(nn.Module):
         self.prob = False
         self.conditional = conditional
         t_span = torch.tensor([1.0, float(self.sde.epsilon)], dtype=torch.float32)
-        x, _ = self._solve(z, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional,
-                           out_scale=out_scale, out_shift=out_shift)
+        x, _ = odeint.solve(self, z, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional,
+                            out_scale=out_scale, out_shift=out_shift)
         return x
 
     @torch.no_grad()
@@ -621,22 +576,10 @@ class ScoreModel(nn.Module):
         ``probe="philox"`` takes the signs of the library's counter-based normals keyed by ``seed`` and the GLOBAL row
         ``sample_offset + r`` (``ff_normal_fill`` with the reserved probe index): drawn on the device (no host draw, no
         upload) and independent of how a batch is cut into shards (``distributed.log_prob_sharded``)."""
-        return self._solve_forward(x0_samples, conditional, atol, rtol, method, options,
-                                   probe_rng=self._probe_rng(probe, seed, sample_offset))
-
-    def _probe_rng(self, probe, seed, sample_offset):
-        if probe == "torch":
-            if seed is not None:
-                raise ValueError("seed= belongs to probe='philox' (the torch probe follows torch.manual_seed)")
-            return None
-        if probe != "philox":
-            raise ValueError(f"probe must be 'torch' or 'philox', not {probe!r}")
-        if not (self.hutch or self.hutchpp or self.xtrace):
-            raise ValueError("probe='philox' draws the probes of a Hutchinson / Hutch++ / XTrace model: construct it with "
-                             "hutchinson=True, hutchpp=True or xtrace=True")
-        if seed is None:      # one draw of torch's generator, so torch.manual_seed still fixes the run
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return int(seed), int(sample_offset)
+        philox_ok = self.hutch or self.hutchpp or self.xtrace
+        return self._solve_forward(x0_samples, conditional, atol, rtol, method, options, probe_rng=trace_estimators.probe_rng(
+            probe, seed, sample_offset, philox_ok, "probe='philox' draws the probes of a Hutchinson / Hutch++ / XTrace model: "
+            "construct it with hutchinson=True, hutchpp=True or xtrace=True"))
 
     @torch.no_grad()
     def _solve_forward(self, x0_samples, conditional, atol, rtol, method, options, in_shift=None, in_scale=None,
@@ -651,56 +594,34 @@ class ScoreModel(nn.Module):
         if (self.hutchpp or self.xtrace) and not self.hutch:
             if in_shift is not None:
                 x0_samples = (x0_samples - in_shift) / in_scale
-            if fused:
-                return self._solve_with_estimator(x0_samples, conditional, atol, rtol, method, options, probe_rng)
-            if probe_rng is not None:
-                raise NotImplementedError("probe='philox' lives on the fused path; a custom score module draws its probes with torch")
-            # any other module: forward() runs the estimator itself (reverse mode, like the reference); the probes are
-            # drawn once per solve on the state's device (:703-719)
-            (r, m), mx = self._probe_counts(x0_samples.shape[1])
-            if self.hutchpp:
-                self.S = trace_estimators.draw_probes(r, x0_samples)
-                self.G = trace_estimators.draw_probes(m, x0_samples)
-            else:
-                self.O = trace_estimators.draw_probes(mx, x0_samples)
-            t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
-            xT, dlogp = self._solve_generic(x0_samples, t_span, method, options, MODE_EXACT, atol, rtol, {})
-            return xT, dlogp.view(-1, 1)
+            return self._solve_with_estimator(x0_samples, conditional, atol, rtol, method, options, fused, probe_rng)
         probe = None
         mode = MODE_EXACT
-        if self.hutch and probe_rng is not None:
-            if x0_samples.dim() != 2:
-                raise NotImplementedError("probe='philox': only [batch, dim] states")
-            z = _native.normal_fill(x0_samples.shape[0], x0_samples.shape[1], probe_rng[0], probe_rng[1],
-                                    x0_samples.device, noise_index=_native.PROBE_NOISE_INDEX)
-            self.e = torch.where(z >= 0, 1.0, -1.0).to(torch.float32)
-        elif self.hutch:
-            # drawn on the CPU and moved, as the reference does (diffusion.py:701)
-            self.e = torch.sign(torch.randn(x0_samples.shape)).to(x0_samples.device)
         if self.hutch:
-            probe = self.e
+            if probe_rng is not None and x0_samples.dim() != 2:
+                raise NotImplementedError("probe='philox': only [batch, dim] states")
+            self.e = probe = trace_estimators.hutchinson_probe(x0_samples, probe_rng)
             mode = MODE_HUTCH
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
-        xT, dlogp = self._solve(x0_samples, t_span, method, options, mode, atol, rtol, cond=conditional, probe=probe,
-                                in_shift=in_shift, in_scale=in_scale)
+        xT, dlogp = odeint.solve(self, x0_samples, t_span, method, options, mode, atol, rtol, cond=conditional, probe=probe,
+                                 in_shift=in_shift, in_scale=in_scale)
         return xT, dlogp.view(-1, 1)
 
-    def _solve_with_estimator(self, x0, conditional, atol, rtol, method, options, probe_rng=None):
-        """Hutch++ / XTrace log-density solve.  The state never depends on the divergence, so the launches are those of the
-        exact trace with the Jacobian of every evaluation row recorded (ff_ode_args.jac_all); the estimates of all rows
-        come from ONE launch (ff_trace_estimate, csrc/ff_trace.hip) and are combined with the tableau's weights.  The
-        adaptive methods run with the step control on the device like every other solve (device_adaptive.py); the host
-        controller with one launch per right-hand side (host_stepper.py) stays for what that cannot describe.  Probes are
-        drawn once per solve on the state's device, as the reference does (:703-719)."""
-        net = self._net()
-        if net.precision != "f32":
-            raise NotImplementedError(f"precision={net.precision!r}: the Hutch++ / XTrace estimators need the Jacobian output of the "
-                                      "f32 kernels (bf16x2 serves hutchinson=True and the exact trace)")
-        if not x0.is_cuda:
-            raise RuntimeError("flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
-                               f"(got a tensor on {x0.device}); there is no CPU fallback")
-        B, D = x0.shape
-        (r, m), mx = self._probe_counts(D)
+    def _solve_with_estimator(self, x0, conditional, atol, rtol, method, options, fused, probe_rng=None):
+        """Hutch++ / XTrace log-density solve.  The state never depends on the divergence, so the fused launches are those
+        of the exact trace with the Jacobian of every evaluation row recorded (ff_ode_args.jac_all); the estimates of all
+        rows come from ONE launch (ff_trace_estimate, csrc/ff_trace.hip) and are combined with the tableau's weights
+        (odeint.py picks the route).  Any other module: forward() runs the estimator itself (reverse mode, like the
+        reference).  Probes are drawn once per solve on the state's device, as the reference does (:703-719)."""
+        if fused:
+            net = self._net()
+            if net.precision != "f32":
+                raise NotImplementedError(f"precision={net.precision!r}: the Hutch++ / XTrace estimators need the Jacobian output of the "
+                                          "f32 kernels (bf16x2 serves hutchinson=True and the exact trace)")
+            _need_gpu(x0)
+        elif probe_rng is not None:
+            raise NotImplementedError("probe='philox' lives on the fused path; a custom score module draws its probes with torch")
+        (r, m), mx = self._probe_counts(x0.shape[1])
         if probe_rng is not None:       # probe="philox": keyed by (seed, global row), independent of the sharding
             draw = lambda n, second=False: trace_estimators.draw_probes_philox(n, x0, probe_rng[0], probe_rng[1], second)
         else:
@@ -713,37 +634,10 @@ class ScoreModel(nn.Module):
             # the reference stores max(1, xt_vecs) probes and redraws inside forward when that exceeds D (:719, :409-416)
             self.O = draw(mx)
             kind, probes = "xtrace", (self.O,)
-        x = x0.detach().to(torch.float32).contiguous()
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
-        if method in solvers.ALL_ADAPTIVE:
-            spec = self._device_schedule(x.device) if method in solvers.NATIVE_ADAPTIVE else None
-            if device_adaptive.supported(spec, x, net, MODE_EXACT, options) and \
-                    device_adaptive.estimator_bytes(net, method, B, kind, probes) <= self._estimator_budget(x.device):
-                y, lp, stats = device_adaptive.solve(net, spec, 1.0, MODE_EXACT, x, float(t_span[0]), float(t_span[1]), rtol, atol,
-                                                     options, method, cond=conditional, estimator=(kind, probes))
-                self.last_solver_stats = stats
-                return y, lp.view(-1, 1)
-            stepper = host_stepper.RowStepper(net, x.device, conditional, lambda A: self._estimate_divergence(A, x))
-            host = self._schedule_inputs()
-            sched = lambda tr: self._schedule(tr, "ode", host)[:3]
-            solver = adaptive.make_solver(stepper.make_step(sched, 1.0), True, rtol, atol, options, method=method)
-            y, lp = solver.integrate(float(t_span[0]), float(t_span[1]), x, torch.zeros(B, device=x.device))
-            self.last_solver_stats = {"attempts": solver.n_attempts, "accepted": solver.n_accepted}
-        else:
-            # fixed grid: one launch per tangent pass records every row's Jacobian, one launch estimates all of them
-            stepper = host_stepper.RowStepper(net, x.device, conditional, None)
-            div_rows = lambda A, lo, hi: _native.trace_estimate(A, kind, tuple(P[:, lo:hi] for P in probes))
-            # (the recorded Jacobians of a chunk of samples may take a quarter of the free device memory: cutting a batch
-            # into many small launches leaves their last rounds of tiles mostly empty)
-            y, lp = stepper.run_table_recorded(x, self._ode_table(t_span, method, options, MODE_EXACT), div_rows,
-                                               cond=conditional, max_bytes=max(1 << 30, self._estimator_budget(x.device) // 2))
+        y, lp = odeint.solve(self, x0, t_span, method, options, MODE_EXACT, atol, rtol, cond=conditional,
+                             estimator=(kind, probes), div_fn=lambda A: self._estimate_divergence(A, x0))
         return y, lp.view(-1, 1)
-
-    @staticmethod
-    def _estimator_budget(device) -> int:
-        """Bytes the recorded Jacobians of an attempted step may take: half of what the device has free right now."""
-        free, _ = torch.cuda.mem_get_info(device)
-        return free // 2
 
     @torch.no_grad()
     def log_prob(self, x0_samples, conditional=None, atol=1e-4, rtol=1e-4, method="dopri5",

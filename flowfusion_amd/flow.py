@@ -21,8 +21,8 @@ from typing import List, Optional, Tuple
 import torch
 from torch import nn
 
-from . import _native, adaptive, device_adaptive, generic, solvers
-from .fused import FusedNet, MODE_EXACT, MODE_HUTCH, MODE_STATE, activation_spec, require_fp32, within_envelope
+from . import _native, device_adaptive, odeint, solvers, trace_estimators
+from .fused import FusedNet, MODE_EXACT, MODE_HUTCH, MODE_STATE, activation_spec, within_envelope
 
 _DEFAULT_SAMPLE_METHOD = "dopri5"     # what odeint() picks when the reference passes no method
 
@@ -66,8 +66,8 @@ class _FlowBase(nn.Module):
         key = tuple(id(m) for m in self.layers) + tuple(repr(m) for m in self.layers if not isinstance(m, nn.Linear))
         return within_envelope(self, key, self._net)
 
-    def _solve_generic(self, x, t_span, method, options, mode, atol, rtol, cond, probe, raw_cond, affine):
-        """The same solve around ``self.velocity`` evaluated by torch: stage combinations, error norms and step
+    def _module_rhs(self, mode, cond, probe):
+        """``self.velocity`` evaluated by torch for the generic route (odeint.py): stage combinations, error norms and step
         control by the library (generic.py), divergences by autograd as in the reference (flow.py:122-166, 598-652)."""
         D = self.target_dimension
 
@@ -90,14 +90,7 @@ class _FlowBase(nn.Module):
                     div = sum(torch.autograd.grad(v[:, i].sum(), y, retain_graph=True)[0][:, i] for i in range(D))
             return v.detach(), div.detach()
 
-        if affine.get("in_shift") is not None:
-            x = (x - affine["in_shift"]) / affine["in_scale"]
-        extra = () if raw_cond is None else (raw_cond.detach().to(x.device, torch.float32),)
-        y, lp, stats = generic.solve(rhs, x, t_span, method, options, mode != MODE_STATE, atol, rtol, norm_only=extra)
-        self.last_solver_stats = stats
-        if affine.get("out_scale") is not None:
-            y = y * affine["out_scale"] + affine["out_shift"]
-        return y, lp
+        return rhs
 
     def _schedule(self, t, first=None):
         """(a, b, c1) for real times t (fp32, CPU): xdot = NET([x, t, cond]) -> a = 0, b = 1,
@@ -109,63 +102,43 @@ class _FlowBase(nn.Module):
             c1 = t[:, None] * w0[:, D][None, :] + b0[None, :]
             return torch.zeros_like(t), torch.ones_like(t), c1
 
-    def _table(self, t_span, method, options, mode, y0=None):
+    def _host_schedule(self):
+        """``_schedule`` for the host controller, with the host copy of the first layer taken once per solve."""
+        first = self._net().first_layer_cpu()
+        return lambda tr: self._schedule(tr, first)
+
+    def _device_schedule(self, device):
+        """``device_adaptive.ScheduleSpec`` of the device controller: xdot = NET([x, t, cond]) -> a = 0, b = 1,
+        c1 = w_t t + b1."""
+        D = self.target_dimension
+        w0t, b0 = self._net().time_columns(device, D, D + 1)
+        return device_adaptive.ScheduleSpec(_native.SCHED_FLOW, (0.0, 0.0, 0.0), True, None, 0.0, w0t, b0)
+
+    def _ode_table(self, t_span, method, options, mode, y0=None):
         plan = solvers.plan_ode(t_span, method, options, y0=y0)
         self._net().require_slots(int(plan.slot.max()) + 1, mode, f"method={method!r}")
         a, b, c1 = self._schedule(plan.t_eval)
         return solvers.build_table(plan, a, b, c1, self._net().width(mode))
 
+    _table = _ode_table       # the flows' older name, still used by the tests and scratch/
+
+    def _schedule_key(self):
+        """Everything besides the first layer that the evaluation table depends on: nothing."""
+        return ()
+
     def _norm_cond(self, conditional):
         return (conditional - self.conditional_shift) / self.conditional_scale
 
-    def _solve(self, x, t_span, method, options, mode, atol, rtol, cond=None, probe=None, raw_cond=None, **affine):
-        require_fp32(self, x, cond, probe, what="an ODE solve")
-        if not self._fusable():
-            return self._solve_generic(x, t_span, method, options, mode, atol, rtol, cond, probe, raw_cond, affine)
-        net = self._net()
-        if method in solvers.ALL_ADAPTIVE:
-            if any(v is not None for v in affine.values()):
-                raise AssertionError("affine epilogues are applied by the caller on the adaptive path")
-            t = t_span.double()
-            sign = -1.0 if bool(t[0] > t[-1]) else 1.0
-            # the reference keeps the raw conditional in the solver state (flow.py:779-796, 855-881)
-            extra = () if raw_cond is None else (raw_cond.detach().to(x.device, torch.float32),)
-            spec = None
-            if x.is_cuda and method in solvers.NATIVE_ADAPTIVE:
-                D = self.target_dimension
-                w0t, b0 = net.time_columns(x.device, D, D + 1)
-                spec = device_adaptive.ScheduleSpec(_native.SCHED_FLOW, (0.0, 0.0, 0.0), True, None, 0.0, w0t, b0)
-            if device_adaptive.supported(spec, x, net, mode, options):
-                # the whole loop on the device (device_adaptive.py): xdot = NET([x, t, cond]) -> a = 0, b = 1, c1 = w_t t + b1
-                y, lp, stats = device_adaptive.solve(net, spec, sign, mode, x, float(sign * t[0]), float(sign * t[-1]), rtol, atol,
-                                                     options, method, cond=cond, probe=probe, norm_only=extra)
-                self.last_solver_stats = stats
-                return y, lp
-            first = net.first_layer_cpu()
-            step = net.make_step(lambda tr: self._schedule(tr, first), sign, mode, x.device, cond=cond, probe=probe)
-            solver = adaptive.make_solver(step, mode != MODE_STATE, rtol, atol, options, norm_only=extra, method=method, sign=sign)
-            lp0 = torch.zeros(x.shape[0], device=x.device) if mode != MODE_STATE else None
-            y, lp = solver.integrate(float(sign * t[0]), float(sign * t[-1]),
-                                     x.detach().to(torch.float32).contiguous(), lp0)
-            self.last_solver_stats = {"attempts": solver.n_attempts, "accepted": solver.n_accepted}
-            return y, lp
-        key = ("flow-ode", tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items())), mode)
-        if (options or {}).get("grid_constructor") is not None:      # the grid may depend on y0: built per call
-            table = self._table(t_span, method, options, mode, y0=x).to(x.device)
-        else:
-            table = net.cached_table(key, x.device, lambda: self._table(t_span, method, options, mode))
-        y, lp, _ = net.integrate(x, table, mode, cond=cond, probe=probe, stage_slots=solvers.resolve_method(method).stages, **affine)
-        return y, (lp if mode != MODE_STATE else None)
+    def _solve(self, x, t_span, method, options, mode, atol, rtol, **kw):
+        """``odeint(self, x, t_span, ...)``: the flow's solve through the shared dispatcher (odeint.py)."""
+        return odeint.solve(self, x, t_span, method, options, mode, atol, rtol, **kw)
 
-    def _fused_sample(self, xT, conditional, method, options, atol, rtol, raw_cond=None):
+    def _fused_sample(self, xT, conditional, method, options, atol, rtol, norm_only=()):
         if torch.is_grad_enabled() and xT.requires_grad:
             raise NotImplementedError("gradients through the fused solve are not available; detach the input")
         method = _DEFAULT_SAMPLE_METHOD if method is None else method
         t_span = torch.tensor([1.0, 0.0], dtype=torch.float32)
-        if method in solvers.ALL_ADAPTIVE:
-            x, _ = self._solve(xT, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional, raw_cond=raw_cond)
-            return x * self.target_scale + self.target_shift
-        x, _ = self._solve(xT, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional,
+        x, _ = self._solve(xT, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional, norm_only=norm_only,
                            out_scale=self.target_scale, out_shift=self.target_shift)
         return x
 
@@ -174,31 +147,15 @@ class _FlowBase(nn.Module):
         extension, as on ScoreModel.log_prob): the signs of the library's counter-based normals keyed by ``seed`` and the
         GLOBAL row ``sample_offset + r`` -- drawn on the device and independent of how a batch is cut into shards
         (``distributed.flow_log_prob_sharded``)."""
-        if probe == "torch":
-            if seed is not None:
-                raise ValueError("seed= belongs to probe='philox' (the torch probe follows torch.manual_seed)")
-            return None
-        if probe != "philox":
-            raise ValueError(f"probe must be 'torch' or 'philox', not {probe!r}")
-        if not hutchinson:
-            raise ValueError("probe='philox' is the Hutchinson probe: pass hutchinson=True")
-        if seed is None:      # one draw of torch's generator, so torch.manual_seed still fixes the run
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return int(seed), int(sample_offset)
+        return trace_estimators.probe_rng(probe, seed, sample_offset, hutchinson,
+                                          "probe='philox' is the Hutchinson probe: pass hutchinson=True")
 
-    def _fused_forward(self, x, conditional, method, options, hutchinson, atol, rtol, raw_cond=None, probe_rng=None):
+    def _fused_forward(self, x, conditional, method, options, hutchinson, atol, rtol, norm_only=(), probe_rng=None):
+        """``norm_only``: the raw conditional, which the reference keeps in the solver state (flow.py:779-796, 855-881)."""
         t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
-        mode, probe = MODE_EXACT, None
-        if hutchinson and probe_rng is not None:
-            mode = MODE_HUTCH
-            z = _native.normal_fill(x.shape[0], x.shape[1], probe_rng[0], probe_rng[1], x.device,
-                                    noise_index=_native.PROBE_NOISE_INDEX)
-            probe = torch.where(z >= 0, 1.0, -1.0).to(torch.float32)
-        elif hutchinson:
-            mode = MODE_HUTCH
-            probe = torch.sign(torch.randn(x.shape)).to(x.device)
-        xT, logj = self._solve(x, t_span, method, options, mode, atol, rtol, cond=conditional, probe=probe,
-                               raw_cond=raw_cond)
+        probe = trace_estimators.hutchinson_probe(x, probe_rng) if hutchinson else None
+        xT, logj = self._solve(x, t_span, method, options, MODE_HUTCH if hutchinson else MODE_EXACT, atol, rtol,
+                               cond=conditional, probe=probe, norm_only=norm_only)
         return xT, logj.view(-1, 1)
 
 
@@ -320,7 +277,7 @@ class ConditionalODEFlow(_FlowBase):
         if gradients:
             raise NotImplementedError("sample(gradients=True) uses odeint_adjoint in the reference "
                                       "(flow.py:779-788); differentiable solves are out of scope")
-        return self._fused_sample(xT, self._norm_cond(conditional), method, options, atol, rtol, raw_cond=conditional)
+        return self._fused_sample(xT, self._norm_cond(conditional), method, options, atol, rtol, norm_only=(conditional,))
 
     def solve_ode_forward(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5,
                           method: str = "dopri5", options: Optional[dict] = None, adjoint: bool = False,
@@ -329,7 +286,7 @@ class ConditionalODEFlow(_FlowBase):
         if adjoint:
             raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
         return self._fused_forward(x, self._norm_cond(conditional), method, options, hutchinson, atol, rtol,
-                                   raw_cond=conditional, probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson))
+                                   norm_only=(conditional,), probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson))
 
     def log_prob(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,

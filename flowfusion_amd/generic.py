@@ -99,25 +99,6 @@ class ModuleStepper:
         return step
 
 
-def solve(rhs: Rhs, x: torch.Tensor, t_span: torch.Tensor, method: str, options, has_lp: bool, atol: float, rtol: float,
-          norm_only=()):
-    """``odeint(func, state, t_span, method=, atol=, rtol=, options=)`` for an external right-hand side: fixed-grid
-    methods (solvers.FIXED_METHODS) and adaptive dopri5.  Returns (y [B, D], dlogp [B] or None) at ``t_span[-1]``."""
-    from . import adaptive
-    _need_gpu(x)
-    stepper = ModuleStepper(rhs, has_lp)
-    if method in solvers.ALL_ADAPTIVE:
-        t = t_span.detach().to("cpu", torch.float32).double()
-        sign = -1.0 if bool(t[0] > t[-1]) else 1.0
-        solver = adaptive.make_solver(stepper.make_step(sign), has_lp, rtol, atol, options, norm_only=norm_only, method=method, sign=sign)
-        lp0 = torch.zeros(x.shape[0], device=x.device) if has_lp else None
-        y, lp = solver.integrate(float(sign * t[0]), float(sign * t[-1]), x.detach().to(torch.float32).contiguous(), lp0)
-        return y, lp, {"attempts": solver.n_attempts, "accepted": solver.n_accepted, "evaluations": stepper.n_evals}
-    plan = solvers.plan_ode(t_span, method, options, y0=x)
-    y, lp = stepper.run_plan(x, plan)
-    return y, lp, {"evaluations": stepper.n_evals}
-
-
 def euler_maruyama(drift: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], g_of_t: Callable[[torch.Tensor], torch.Tensor],
                    x: torch.Tensor, draw, T, epsilon, steps: int, progress=None):
     """The reverse-SDE loop of ``sample_sde`` (flowfusion/diffusion.py:539-563) for an external drift

@@ -1,0 +1,106 @@
+"""The one place where an ODE solve of a score model (diffusion.py) or a flow (flow.py) picks its route.
+
+* **generic**: a network no compiled kernel holds is evaluated by torch, the library steps around it (generic.py);
+* **fixed grid**: one fused launch per solve, the PopulationModel / flow affine maps in its prologue and epilogue;
+* **device controller**: the adaptive loop on the GPU (device_adaptive.py);
+* **host controller**: the adaptive loop in Python (adaptive.py), for what the device controller cannot describe.
+
+Hutch++ / XTrace solves take the same routes with the Jacobian of every evaluation row recorded (host_stepper.py).  The
+front ends supply only what differs between them: ``_fusable()`` / ``_net()``, ``_device_schedule(device)``,
+``_host_schedule()``, ``_ode_table(...)`` with ``_schedule_key()``, and ``_module_rhs(mode, cond, probe)`` for the generic
+route.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _native, adaptive, device_adaptive, solvers
+from ._native import MODE_EXACT, MODE_STATE
+from .fused import require_fp32
+from .generic import ModuleStepper, _need_gpu
+from .host_stepper import RowStepper
+
+
+def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=None, norm_only=(), estimator=None,
+          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None):
+    """``odeint(front, x, t_span, method=, atol=, rtol=, options=)``; returns (y [B, D], dlogp [B] or None) and sets
+    ``front.last_solver_stats`` (fused fixed-grid solves leave it alone).
+
+    ``norm_only``: state components the reference carries with a zero derivative (a flow's raw conditional), seen by the
+    adaptive error norm only.  ``estimator = (kind, probes)``: a Hutch++ / XTrace solve in MODE_EXACT (``div_fn(A)`` is its
+    estimate on the host controller; on the generic route the front end's module estimates by itself).  The affine maps
+    (PopulationModel*, flow sampling): ``(x - in_shift) / in_scale`` before the solve, ``y * out_scale + out_shift`` after
+    it -- on the host around the adaptive and generic routes, in the kernel's prologue / epilogue on fixed grids."""
+    if estimator is None:           # (the estimator solves have never refused other dtypes: they cast the state to fp32)
+        require_fp32(front, x, cond, probe, what="an ODE solve")
+    fused = front._fusable()
+    net = front._net() if fused else None
+    adaptive_method = method in solvers.ALL_ADAPTIVE
+    if fused and estimator is None and not adaptive_method:
+        key = (tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items())), mode) + front._schedule_key()
+        if (options or {}).get("grid_constructor") is not None:      # the grid may depend on y0: built per call
+            table = front._ode_table(t_span, method, options, mode, y0=x).to(x.device)
+        else:
+            table = net.cached_table(key, x.device, lambda: front._ode_table(t_span, method, options, mode))
+        y, lp, _ = net.integrate(x, table, mode, cond=cond, probe=probe, stage_slots=solvers.resolve_method(method).stages,
+                                 in_shift=in_shift, in_scale=in_scale, out_scale=out_scale, out_shift=out_shift)
+        return y, (lp if mode != MODE_STATE else None)
+    if in_shift is not None:
+        x = (x - in_shift) / in_scale
+    if fused and estimator is not None:
+        x = x.detach().to(torch.float32).contiguous()
+    if adaptive_method:
+        t = t_span.detach().to("cpu", torch.float32).double()
+        sign = -1.0 if bool(t[0] > t[-1]) else 1.0        # a decreasing span is solved in reversed time
+        norm_only = tuple(c.detach().to(x.device, torch.float32) for c in norm_only)
+    if not fused:
+        # generic: the front end's module evaluated by torch, every stage combination one ff_stage_combine launch
+        _need_gpu(x)
+        stepper = ModuleStepper(front._module_rhs(mode, cond, probe), mode != MODE_STATE)
+        if adaptive_method:
+            y, lp = _host_adaptive(front, stepper.make_step(sign), x, t, sign, method, options, mode, atol, rtol, norm_only)
+            front.last_solver_stats["evaluations"] = stepper.n_evals
+        else:
+            y, lp = stepper.run_plan(x, solvers.plan_ode(t_span, method, options, y0=x))
+            front.last_solver_stats = {"evaluations": stepper.n_evals}
+    elif not adaptive_method:
+        # Hutch++ / XTrace on a fixed grid: one launch per tangent pass records every row's Jacobian, one launch estimates
+        # all of them (the recorded Jacobians of a chunk of samples may take a quarter of the free device memory: cutting a
+        # batch into many small launches leaves their last rounds of tiles mostly empty)
+        kind, probes = estimator
+        div_rows = lambda A, lo, hi: _native.trace_estimate(A, kind, tuple(P[:, lo:hi] for P in probes))
+        y, lp = RowStepper(net, x.device, cond, None).run_table_recorded(
+            x, front._ode_table(t_span, method, options, MODE_EXACT), div_rows, cond=cond,
+            max_bytes=max(1 << 30, _estimator_budget(x.device) // 2))
+    else:
+        spec = front._device_schedule(x.device) if (x.is_cuda and method in solvers.NATIVE_ADAPTIVE) else None
+        if device_adaptive.supported(spec, x, net, mode, options) and (estimator is None or device_adaptive.estimator_bytes(
+                net, method, x.shape[0], *estimator) <= _estimator_budget(x.device)):
+            # the whole loop on the device: attempts, error norms, step control, the next attempt's table rows
+            y, lp, front.last_solver_stats = device_adaptive.solve(
+                net, spec, sign, mode, x, float(sign * t[0]), float(sign * t[-1]), rtol, atol, options, method, cond=cond,
+                probe=probe, norm_only=norm_only, estimator=estimator)
+        else:
+            # the host controller: one launch per attempted step, or per right-hand side for the estimators
+            step = (net.make_step(front._host_schedule(), sign, mode, x.device, cond=cond, probe=probe) if estimator is None
+                    else RowStepper(net, x.device, cond, div_fn).make_step(front._host_schedule(), sign))
+            y, lp = _host_adaptive(front, step, x, t, sign, method, options, mode, atol, rtol, norm_only)
+    if out_scale is not None:
+        y = y * out_scale + out_shift
+    return y, lp
+
+
+def _host_adaptive(front, step, x, t, sign, method, options, mode, atol, rtol, norm_only):
+    """The host controller around any of the three step functions (``FusedNet`` / ``RowStepper`` / ``ModuleStepper``)."""
+    has_lp = mode != MODE_STATE
+    solver = adaptive.make_solver(step, has_lp, rtol, atol, options, norm_only=norm_only, method=method, sign=sign)
+    lp0 = torch.zeros(x.shape[0], device=x.device) if has_lp else None
+    y, lp = solver.integrate(float(sign * t[0]), float(sign * t[-1]), x.detach().to(torch.float32).contiguous(), lp0)
+    front.last_solver_stats = {"attempts": solver.n_attempts, "accepted": solver.n_accepted}
+    return y, lp
+
+
+def _estimator_budget(device) -> int:
+    """Bytes the recorded Jacobians of an attempted step may take: half of what the device has free right now."""
+    free, _ = torch.cuda.mem_get_info(device)
+    return free // 2

@@ -126,3 +126,32 @@ def draw_probes_philox(n: int, like: torch.Tensor, seed: int, sample_offset: int
         raise ValueError("at most 32768 probes per set")
     zs = [_native.normal_fill(B, D, seed, sample_offset, like.device, noise_index=base + c) for c in range(n)]
     return torch.where(torch.stack(zs) >= 0, 1.0, -1.0).to(torch.float32)
+
+
+def hutchinson_probe(like: torch.Tensor, rng=None) -> torch.Tensor:
+    """The +-1 Hutchinson probe [B, D] of a log-density solve: drawn on the CPU and moved, as the reference does
+    (diffusion.py:701), or with ``rng = (seed, global index of row 0)`` the signs of the library's counter-based normals
+    (``ff_normal_fill`` with the reserved probe index), drawn on the device."""
+    if rng is None:
+        return torch.sign(torch.randn(like.shape)).to(like.device)
+    from . import _native
+    z = _native.normal_fill(like.shape[0], like.shape[1], rng[0], rng[1], like.device, noise_index=_native.PROBE_NOISE_INDEX)
+    return torch.where(z >= 0, 1.0, -1.0).to(torch.float32)
+
+
+def probe_rng(probe: str, seed, sample_offset: int, philox_ok: bool, refusal: str):
+    """``probe="torch"`` (default): None, the probes follow torch's generator.  ``probe="philox"`` (keyword-only extension of
+    the log-density methods): ``(seed, sample_offset)`` keying the counter-based probes by the GLOBAL row, so that they do not
+    depend on how a batch is cut into shards (``distributed.log_prob_sharded``); only where ``philox_ok`` (the model draws
+    probes at all), else ``ValueError(refusal)``."""
+    if probe == "torch":
+        if seed is not None:
+            raise ValueError("seed= belongs to probe='philox' (the torch probe follows torch.manual_seed)")
+        return None
+    if probe != "philox":
+        raise ValueError(f"probe must be 'torch' or 'philox', not {probe!r}")
+    if not philox_ok:
+        raise ValueError(refusal)
+    if seed is None:      # one draw of torch's generator, so torch.manual_seed still fixes the run
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return int(seed), int(sample_offset)
