@@ -55,6 +55,92 @@ def test_trace_estimate_kernel_against_the_torch_statement(generic, monkeypatch)
         assert float((got - TE.xtrace(flat, rep(S)))[ok].abs().max()) < 2e-6 * scale * max(1, r), (D, r)
 
 
+def _estimate_raw(A, kind, probes, misalign=False):
+    """ff_trace_estimate on A [n, B, D, D] with the Jacobians at a base one float past 16-byte alignment if `misalign`, and a
+    workspace filled with NaN: (estimates [n * B], whether the general kernel ran -- the LDS-tile kernels never touch the
+    workspace, the general one keeps its scratch there)."""
+    import ctypes
+    from flowfusion_amd import _native
+    n, B, D, _ = A.shape
+    code, p0, p1, r, m = _native.trace_kind_and_probes(kind, probes)
+    buf = torch.zeros(A.numel() + 4, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    jac = buf[1:1 + A.numel()] if misalign else buf[:A.numel()]
+    jac.copy_(A.reshape(-1).to(DEV))
+    assert (jac.data_ptr() % 16 == 4) == misalign
+    p0 = p0.to(DEV, torch.float32).contiguous()
+    p1 = None if p1 is None else p1.to(DEV, torch.float32).contiguous()
+    out = torch.full((n * B,), float("nan"), device=DEV)
+    ws = torch.full((int(_native.lib().ff_trace_workspace_floats(code, D, r, n * B)),), float("nan"), device=DEV)
+    a = _native.TraceArgs()
+    a.kind, a.dim, a.n_rows, a.r, a.m, a.batch = code, D, n, r, m, B
+    a.jac, a.probes0, a.probes1 = jac.data_ptr(), p0.data_ptr(), (0 if p1 is None else p1.data_ptr())
+    a.out, a.workspace = out.data_ptr(), ws.data_ptr()
+    rc = _native.lib().ff_trace_estimate(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == _native.FF_OK, rc
+    torch.cuda.synchronize()
+    return out.cpu(), bool(torch.isfinite(ws).any())
+
+
+def _tile_holds(kind, D, r):
+    """ff_trace_estimate's test for the LDS-tile path, restated from ff_trace_workspace_floats: the matrices and the scratch
+    of a tile (64 items up to 16 dimensions, 32 beyond) at a pitch of items + 1 words within 158 KiB."""
+    from flowfusion_amd import _native
+    code = _native.TRACE_HUTCHPP if kind == "hutchpp" else _native.TRACE_XTRACE
+    items = 64 if D <= 16 else 32
+    words = (items + 1) * (D * D + int(_native.lib().ff_trace_workspace_floats(code, D, r, 1)))
+    return D <= 32 and 4 * words <= 158 * 1024
+
+
+def test_trace_estimate_every_path_and_its_boundaries():
+    """Every path ff_trace_estimate can take, against the float64 torch statement: the LDS tile with the dimension compiled
+    in (1, 2, 3, 4, 8, 16; 32 on 32-item tiles), with a run-time dimension on 64-item tiles (5, 12, 15) and on 32-item
+    tiles (17, 24, 31), and the general kernel (beyond 32 dimensions, and where the tile outgrows the LDS).  Both sides of
+    the LDS limit, derived from ff_trace_workspace_floats (the largest r the tile holds for XTrace at 16 and 32 dimensions
+    and Hutch++ at 32, and r + 1) with the side each lands on asserted; item counts of 1, ITEMS - 1 and ITEMS + 1; and the
+    dword staging of a Jacobian base one float past 16-byte alignment (D * D % 4 == 0), bitwise the aligned result."""
+    from flowfusion_amd import trace_estimators as TE
+    torch.manual_seed(29)
+    cases = []                                                    # (kind, D, r, m, n_rows, B)
+    for D in (1, 2, 3, 4, 8, 16, 32, 5, 12, 15, 17, 24, 31, 40):
+        items = 64 if D <= 16 else 32
+        r = min(D, 2)
+        for n, B in ((1, 1), (1, items - 1), (1, items + 1), (3, items // 2 + 3)):
+            cases += [("hutchpp", D, r, 2, n, B), ("xtrace", D, r, 0, n, B)]
+    edges = []
+    for kind, D in (("xtrace", 16), ("xtrace", 32), ("hutchpp", 32)):
+        r = max(q for q in range(1, D + 1) if _tile_holds(kind, D, q))
+        assert r < D and not _tile_holds(kind, D, r + 1)
+        edges.append((kind, D, r))
+        items = 64 if D <= 16 else 32
+        for q in (r, r + 1):
+            cases += [(kind, D, q, 3, 1, items + 1), (kind, D, q, 3, 2, items - 1)]
+    print(f"\n[trace] LDS-tile limits (kind, D, largest r on the tile): {edges}")
+    for kind, D, r, m, n, B in cases:
+        A = torch.randn(n, B, D, D)
+        S = torch.sign(torch.randn(r, B, D))
+        for _ in range(100):                                      # (redraw rank-deficient probe sets: B may be 1)
+            bad = ~well_posed(S)
+            if not bad.any():
+                break
+            S[:, bad] = torch.sign(torch.randn(r, int(bad.sum()), D))
+        probes = (S, torch.sign(torch.randn(m, B, D))) if kind == "hutchpp" else (S,)
+        rep = lambda P: P.unsqueeze(1).expand(P.shape[0], n, B, D).reshape(P.shape[0], n * B, D).double()
+        flat = A.reshape(n * B, D, D).double()
+        want = TE.hutchpp(flat, rep(probes[0]), rep(probes[1])) if kind == "hutchpp" else TE.xtrace(flat, rep(S))
+        ok = well_posed(S).repeat(n)
+        assert ok.all(), (kind, D, r, B)
+        scale = max(1.0, float(A.abs().sum(dim=(2, 3)).max())) * (max(1, r) if kind == "xtrace" else 1)
+        tag = (kind, D, r, m, n, B)
+        got, general = _estimate_raw(A, kind, probes)
+        assert general == (not _tile_holds(kind, D, r)), tag + (general,)
+        assert bool(torch.isfinite(got[ok]).all()), tag
+        assert float((got.double() - want)[ok].abs().max()) < 2e-6 * scale, tag
+        if (D * D) % 4 == 0 and not general:
+            got_m, general_m = _estimate_raw(A, kind, probes, misalign=True)
+            assert not general_m and torch.equal(got_m[ok], got[ok]), tag + ("misaligned",)
+
+
 def _with_probes(monkeypatch, probes):
     from flowfusion_amd import trace_estimators as TE
     queue = [p.to(DEV) for p in probes]
