@@ -18,12 +18,10 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
-# FF_BUILD_FULL=1 (round 2's instance set, for A/B measurements) builds beside the product library, not over it
-FULL = os.environ.get("FF_BUILD_FULL", "") not in ("", "0")
-GEN = PKG / "_build" / ("gen_full" if FULL else "gen")
-OBJ = PKG / "_build" / ("obj_full" if FULL else "obj")
+GEN = PKG / "_build" / "gen"
+OBJ = PKG / "_build" / "obj"
 LIBDIR = PKG / "lib"
-LIB = LIBDIR / ("libflowfusion_amd_full.so" if FULL else "libflowfusion_amd.so")
+LIB = LIBDIR / "libflowfusion_amd.so"
 
 ARCH = "gfx950"
 
@@ -37,8 +35,6 @@ ARCH = "gfx950"
 #
 # Round 3: the clean build was cut from 265 translation units / 68 CPU-minutes to what a BASELINE configuration, a
 # reference demo shape or a documented option of the reference's constructors reaches.
-# FF_BUILD_FULL=1 restores the round-2 set (compiled-in activations, 5-6 hidden layers on the split family, ...) for
-# A/B measurements.
 INSTANCES = [
     # narrow networks: 32 samples per wavefront, one wavefront per SIMD (width 64; width 128 beyond 16 dimensions)
     (32, h, d, c, t, 1, 8, 0)
@@ -48,7 +44,7 @@ INSTANCES = [
     for t in (0, 1)
 ] + [
     # 128-wide networks on the 16-column tile (round 3: the reference's own notebook networks are 3x128; the 32-column
-    # kernels ran them at ~65 % of the MFMA rate with one wavefront per SIMD -- measured scratch/tile16_h128.py: +8..12 %
+    # kernels ran them at ~65 % of the MFMA rate with one wavefront per SIMD -- measured profiles/r03/tile16_h128.txt: +8..12 %
     # at 2^20 samples with two wavefronts per SIMD, notebook log_prob 19.1 -> 16.7 ms).  THREE wavefronts per SIMD with four
     # chunks in flight (149 registers, no spill; eight chunks spill at the 168-register cap): another +1..5 %, 16.1 ms --
     # at this width the activations' VALU time is half of the MFMA time, and a third wavefront hides more of it
@@ -74,7 +70,7 @@ INSTANCES = [
 ] + [
     # Non-default activations (`activation=` of the reference constructors; its code, docs and notebooks only ever use
     # SiLU).  ACT = 9 chooses the function at run time (the chosen kind's stages run back to back behind a wave-uniform
-    # switch): measured against the compiled-in variants (scratch/act_bench.py, profiles/r03/act_bench.txt) it costs
+    # switch): measured against the compiled-in variants (profiles/r03/act_bench.txt) it costs
     # 0-3 % for state-only solves at width 256, 9-14 % at width 128 and is what the 512-wide kernels (over a minute of
     # compile time each) use; with tangent columns at width 256 it costs 16 % (the switch at every activation site spills
     # 187 registers at two wavefronts per SIMD, so it would run one): THAT shape keeps a compiled-in instantiation per
@@ -84,25 +80,11 @@ INSTANCES = [
     (16, 256, 8, 4, 0, 2, 8, 9), (16, 512, 16, 4, 0, 1, 4, 9), (16, 512, 16, 4, 1, 1, 4, 9),
 ] + [
     (16, 256, 8, 4, 1, 2, 8, act) for act in range(1, 9)
-] + ([
-    # round-2 extras (FF_BUILD_FULL): width 256 on the 32-wide tile (A/B runs, FF_TILE=32); up to 32 conditional inputs
-    # at width 512 (the wide catch-alls serve them otherwise); the narrow 32-column shapes the 16-column tile replaced;
-    # every non-SiLU activation compiled in per width <= 256 and mode, and run-time choice everywhere
-    (32, 256, 8, 0, 0, 1, 8, 0), (32, 256, 8, 0, 1, 1, 8, 0),
-    (16, 512, 16, 8, 0, 1, 4, 0), (16, 512, 16, 8, 1, 1, 4, 0),
-    (16, 256, 8, 4, 1, 1, 8, 9),
-] + [
-    (32, 128, d, c, t, 1, 8, 0) for d in (4, 8) for c in (0, 8) for t in (0, 1)
-] + [
-    (tile, h, d, c, t, wps, 8, act)
-    for act in range(1, 9)
-    for (tile, h, d, c, t, wps) in ((32, 64, 16, 8, 0, 1), (32, 64, 16, 8, 1, 1), (32, 128, 16, 8, 0, 1), (32, 128, 16, 8, 1, 1),
-                                    (16, 256, 8, 4, 0, 2))
-] if FULL else [])
+]
 
 # Wide catch-alls (kernel template WIDE: cooperative at every batch size, hidden operands read from LDS): networks up
 # to 1024 wide, states up to 128 dimensions, up to 64 conditional inputs.  (TILE, H, DREGS, CREGS, TANGENTS)
-WIDE_INSTANCES = [(16, 1024, d, c, t) for (d, c) in (((16, 8), (32, 16)) if FULL else ((32, 16),)) for t in (0, 1)]
+WIDE_INSTANCES = [(16, 1024, 32, 16, t) for t in (0, 1)]
 
 
 def _wide_name(tile, h, d, c, t) -> str:
@@ -115,17 +97,12 @@ def _wide_name(tile, h, d, c, t) -> str:
 # Frozen in round 3 at what the BASELINE configurations and the reference's demo networks reach: 1-4 hidden layers
 # (configs 2, 3 and 5 are 4x256, the notebooks 3x128); two parts: every mode for states of up to 16 dimensions, state-only
 # (Euler-Maruyama: config 5) for 17-32 dimensions, 128-wide instances; three parts: state-only, 256 wide.
-if FULL:
-    SPLIT_INSTANCES = [(nh, t, parts, 1, 256) for parts in (3, 2) for nh in (1, 2, 3, 4, 5, 6) for t in (0, 1, 2)] + \
-                      [(nh, t, 2, 2, 256) for nh in (1, 2, 3, 4, 5, 6) for t in (0, 1, 2)] + \
-                      [(nh, t, parts, dt, 128) for (parts, dt) in ((3, 1), (2, 1), (2, 2)) for nh in (1, 2, 3, 4) for t in (0, 1, 2)]
-else:
-    # three parts (fp32-class): the state-only kernels -- the second record of the headline workload is what round 1 asked
-    # of this option; log-densities under precision= take the two-part kernels or f32
-    SPLIT_INSTANCES = [(nh, 0, 3, 1, 256) for nh in (1, 2, 3, 4)] + \
-                      [(nh, t, 2, 1, 256) for nh in (1, 2, 3, 4) for t in (0, 1, 2)] + \
-                      [(nh, 0, 2, 2, 256) for nh in (1, 2, 3, 4)] + \
-                      [(nh, t, 2, 1, 128) for nh in (1, 2, 3, 4) for t in (0, 1, 2)]
+# Three parts (fp32-class): the state-only kernels -- the second record of the headline workload is what round 1 asked
+# of this option; log-densities under precision= take the two-part kernels or f32.
+SPLIT_INSTANCES = [(nh, 0, 3, 1, 256) for nh in (1, 2, 3, 4)] + \
+                  [(nh, t, 2, 1, 256) for nh in (1, 2, 3, 4) for t in (0, 1, 2)] + \
+                  [(nh, 0, 2, 2, 256) for nh in (1, 2, 3, 4)] + \
+                  [(nh, t, 2, 1, 128) for nh in (1, 2, 3, 4) for t in (0, 1, 2)]
 
 
 # ---- test-only libraries (tests/test_gpu_skew.py; csrc/ff_skew.h) -------------------------------------------------------
@@ -144,27 +121,8 @@ VARIANTS = {
 }
 
 
-if os.environ.get("FF_BUILD_NOSLP", "") not in ("", "0"):
-    # one-off A/B (round 4; scratch/slp_ab.py): the headline, config-3 and notebook kernels with hipcc's SLP
-    # vectoriser off -- it packs the SiLU tail's scalar products into v_pk_mul_f32 / v_pk_fma_f32 between the MFMAs
-    VARIANTS["noslp"] = dict(defines=["-fno-slp-vectorize"],
-                             instances=[(16, 256, 4, 0, 0, 2, 8, 0), (16, 256, 4, 0, 1, 2, 8, 0), (16, 128, 4, 0, 0, 3, 4, 0),
-                                        (16, 128, 4, 0, 1, 3, 4, 0)], wide=[], split=[])
-
-
-if os.environ.get("FF_BUILD_EXP_DPP", "") not in ("", "0"):
-    VARIANTS["dpp"] = dict(defines=["-DFF_EXP_DPP=1"], instances=[(16, 256, 4, 0, 1, 2, 8, 0), (16, 128, 4, 0, 1, 3, 4, 0)], wide=[], split=[])
-
-
 def variant_lib(name: str) -> Path:
     return LIBDIR / f"libflowfusion_amd_{name}.so"
-
-
-def _has_four_slot_twin(inst) -> bool:
-    """128-wide kernels for states of up to 16 dimensions: a twin with four stage slots (two workgroups per CU, +26 % on the
-    opt-in arithmetic at notebook widths).  Built with FF_BUILD_FULL only since round 3 (12 translation units of a frozen,
-    opt-in family); the launcher's `launch4` pointer is then null and every launch takes the seven-slot kernel."""
-    return FULL and inst[2] in (2, 3) and inst[3] == 1 and inst[4] == 128
 
 
 def _split_name(nh, t, parts=3, dt=1, width=256) -> str:
@@ -173,8 +131,8 @@ def _split_name(nh, t, parts=3, dt=1, width=256) -> str:
 
 def _has_coop(h, act=0) -> bool:
     """Instances that get a cooperative twin: the blocks of a layer (H / 32) must split four ways.  (Of the
-    non-SiLU instantiations only the run-time-choice one at width 256 gets one, and every one of round 2's set: build time.)"""
-    return (h // 32) % 4 == 0 and (act == 0 or (h <= 256 and (act == 9 or FULL)))
+    non-SiLU instantiations only the run-time-choice one at width 256 gets one: build time.)"""
+    return (h // 32) % 4 == 0 and (act == 0 or (h <= 256 and act == 9))
 
 
 def _hipcc() -> str:
@@ -244,23 +202,19 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None)
         name = _wide_name(tile, h, d, c, t)
         files.append(_write(GEN / f"{name}.hip", _launcher_unit(
             name, "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, 1, 4, 0, true, true>")))
-    split_units = [(i, False) for i in SPLIT_INSTANCES] + [(i, True) for i in SPLIT_INSTANCES if _has_four_slot_twin(i)]
-    for (nh, t, parts, dt, width), four in split_units:
-        name = _split_name(nh, t, parts, dt, width) + ("_s4" if four else "")
+    for nh, t, parts, dt, width in SPLIT_INSTANCES:
+        name = _split_name(nh, t, parts, dt, width)
         files.append(_write(GEN / f"{name}.hip", _launcher_unit(
-            name, "ff_mlp_ode_split.hpp", f"split::mlp_ode_split_kernel<{nh}, {t}, {parts}, {dt}, {width}{', 4' if four else ''}>")))
+            name, "ff_mlp_ode_split.hpp", f"split::mlp_ode_split_kernel<{nh}, {t}, {parts}, {dt}, {width}>")))
     decls = "\n".join(
         [f"int launch_{_inst_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES] +
         [f"int launch_{_inst_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES
          if _has_coop(i[1], i[7])] +
         [f"int launch_{_wide_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in WIDE_INSTANCES] +
-        [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES] +
-        [f"int launch_{_split_name(*i)}_s4(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES
-         if _has_four_slot_twin(i)]
+        [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES]
     )
     split_rows = ",\n".join(
-        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_split_name(*i)}, "{_split_name(*i)}", '
-        + (f"launch_{_split_name(*i)}_s4" if _has_four_slot_twin(i) else "nullptr") + "}" for i in SPLIT_INSTANCES
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_split_name(*i)}, "{_split_name(*i)}"}}' for i in SPLIT_INSTANCES
     )
     rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, {i[7]}, launch_{_inst_name(*i)}, "{_inst_name(*i)}", '
@@ -274,7 +228,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None)
             for i in WIDE_INSTANCES
         )
     if not SPLIT_INSTANCES:          # (a test variant without the family: one inert row, count 0 -- no zero-length array)
-        split_rows = '    {0, 0, 0, 0, 0, nullptr, "", nullptr}'
+        split_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 namespace ff {{
@@ -389,7 +343,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
     srcs = _gen_sources()
     units = [(s, OBJ, ()) for s in srcs]
     extra = {}
-    if variants and not FULL:
+    if variants:
         for name, v in VARIANTS.items():
             gen, obj = PKG / "_build" / f"gen_{name}", PKG / "_build" / f"obj_{name}"
             obj.mkdir(parents=True, exist_ok=True)
@@ -402,7 +356,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         done = dict(zip([(u[0], u[1]) for u in order],
                         ex.map(lambda u: _compile(u[0], _deps_hash(u[0]), verbose, u[1], u[2]), order)))
-    _link([done[(s, OBJ)] for s in srcs], LIB, PKG / "_build" / ("link_full.stamp" if FULL else "link.stamp"), verbose)
+    _link([done[(s, OBJ)] for s in srcs], LIB, PKG / "_build" / "link.stamp", verbose)
     for name, (vs, obj, _) in extra.items():
         _link([done[(s, obj)] for s in vs], variant_lib(name), PKG / "_build" / f"link_{name}.stamp", verbose)
     return LIB

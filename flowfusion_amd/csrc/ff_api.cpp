@@ -110,11 +110,7 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
     const int need_t = mode != FF_MODE_STATE;
     // Preference among kernels that fit: narrowest width first (it dominates the FLOPs); at equal
     // width the 16x16x4 two-waves-per-SIMD kernels (measured ~3% faster than 32x32x2 at width 256),
-    // then fewer first-layer k-steps.  FF_TILE=32|16 pins the tile (experiments).
-    const char* pin = getenv("FF_TILE");
-    const int pin_tile = pin ? atoi(pin) : 0;
-    // FF_ACT_ANY=1 / 0 (A/B runs on a library built with FF_BUILD_FULL): only / never the run-time-choice instantiations
-    const char* pin_any = getenv("FF_ACT_ANY");
+    // then fewer first-layer k-steps.
     int best = -1;
     for (int i = 0; i < ff::g_n_kernels; ++i) {
         const ff::KernelEntry& k = ff::g_kernels[i];
@@ -122,8 +118,6 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
         const int need_c = cond_dim > 0 ? ff::regs_for(k.tile, cond_dim) : 0;
         if (k.H < wmax || k.dregs < need_d || k.cregs < need_c || k.tangents != need_t ||
             !(k.act == activation || (k.act == 9 && activation != FF_ACT_SILU))) continue;
-        if (pin_tile && k.tile != pin_tile) continue;
-        if (pin_any && activation != FF_ACT_SILU && (k.act == 9) != (atoi(pin_any) != 0)) continue;
         if (best < 0) { best = i; continue; }
         const ff::KernelEntry& b = ff::g_kernels[best];
         const int kc = k.dregs * (64 / k.tile) + k.cregs * (64 / k.tile);     // first-layer features covered
@@ -419,11 +413,8 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
     const long long spw = k.tangents == 0 ? 128 : (k.tangents == 1 ? 64 : 8 * (16 / (1 + nt)));
     const long long grid = (a->batch + spw - 1) / spw;
     if (grid > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
-    // the caller may say how many stage slots the table uses (ff_ode_args.stage_slots): up to four, the twin that keeps
-    // four slots on chip and shares a CU between two workgroups serves the launch (same arithmetic, same results)
-    const bool four = k.launch4 && a->stage_slots >= 1 && a->stage_slots <= 4 && !getenv("FF_SPLIT_NO_TWIN");
-    const unsigned lds = (unsigned)ff::split::lds_map(plan->width, plan->n_hidden, k.parts, k.dt, four ? 4 : 0).total;
-    const int herr = (four ? k.launch4 : k.launch)(&ka, (unsigned)grid, lds, (hipStream_t)hip_stream);
+    const unsigned lds = (unsigned)ff::split::lds_map(plan->width, plan->n_hidden, k.parts, k.dt).total;
+    const int herr = k.launch(&ka, (unsigned)grid, lds, (hipStream_t)hip_stream);
     if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
     return FF_OK;
 }
@@ -433,8 +424,8 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
 // Small batches: when the tiles of the batch would leave at least half the chip's 1024 SIMDs without one, the
 // cooperative twin (one tile per WORKGROUP, the layer's rows split over its four wavefronts) finishes an evaluation
 // in about a third of the time.  Same packed weights, bitwise the same results.  FF_COOP=0 / 1 pins the choice.
-// One rule for whole launches and for tails (below), fitted to measurements at widths 128 / 256 / 512 (scratch/tail_split.py,
-// scratch/tail_margin.py, scratch/coop_threshold.py; in units of a full round of the one-wavefront kernel):
+// One rule for whole launches and for tails (below), fitted to measurements at widths 128 / 256 / 512 (profiles/r03/:
+// tail_split.txt, tail_margin.txt, coop_threshold.txt; in units of a full round of the one-wavefront kernel):
 //   one-wavefront kernel, n tiles:  ceil(n / 1024) / wps      (n tiles run with that many wavefronts per SIMD; a wavefront
 //                                                              does not finish sooner for having fewer neighbours)
 //   twin, n tiles:                  max(least, c0 + n / (0.95 chip)),  chip = 1024 wps tiles in flight,
@@ -445,7 +436,7 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
 // dispatcher fills SIMDs evenly, a wavefront does not finish sooner for having fewer neighbours than wps allows).
 // The cooperative twin -- a tile per workgroup, bitwise the same results -- gets through about 0.8-0.9 of a chip's worth
 // of tiles in a round's time and never needs less than ~0.3 of it.  Whenever that is the shorter of the two, the
-// leftover rows go to the twin as a second launch (scratch/tail_split.py: up to +34 % just above a whole number of
+// leftover rows go to the twin as a second launch (profiles/r03/tail_split.txt: up to +34 % just above a whole number of
 // rounds, +5 % at eight rounds).  FF_TAIL_SPLIT=0 switches it off (A/B runs, tests).
 struct LaunchChoice {
     bool coop;                 // the main launch is the cooperative twin (or the wide catch-all)
@@ -470,11 +461,7 @@ static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, boo
     if (!coop && k.launch_coop != nullptr && k.wps > 0 && !jac_out) {
         const long long rem = tiles % chip;
         const char* pin = getenv("FF_TAIL_SPLIT");
-        if (tiles > chip && rem > 0 && !(pin && atoi(pin) == 0)) {
-            bool split = twin_wins(rem);
-            if (const char* m = getenv("FF_TAIL_MAX")) split = rem <= atoll(m);          // (experiments: scratch/tail_split.py)
-            if (split) tail_tiles = rem;
-        }
+        if (tiles > chip && rem > 0 && !(pin && atoi(pin) == 0) && twin_wins(rem)) tail_tiles = rem;
     }
     return LaunchChoice{coop, tiles - tail_tiles, tail_tiles};
 }

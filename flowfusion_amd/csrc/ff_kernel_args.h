@@ -48,7 +48,6 @@ struct KernelArgs {
     int jac_all;         // 1: jac_out is [n_evals, batch, dim, dim] and every evaluation row writes its Jacobian
     int act_kind;        // FF_ACT_* (read by the run-time-choice instantiations only)
     float act_p0, act_p1;   // parameters of the hidden activation (FF_ACT_LEAKY_RELU / ELU / SOFTPLUS)
-    unsigned long long* debug_stamps;   // diagnostic builds only (FF_DEBUG_STAMPS); NULL in the product
     const int* gate;     // ff_ode_args.gate: device word read at kernel start; 0 = this launch does nothing (NULL = run)
 };
 

@@ -288,17 +288,10 @@ __device__ __forceinline__ void act_stage(ActGroup& g, float* __restrict__ dst, 
         act_stage_kind<TANGENTS, ACT, STAGE>(g, dst, is_tangent, value_lane_bytes, spec);
         return;
     } else {
-#ifdef FF_DEBUG_LINEAR_ACT      // timing experiment only: identity activation (wrong results)
-    if constexpr (STAGE == 3) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dst[i] = g.pre[i];
-    }
-    return;
-#endif
     // Written as scalar code; what the compiler makes of it is its own business: hipcc's SLP vectoriser packs part of this
     // tail into v_pk_mul_f32 / v_pk_fma_f32 (headline kernel: 138 packed instructions, 38 of them between MFMAs; with
     // -fno-slp-vectorize 92 remain -- the f32x4 stage algebra -- and 2 between MFMAs).  Measured both ways in round 4
-    // (scratch/slp_ab.py, profiles/r04/slp_ab.txt): headline 1224.0 vs 1226.5 ms, config 3 2521.4 vs 2520.8 ms, the
+    // (profiles/r04/slp_ab.txt): headline 1224.0 vs 1226.5 ms, config 3 2521.4 vs 2520.8 ms, the
     // 128-wide notebook kernels 59.88 vs 59.97 and 199.31 vs 199.33 ms, bitwise the same results -- packing neither costs
     // nor saves here, so the build keeps the compiler's default.
 #pragma unroll
@@ -314,11 +307,7 @@ __device__ __forceinline__ void act_stage(ActGroup& g, float* __restrict__ dst, 
                 // silu'(a) = s + a s (1 - s) = s (1 + a (1 - s)),  s = sigmoid(a): two fmas
                 const float w = __builtin_fmaf(-g.pre[i], g.r[i], g.pre[i]);
                 const float d = __builtin_fmaf(g.r[i], w, g.r[i]);
-#ifdef FF_EXP_DPP       // timing experiment only (Hutchinson pairs: the value column is the lane to the left)
-                g.dv[i] = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, d), 0x111, 0xf, 0xf, false);
-#else
                 g.dv[i] = __builtin_amdgcn_ds_bpermute(value_lane_bytes, __builtin_bit_cast(int, d));
-#endif
             } else {
                 dst[i] = g.pre[i] * g.r[i];
             }
@@ -331,19 +320,6 @@ __device__ __forceinline__ void act_stage(ActGroup& g, float* __restrict__ dst, 
 }
 constexpr int kActStages = 5;
 constexpr int kTailSlots = 2 * kActStages;   // slots granted after a layer's last MFMA
-
-#ifdef FF_DEBUG_STAMPS
-// Diagnostic build: cycle stamps (s_memtime) of wavefront 0, written to a buffer nothing else reads.
-__device__ __forceinline__ void ff_stamp(unsigned long long* buf, int& n, bool on)
-{
-    __builtin_amdgcn_sched_barrier(0);
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    buf[(on && n < 4095) ? n : 4095] = t;      // branch-free: everyone else scribbles on the last slot
-    ++n;
-}
-#endif
 
 // One layer:  acc[ob] = W[ob,:] . B  over the layer's chunk stream, consumed in the order of
 // ff_layout.h.  `ring` holds the next RING chunks on entry and on exit (of the following
@@ -365,19 +341,17 @@ __device__ __forceinline__ void ff_stamp(unsigned long long* buf, int& n, bool o
 //                  zero C operand); otherwise they come in holding the layer's bias, which the MFMA chain then
 //                  adds for free (the caller loads the next layer's bias into a block once it has been consumed)
 template <int TILE, int RING, int KR, int NOB, bool WRAP, bool ZERO_INIT, int LAST_PHYS = Tile<TILE>::PHYS, class PreFn,
-          class SlotFn, class LastFn, class DbgFn>
+          class SlotFn, class LastFn>
 __device__ __forceinline__ void run_layer(f32x4 (&ring)[RING][Tile<TILE>::PHYS], const Stream& ws, int lane16,
                                           int sbyte, const float (&B)[KR], BlockAcc<TILE> (&acc)[NOB],
-                                          PreFn&& pre_block, SlotFn&& slot_fn, LastFn&& last, DbgFn&& dbg)
+                                          PreFn&& pre_block, SlotFn&& slot_fn, LastFn&& last)
 {
     typedef Tile<TILE> T;
     constexpr LayerGeom L = layer_geom(KR, NOB, T::RB / 4);
     constexpr int CB = 1024 * T::PHYS;              // bytes per chunk
-    dbg();
     static_for<L.CPAD>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
         constexpr int slot = c % RING;
-        if constexpr (c == L.GA * L.NOB && c > 0) dbg();
         if constexpr (c < L.NC) {
             constexpr int g = chunk_group(L, c);
             constexpr int ob = chunk_block(L, c);
@@ -401,16 +375,13 @@ __device__ __forceinline__ void run_layer(f32x4 (&ring)[RING][Tile<TILE>::PHYS],
                 });
             });
             if constexpr (c == L.NC - 1) {
-                dbg();
                 last(acc[NOB - 1]);
                 static_for<kTailSlots>([&](auto tt) {
                     slot_fn(std::integral_constant<int, 4 * L.NC * T::PHYS + decltype(tt)::value>{}, acc);
                 });
-                dbg();
             }
         }
         constexpr int nxt = c + RING;
-#ifndef FF_DEBUG_NO_WLOADS      // timing experiment only: never refill the ring (wrong results)
         static_for<T::PHYS>([&](auto pp) {
             constexpr int p = decltype(pp)::value;
             if constexpr (WRAP && nxt >= L.CPAD)
@@ -418,7 +389,6 @@ __device__ __forceinline__ void run_layer(f32x4 (&ring)[RING][Tile<TILE>::PHYS],
             else
                 ring[slot][p] = sload(ws, lane16, sbyte + nxt * CB + p * 1024);
         });
-#endif
         // Pin the stream order: MFMAs and vector-memory loads may not be scheduled across this
         // point (VALU / SALU / transcendental / DS work of the activations may), so every load
         // is issued exactly one ring length ahead of its use.
@@ -627,10 +597,6 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
 #pragma unroll
         for (int o = 0; o < NB; ++o) hacc[o] = load_bias_acc<TILE>(ts, q16b, 128 + o * 128);
     }
-#ifdef FF_DEBUG_STAMPS
-    int stamp_n = 0;
-    const bool stamp_on = (blockIdx.x == 0 && threadIdx.x == 0 && args.debug_stamps != nullptr);
-#endif
 
     bool bad_slot = false;
     // Cooperative twin: the exchange buffer of the NEXT activation hand-over.  It alternates over the whole launch, not per
@@ -673,12 +639,6 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
             }
         }
 
-#ifdef FF_DEBUG_STAMPS
-        auto dbg = [&]() { ff_stamp(args.debug_stamps, stamp_n, stamp_on); };
-        dbg();
-#else
-        auto dbg = []() {};
-#endif
         float net[NOB_OUT * RB];
         if constexpr (COOP) {
             // ---- cooperative evaluation: NB / 4 blocks of every layer per wavefront, activations exchanged through LDS --
@@ -875,7 +835,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
             run_layer<TILE, RING, K1, NB, false, false>(
                 ring, ws, lane16, 0, y, hacc, [&](auto ob) { refill(ws, nbyte, ob); },
                 [&](auto mm, const BlockAcc<TILE> (&acc)[NB]) { own_slot(G1{}, mm, acc); },
-                [&](const BlockAcc<TILE>& acc) { park_and_refill(ws, nbyte, acc); }, dbg);
+                [&](const BlockAcc<TILE>& acc) { park_and_refill(ws, nbyte, acc); });
         }
         // ---- hidden -> hidden ------------------------------------------------------------
         for (int l = 0; l < args.n_hidden - 1; ++l) {
@@ -890,7 +850,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
                     prev_slot(mm);
                     own_slot(GH{}, mm, acc);
                 },
-                [&](const BlockAcc<TILE>& acc) { park_and_refill(ws, nbyte, acc); }, dbg);
+                [&](const BlockAcc<TILE>& acc) { park_and_refill(ws, nbyte, acc); });
         }
         // ---- output layer ----------------------------------------------------------------
         // the hidden accumulators are idle from here to the next evaluation's first layer: fetch its c1 now
@@ -924,8 +884,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
 #pragma unroll
                 for (int r = 0; r < RB; ++r)
                     net[(NOB_OUT - 1) * RB + r] = acc.reg(r) + bias[(NOB_OUT - 1) & 1].reg(r);
-            },
-            dbg);
+            });
         }   // !COOP
 
         // ---- RHS and stage bookkeeping -----------------------------------------------------

@@ -114,10 +114,7 @@ __device__ __forceinline__ float from_value_lane(float v)
 // below): left to the list scheduler the same instructions clump -- four or five behind one MFMA, none behind the next
 // six.  Value columns: SiLU(a).  Tangent columns (forward-mode derivative through the same weights): a' * SiLU'(a of
 // the sample's value column), SiLU'(a) = s + a s (1 - s).
-#ifndef FF_SPLIT_AHEAD
-#define FF_SPLIT_AHEAD 1
-#endif
-constexpr int kAhead = FF_SPLIT_AHEAD;      // groups between the LDS read of a weight fragment and its MFMAs
+constexpr int kAhead = 1;      // groups between the LDS read of a weight fragment and its MFMAs
 
 struct UnitState {
     float a0, a1, t0, t1, h0, h1, o0, o1;      // (h, o: tangent kernels only)
@@ -146,9 +143,6 @@ __device__ __forceinline__ void unit_micro(float pre0, float pre1, UnitState& u,
     constexpr float NLOG2E = -1.44269504088896340736f;
     constexpr bool TANGENTS = TM != 0;
     constexpr int OP = micro_op(TANGENTS, NP, J);
-#ifdef FF_SPLIT_SKIP_OPS        // timing experiments only: bit OP set = that micro-op is left out (wrong results)
-    if constexpr (((FF_SPLIT_SKIP_OPS) >> OP) & 1) return;
-#endif
     if constexpr (OP == M_LOAD) {              // pre-activations out of the accumulator tile (AGPR -> VGPR copies, here)
         u.a0 = pre0;
         u.a1 = pre1;
@@ -230,10 +224,7 @@ __device__ __forceinline__ void unit_micro(float pre0, float pre1, UnitState& u,
 // allows (one with three parts; up to two with two parts, whose k-steps are half as long).  Units of span kind 1 read
 // row tiles 0 and 1 of the span's OWN output, complete after groups 0 and 1: they start behind group 1.
 constexpr int kMaxSpanGaps = 16 * 12, kMaxPerGap = 5;
-#ifndef FF_SPLIT_SPACING
-#define FF_SPLIT_SPACING 2
-#endif
-constexpr int kMicroSpacing = FF_SPLIT_SPACING;      // gaps between consecutive micro-ops of a unit
+constexpr int kMicroSpacing = 2;      // gaps between consecutive micro-ops of a unit
 FF_HD constexpr int gaps_per_group(int parts) { return 2 * products_of(parts); }
 // gap i of a group that opens a granule issues one of the wavefront's `ndma` LDS-DMAs (its quarter of the granule:
 // parts * granule_groups / 4 fragments -- 6 / 4 at width 256, 3 / 2 at width 128)
@@ -302,16 +293,15 @@ __device__ __forceinline__ void dma_fragment(unsigned lds_byte, const void* g, i
 // NH (hidden layers) is a compile-time parameter: with the layer sequence unrolled the evaluation loop is one
 // straight-line body and the accumulator tiles keep their registers (a run-time layer loop made hipcc shuffle all 256
 // accumulator registers at every control-flow join).
-// NSL = stage slots kept in LDS: slots_on_chip(DT), or 4 for the four-slot twins (two workgroups per CU)
-template <int NH, int TM, int NP = 3, int DT = 1, int HW = 256, int NSL = slots_on_chip(DT)>
-__global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ? 2 : 1) void mlp_ode_split_kernel(const KernelArgs args)
+template <int NH, int TM, int NP = 3, int DT = 1, int HW = 256>
+__global__ __launch_bounds__(256, 1) void mlp_ode_split_kernel(const KernelArgs args)
 {
     static_assert(HW == 256 || HW == 128, "on-chip width: 256 or 128");
     static_assert(TM >= 0 && TM <= 2, "0: state only, 1: Hutchinson column pairs, 2: exact trace (unit tangents)");
     constexpr bool TANGENTS = TM != 0;
     static_assert(NP == 2 || NP == 3, "two (round-to-nearest) or three (truncation) bf16 parts per operand");
     static_assert(DT == 1 || (DT == 2 && NP == 2), "states of up to 32 dimensions: two-part kernels only (LDS)");
-    constexpr int NSLOT = NSL;                         // stage slots kept in LDS: 7 / 4
+    constexpr int NSLOT = slots_on_chip(DT);           // stage slots kept in LDS: 7 / 4
     constexpr int NR = row_tiles(HW);                  // row tiles of 16 rows: 16 (width 256) / 8
     constexpr int NS = ksteps(HW);                     // k-steps of 32 features: 8 / 4
     constexpr int H = HW;
@@ -319,8 +309,6 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
     constexpr int GB = granule_bytes(NP, HW);          // 24 KiB (three parts) / 16 KiB (two) at width 256, half that at 128
     constexpr int GG = gaps_per_group(NP);             // MFMAs of a group: 12 / 6
     constexpr int NDMA = dma_count(NP, HW);            // fragments of a granule this wavefront fetches
-    // weight buffers in LDS: 3 (the DMA runs two granules ahead) or, in the three-part four-slot twins, 2 (one granule ahead)
-    constexpr int NBUF = (NSL == 4 && DT == 1 && has_four_slot_twin(NP, DT, HW)) ? weight_buffers(NP, 4) : kBuffers;
     typedef const __attribute__((address_space(4))) RowHdr* HdrPtr;
 
     // a cleared gate word (launches enqueued ahead of a device-side decision: ff_adaptive.hip) makes this launch a no-op
@@ -333,7 +321,7 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
     const int col = lane & 15;                         // column within a column block
     const int lane16 = lane * 16;
     const int D = args.dim, C = args.cond_dim;
-    const LdsMap M = lds_map(H, NH, NP, DT, NSL);
+    const LdsMap M = lds_map(H, NH, NP, DT);
 
     // ---- column roles: this lane serves one column of each of the two column blocks ---------------------------------
     const long long wave = (long long)blockIdx.x * 4 + wv;
@@ -453,21 +441,6 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
             }
         }
     }
-#ifdef FF_SPLIT_STAMPS          // diagnostic builds only (scratch/kbench_split.hip): cycle stamps of wavefront 0, evaluations 2 and 3
-    int stamp_i = 0;
-    bool stamp_on = false;
-#define FF_STAMP()                                                                                         \
-    do {                                                                                                   \
-        if (stamp_on) {                                                                                    \
-            const unsigned long long t_ = __builtin_readcyclecounter();                                    \
-            if (lane == 0) args.debug_stamps[stamp_i] = t_;                                                \
-            ++stamp_i;                                                                                     \
-        }                                                                                                  \
-    } while (0)
-#else
-#define FF_STAMP() do {} while (0)
-#endif
-
     // ---- weight pipeline state (all wave-uniform) -----------------------------------------------------------------
     const unsigned char* const wbase = (const unsigned char*)args.wpack;
     const long long wbytes = (long long)granules_per_eval(NH, DT, HW) * GB;
@@ -482,7 +455,7 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
     };
     FF_SKEW_HOLD(wv == kSkewWave, 1);                  // (test builds, ff_skew.h: this wavefront starts late ...)
     fetch_c1(0);
-    for (int g = 0; g < NBUF - 1; ++g) {               // the first NBUF - 1 granules into their buffers
+    for (int g = 0; g < kBuffers - 1; ++g) {           // the first kBuffers - 1 granules into their buffers
 #pragma unroll
         for (int f = 0; f < NDMA; ++f) dma_fragment(g * GB + my_frag + f * 1024, wbase + dpos + my_frag + f * 1024, lane16);
         dpos += GB;
@@ -529,8 +502,8 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
             // The stream position is periodic in the evaluation loop, so hipcc would compute all ~300 fragment
             // addresses of an evaluation once, ahead of the loop, and keep them in (spilled) SGPRs: hide the bases.
             asm volatile("" : "+s"(rbuf));
-            unsigned wb = rbuf + (NBUF - 1) * GB;
-            if (wb >= NBUF * GB) wb -= NBUF * GB;      // granule + NBUF - 1 -> the buffer read before this one
+            unsigned wb = rbuf + (kBuffers - 1) * GB;
+            if (wb >= kBuffers * GB) wb -= kBuffers * GB;      // granule + kBuffers - 1 -> the buffer read before this one
             dsrc = wbase + dpos + my_frag;
             ddst = wb + my_frag;
             asm volatile("" : "+s"(dsrc), "+s"(ddst));
@@ -540,17 +513,14 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
         if constexpr (GQ == GRG - kAhead) {
             // everything but the NDMA DMAs issued in this granule has landed, and this wavefront's reads of the current
             // buffer have returned: after the barrier the next granule is visible to all and the previous buffer is free
-            if constexpr (NBUF == 2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // (one granule ahead: all of it)
-            else if constexpr (NDMA == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+            if constexpr (NDMA == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
             else if constexpr (NDMA == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
             else if constexpr (NDMA == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-#ifndef FF_SPLIT_NOBARRIER       // timing experiment only (with FF_SPLIT_NODMA)
             __builtin_amdgcn_s_barrier();
-#endif
             FF_SKEW_HOLD(wv == kSkewWave, 1);          // (... and is late behind every granule barrier)
             rbuf += GB;
-            if (rbuf >= NBUF * GB) rbuf = 0;
+            if (rbuf >= kBuffers * GB) rbuf = 0;
             wa_next = lane16 + rbuf;
         }
         sfor<GG>([&](auto ii) {
@@ -560,25 +530,16 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
             constexpr int bp = (pr == 1 || pr == 4) ? 1 : (pr == 3 ? 2 : 0);
             acc[cb] = mm(wq[0][wp], b[cb][bp], acc[cb]);
             constexpr int part = read_part(NP, I);
-#ifdef FF_SPLIT_NOWREAD          // timing experiment only: one group's fragments serve the whole granule (wrong results)
-            if constexpr (part >= 0 && GQ == 0) {
-#else
             if constexpr (part >= 0) {
-#endif
                 constexpr int T = GQ + kAhead;                          // fragments of the group kAhead groups on
                 if constexpr (T >= GRG) wq[kAhead][part] = *(const u32x4*)(lds + wa_next + ((T - GRG) * NP + part) * 1024);
                 else wq[kAhead][part] = *(const u32x4*)(lds + wa + (T * NP + part) * 1024);
             }
-#ifndef FF_SPLIT_NODMA           // timing experiment only: never refresh the weight buffers (wrong results)
             if constexpr (GQ == 0 && dma_gap(NP, HW, I))
                 dma_fragment(ddst + dma_index(NP, I) * 1024, dsrc + dma_index(NP, I) * 1024, lane16);
-#endif
             fill(ii);
             __builtin_amdgcn_sched_barrier(0);
         });
-#ifdef FF_SPLIT_NOWREAD
-        if constexpr (GQ == 0)
-#endif
 #pragma unroll
         for (int a = 0; a < kAhead; ++a)
 #pragma unroll
@@ -589,16 +550,6 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
 
     u32x4 bf[2][2][NP];                                // B fragments [k-step parity][column block][part] in use / in preparation
     UnitState us[8];                                   // activation units in flight
-#ifdef FF_SPLIT_SKIP_OPS
-#pragma unroll
-    for (int i = 0; i < 8; ++i) us[i] = UnitState{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int k = 0; k < NP; ++k) bf[i][j][k] = u32x4{0u, 0u, 0u, 0u};
-#endif
 
     // The micro-ops the plan `KIND` pins to gap G of a span: the units turn row tiles (2 sn, 2 sn + 1) of `T` into the
     // fragments of k-step sn.  Unit u: column block u >> 2, word u & 3 = registers 2 (u & 1), 2 (u & 1) + 1 of row tile
@@ -645,17 +596,8 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
             } else {
                 sfor<NR>([&](auto tt) {
                     constexpr int rt = decltype(tt)::value;
-#ifdef FF_SPLIT_STAMP_GROUPS    // diagnostic: a stamp per group of k-step 3 (every hidden layer)
-                    if constexpr (s == 3) FF_STAMP();
-#endif
                     group(std::integral_constant<int, rt % GRG>{}, Cc[rt], bf[s & 1], [&](auto ii) {
                         constexpr int G = rt * GG + decltype(ii)::value;
-#ifdef FF_SPLIT_STAMP_GAPS      // diagnostic: a stamp behind every MFMA of groups 0 and 1 of k-step 3
-                        if constexpr (s == 3 && rt < 2) FF_STAMP();
-#endif
-#ifdef FF_SPLIT_UNITS_PARITY      // diagnostic: the activation units run in the k-steps of one parity only (wrong results)
-                        if constexpr (s % 2 != (FF_SPLIT_UNITS_PARITY)) return;
-#endif
                         if constexpr (s < NS - 1)       // the operands of the next k-step, out of the layer before
                             act_gap(std::integral_constant<int, 0>{}, std::integral_constant<int, G>{},
                                     std::integral_constant<int, s + 1>{}, P, bf[(s + 1) & 1]);
@@ -669,16 +611,11 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
                 P[2 * s + 2][0] = P[2 * s + 2][1] = bias_tile(refill, 2 * s + 2);
                 P[2 * s + 3][0] = P[2 * s + 3][1] = bias_tile(refill, 2 * s + 3);
             }
-            FF_STAMP();
         });
     };
 
     bool bad_slot = false;
     for (int e = 0; e < args.n_evals; ++e) {
-#ifdef FF_SPLIT_STAMPS
-        stamp_on = args.debug_stamps && blockIdx.x == 0 && wv == 0 && (e == 2 || e == 3);
-#endif
-        FF_STAMP();
         HdrPtr hdr = (HdrPtr)(args.etab + (size_t)e * args.etab_stride);
         const float a_e = hdr->a, b_e = hdr->b;
         const uint32_t flags = hdr->flags;
@@ -718,7 +655,6 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
                 split2<NP>(v[2], v[3], yf[0][cb], 2 * t + 1);
             }
 
-        FF_STAMP();
         // ---- layer 1: [state | conditional] (one k-step) -> H, accumulators A already hold c1_e --------------------
         sfor<DT>([&](auto kk) {
             constexpr int k1 = decltype(kk)::value;                      // k-step of the first layer
@@ -735,7 +671,6 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
             });
         });
 
-        FF_STAMP();
         // ---- hidden -> hidden layers, ping-pong A -> B -> A ..., then the output layer ------------------------------
         // refill address of the set being READ by layer j (1-based; j = NH is the output layer): the bias of the next
         // layer that writes that set -- layer j+1 of this evaluation if it is a hidden one, else the first layer of the
@@ -760,7 +695,6 @@ __global__ __launch_bounds__(256, (NSL == 4 && has_four_slot_twin(NP, DT, HW)) ?
             }
         });
 
-        FF_STAMP();
         // ---- right-hand side and stage bookkeeping ------------------------------------------------------------------
         // (a row naming a slot beyond the NSLOT on chip -- behind them sit the parked stage input and the state -- is
         // refused: nothing is stored, the status word says so)

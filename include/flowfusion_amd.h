@@ -96,8 +96,8 @@ extern "C" {
 /* bits OR-ed into ff_ode_args.status by a launch */
 #define FF_STATUS_NAN      1u   /* a final state holds a NaN                                */
 #define FF_STATUS_BAD_SLOT 2u   /* an evaluation row named a stage slot the kernel does not
-                                   keep on chip (>= FF_MAX_SLOTS; >= 4 for the plans and twins
-                                   with four slots): that row's right-hand side was NOT stored,
+                                   keep on chip (>= FF_MAX_SLOTS; >= 4 for the plans with four
+                                   slots): that row's right-hand side was NOT stored,
                                    the results are invalid                                  */
 
 /* evaluation-row flag bits (word 3 of the row header) */
@@ -188,11 +188,9 @@ typedef struct ff_ode_args {
                                 for all rows at once and combined with the tableau's weights by the caller. */
     int32_t      stage_slots; /* stage slots the table uses (highest slot index + 1, <= FF_MAX_SLOTS); 0 = unknown.
                                  Plans whose kernel keeps fewer slots on chip than FF_MAX_SLOTS (FF_PREC_BF16X2 with dim > 16:
-                                 4) require the table to stay within them (a larger value is FF_ERR_UNSUPPORTED); for the others
-                                 a value <= 4 lets the launcher pick a twin that trades unused slots for occupancy.  The value is
-                                 a PROMISE: a row that names a slot the chosen kernel does not keep is refused by the kernel
-                                 (FF_STATUS_BAD_SLOT, nothing stored) -- a wrong hint is an error, not a no-op.  With a correct
-                                 hint the results do not depend on it. */
+                                 4) require the table to stay within them (a larger value is FF_ERR_UNSUPPORTED).  A row that
+                                 names a slot the kernel does not keep is refused by the kernel (FF_STATUS_BAD_SLOT, nothing
+                                 stored).  With a correct hint the results do not depend on it. */
     const int32_t* gate;     /* optional DEVICE word read when the kernel starts: 0 = this launch does nothing.  For launches
                                 enqueued ahead of a decision taken on the device (ff_mlp_ode_adaptive); NULL = run. */
 } ff_ode_args;

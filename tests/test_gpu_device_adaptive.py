@@ -381,10 +381,11 @@ def test_gate_word_makes_a_launch_a_no_op(prec):
 
 
 def test_rows_naming_a_slot_off_chip_are_refused():
-    """the stage slot of a row was used unchecked.  f32 kernels keep FF_MAX_SLOTS = 7; the four-slot twins
-    of the split family keep 4 and are chosen from the caller's `stage_slots` promise: a dopri5 table behind a promise of
-    4 used to overwrite the parked stage input and the state in LDS.  Now the row is refused and the status word says so;
-    plans with four slots reject a larger promise before any launch."""
+    """the stage slot of a row was used unchecked.  f32 kernels keep FF_MAX_SLOTS = 7, and so do the split
+    family's kernels for states of up to 16 dimensions; a row naming a slot beyond them used to overwrite the parked stage
+    input and the state in LDS.  Now the row is refused and the status word says so.  The caller's `stage_slots` promise
+    does not change which kernel serves the launch, and plans with four slots (17-32 dimensions) reject a larger promise
+    before any launch."""
     from flowfusion_amd import _native
     sm, _, _ = _seeded_score_model(6, 0, [128, 128], "VPSDE", True, 3)
     x = torch.randn(300, 6, device=DEV)
@@ -396,20 +397,17 @@ def test_rows_naming_a_slot_off_chip_are_refused():
     assert rc == 0 and int(status.item()) == 0
     rc, _ = _raw_launch(sm, x, bad.to(DEV), status=status)
     assert rc == 0 and int(status.item()) & _native.STATUS_BAD_SLOT
-    # the four-slot twin behind a wrong promise
+    # a wrong promise on a seven-slot split kernel: the kernel keeps every slot the table names, nothing is refused
     sm.precision = "bf16x2"
     dp = sm._ode_table(torch.tensor([1.0, 1e-3]), "dopri5_fixed", {"step_size": 0.25}, 0).to(DEV)      # slots 0..5
     status.zero_()
     rc, lied = _raw_launch(sm, x, dp, stage_slots=4, status=status)
     flagged = bool(int(status.item()) & _native.STATUS_BAD_SLOT)
     status.zero_()
-    rc2, out = _raw_launch(sm, x, dp, stage_slots=6, status=status)      # an honest promise: the seven-slot kernel
+    rc2, out = _raw_launch(sm, x, dp, stage_slots=6, status=status)      # an honest promise
     want, _ = sm.sample_ode_from_base(x, method="dopri5_fixed", options={"step_size": 0.25})
     assert rc == 0 and rc2 == 0 and int(status.item()) == 0 and torch.equal(out, want)
-    # a library with the four-slot twins (FF_BUILD_FULL) serves the false promise with a twin, which refuses rows 4 and 5; the
-    # default library has no twin, the seven-slot kernel serves the launch and the promise did not matter -- never a silent
-    # wrong answer in between
-    assert flagged or torch.equal(lied, want)
+    assert not flagged and torch.equal(lied, want)
     # plans that keep four slots (17-32 dimensions) reject a larger promise
     sw, _, _ = _seeded_score_model(20, 0, [128, 128], "VPSDE", True, 4)
     sw.precision = "bf16x2"

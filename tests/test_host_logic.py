@@ -382,8 +382,8 @@ def test_activation_plumbing_matches_oracle(act, built_library):
     sm = D.ScoreModel(D.MLP(5, 2, 8, [48, 64], activation=act), D.VESDE(), no_sigma=False).eval()
     net = sm._net()
     plan = _native.plan_words(net.plan(MODE_EXACT))
-    # the plan carries THIS activation; the kernel either has it compiled in (name suffix _a<FF_ACT code>, FF_BUILD_FULL)
-    # or chooses it at run time from the plan (suffix _a9: one instantiation per width and mode since round 3)
+    # the plan carries THIS activation; the kernel either has it compiled in (name suffix _a<FF_ACT code>: the 256-wide
+    # divergence kernels) or chooses it at run time from the plan (suffix _a9)
     assert plan[8] == net.act[0] != _native.ACT_SILU
     assert built_library.ff_kernel_name(plan[6]).endswith((b"_a%d" % net.act[0], b"_a9"))
     so = O.ScoreOracle(O.mlp_params_from_state_dict(sm.state_dict()), O.VE(dtype=torch.float64), no_sigma=False,
