@@ -6,23 +6,29 @@ model, MLP 4x256 (embedding 8, no conditionals), 100-step RK4 (torchdiffeq's "rk
 network evaluations per sample), batch 2^20 per GPU, random-init weights (seed 0), synthetic
 standard-normal base samples resident in HBM.  One "step" = one full solve of the batch.
 
-    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the steps, writes its outputs (--dump-outputs) and prints the
+line.  Everything else the line can carry takes runs of its own and is measured or checked only with
+--full: the CPU baselines and the parity against the CPU oracle, rank invariance, the split-precision
+records, the other BASELINE configurations, the streaming helpers and the committed HBM traffic.
 
 N > 1: one process per GPU, every rank solves its own 2^20-sample shard (weak scaling) and the
 shards meet in one RCCL all-gather per step, inside the timed region.  Rank 0 prints ONE JSON line.
-After the timed loop the N > 1 run also solves the two BASELINE configurations that are WORDED for a
-node -- configs[3] (64-dim flow, 2^22 rows sharded N ways) and configs[4] (conditional 32-dim VE,
-1000-step Euler-Maruyama, 2^20 rows sharded N ways, noise keyed by the global row) -- one all-gather
-each, under `extra_configs`, and checks that a rank's rows equal a single-launch solve of those rows
-(`rank_invariant`).  Host threads are capped at usable_cores() // N per rank.
+With --full, after the timed loop the N > 1 run also solves the BASELINE configurations that are
+WORDED for a node -- configs[3] (64-dim flow, 2^22 rows sharded N ways) and configs[4] (conditional
+32-dim VE, 1000-step Euler-Maruyama, 2^20 rows sharded N ways, noise keyed by the global row) -- one
+all-gather each, under `extra_configs`, and checks that a rank's rows equal a single-launch solve of
+those rows (`rank_invariant`).  Host threads are capped at usable_cores() // N per rank.
 
 `roofline`: the path is a dense fp32 contraction (1.3e6 FLOP per algorithmic HBM byte), so the
 bounding roofline is the fp32 MFMA peak; `achieved` = algorithmic FLOPs of one launch (2 x MACs of
 the Linear layers x 400 evaluations x batch) / the kernel's launch duration measured with HIP
-events on the launch stream.  `cpu_baseline`: the CPU oracle (unfused torch ops + Python stepping
-loop, i.e. the reference's CPU algorithm restated) timed on the host cores on a bounded sample.
+events on the launch stream in the timed steps.  `cpu_baseline` (--full): the CPU oracle
+(unfused torch ops + Python stepping loop, i.e. the reference's CPU algorithm restated) timed on the
+host cores on a bounded sample.
 """
 import argparse
 import json
@@ -666,11 +672,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=1 << 20, help="samples per GPU")
-    ap.add_argument("--cpu-batch", type=int, default=32768, help="samples for the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else the line can carry (see the module "
+                         "docstring); a plain run only sets up, warms up, times the steps, dumps and prints")
+    ap.add_argument("--cpu-batch", type=int, default=32768, help="--full: samples for the CPU baseline (0 = skip)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (gloo: rehearsal of the multi-rank path on one GPU)")
     ap.add_argument("--no-extras", dest="extras", action="store_false",
-                    help="skip the one-launch timings of BASELINE configs 3, 4, 5 (N = 1 only)")
+                    help="--full: keep only the CPU baselines, the parity and the rank-invariance checks")
     ap.add_argument("--watchdog-seconds", type=float, nargs=2, default=(900.0, 300.0),
                     help="N > 1: patience with the sharded extras / the adaptive extra before the line is printed without them")
     ap.add_argument("--test-desert-rank", type=int, default=-1,
@@ -786,13 +795,15 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = {"kernel_ms_avg": [float(t[0]) for t in allr], "allgather_ms_avg": [float(t[1]) for t in allr]}
-    # rank invariance of the headline: this rank's first 256 rows as a launch of their own, and as they arrived in the
-    # gathered tensor, equal the rows of the timed solve bit for bit
-    head, _ = sm.sample_ode_from_base(z[:256].contiguous(), method="rk4", options=opts)
-    rank_invariant = bool(torch.equal(head, x[:256]))
+    # --full: rank invariance of the headline: this rank's first 256 rows as a launch of their own, and as they arrived in
+    # the gathered tensor, equal the rows of the timed solve bit for bit
+    rank_invariant = None
+    if args.full:
+        head, _ = sm.sample_ode_from_base(z[:256].contiguous(), method="rk4", options=opts)
+        rank_invariant = bool(torch.equal(head, x[:256]))
     sharded = None
     hung = False
-    if multi:
+    if multi and args.full:
         rank_invariant &= bool(torch.equal(gathered[rank * B: rank * B + 256].to(device), x[:256]))
         flag = torch.tensor([1.0 if rank_invariant else 0.0], device=gather_dev, dtype=torch.float64)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)                   # the headline's invariance, over all ranks
@@ -859,16 +870,17 @@ def main():
                          "algorithmic_hbm_GBps": alg_bytes / (kernel_ms_avg * 1e-3) / 1e9,
                          "hbm_frac_of_8TBps": alg_bytes / (kernel_ms_avg * 1e-3) / 1e9 / PEAK_HBM_GBS},
         }
-        out["rank_invariant"] = rank_invariant
+        if args.full:
+            out["rank_invariant"] = rank_invariant
         out["host_threads_per_rank"] = host_threads
         if per_rank is not None:
             out["per_rank"] = per_rank
         if sharded is not None:
             out["extra_configs"] = sharded
-        # `traffic` cannot be measured by this process (PMC counters need a rocprofv3 pass of their own): it is the
+        # --full: `traffic` cannot be measured by this process (PMC counters need a rocprofv3 pass of their own): it is the
         # committed result of tools/profile_round.sh for this kernel at this batch, and says so
         traffic_file = ROOT / "profiles" / "hbm_traffic.json"
-        if traffic_file.exists():
+        if args.full and traffic_file.exists():
             tf = json.loads(traffic_file.read_text())
             if tf.get("batch") == B and kernel_name.split("_m")[-1].split("_")[0] in tf.get("kernel", ""):
                 out["roofline"]["traffic"] = tf.get("bytes_per_launch")
@@ -876,7 +888,7 @@ def main():
                     "file": "profiles/hbm_traffic.json", "from": tf.get("source"), "commit": tf.get("commit"),
                     "note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (tools/profile_round.sh), "
                             "not measured by this run"}
-        if args.cpu_batch > 0 and not multi:      # CPU baseline and oracle parity: rank 0 of the 1-GPU run only
+        if args.full and args.cpu_batch > 0 and not multi:      # CPU baseline and oracle parity: rank 0 of the 1-GPU run only
             ref, zc, cb = cpu_baseline(sm, args.cpu_batch, opts)
             out["cpu_baseline"] = cb
             # parity of the timed configuration: GPU vs oracle on the same base samples
@@ -917,7 +929,7 @@ def main():
             _, _, cb1 = cpu_baseline(sm, 2048, opts, budget_s=10.0, threads=1)
             out["cpu_baseline_1thread"] = cb1
             torch.set_num_threads(host_threads)
-        if args.extras and not multi:
+        if args.full and args.extras and not multi:
             out["split_precision_record"] = split_precision_record(device, z, opts, args.steps, 1, x, "bf16x3")
             out["split_precision_record_bf16x2"] = split_precision_record(device, z, opts, args.steps, 1, x, "bf16x2")
             if args.cpu_batch > 0:

@@ -395,7 +395,7 @@ def test_bench_four_ranks_rehearsal_on_one_gpu():
     W = 4
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(W), "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(root / "bench.py"), "--gpus", str(W), "--backend", "gloo", "--single-device",
-           "--steps", "1", "--warmup", "0", "--cpu-batch", "0", "--batch", "16384",
+           "--full", "--steps", "1", "--warmup", "0", "--cpu-batch", "0", "--batch", "16384",
            "--c3-rows", "6100", "--c3-steps", "6", "--adaptive-rows", "3001",
            "--c4-rows", "4100", "--c4-steps", "8", "--c5-rows", "8200", "--c5-steps", "24"]       # ragged shards on purpose
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(root))
@@ -459,7 +459,7 @@ def test_bench_multi_rank_branch_under_rccl_with_one_rank():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--group-of-one", "--steps", "2", "--warmup", "1",
-           "--cpu-batch", "0", "--batch", "16384", "--c3-rows", "6100", "--c3-steps", "6", "--adaptive-rows", "3001",
+           "--full", "--cpu-batch", "0", "--batch", "16384", "--c3-rows", "6100", "--c3-steps", "6", "--adaptive-rows", "3001",
            "--c4-rows", "4100", "--c4-steps", "8", "--c5-rows", "8200", "--c5-steps", "24"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
@@ -492,7 +492,7 @@ def test_bench_line_survives_a_collective_that_never_completes():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device",
-           "--steps", "1", "--warmup", "0", "--cpu-batch", "0", "--batch", "8192", "--c3-rows", "2100", "--c3-steps", "4",
+           "--full", "--steps", "1", "--warmup", "0", "--cpu-batch", "0", "--batch", "8192", "--c3-rows", "2100", "--c3-steps", "4",
            "--c4-rows", "2100", "--c4-steps", "4", "--c5-rows", "2100", "--c5-steps", "8", "--adaptive-rows", "2001",
            "--watchdog-seconds", "600", "8", "--test-desert-rank", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(root))

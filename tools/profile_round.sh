@@ -12,9 +12,9 @@ STAGE=${2:-all}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 if [ "$STAGE" != "pmc" ]; then
-python bench.py --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --steps 3 --warmup 1 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench done: $(cut -c1-120 "$OUT/bench.json")"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python bench.py --steps 2 --warmup 1 --cpu-batch 0 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python bench.py --steps 2 --warmup 1 --full --cpu-batch 0 \
     > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err"
 python tools/filter_rocprof.py "$OUT/trace"
 echo "kernel trace done"
@@ -23,7 +23,7 @@ if [ "$STAGE" = "trace" ]; then exit 0; fi
 i=0
 for SET in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES" "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA" \
            "SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS"; do
-    rocprofv3 --pmc $SET --output-format csv -d "$OUT/pmc$i" -- python bench.py --steps 1 --warmup 0 --cpu-batch 0 \
+    rocprofv3 --pmc $SET --output-format csv -d "$OUT/pmc$i" -- python bench.py --steps 1 --warmup 0 --full --cpu-batch 0 \
         > "$OUT/pmc$i.json" 2> "$OUT/pmc$i.err"
     python tools/filter_rocprof.py "$OUT/pmc$i"
     echo "pmc pass $i ($SET) done"

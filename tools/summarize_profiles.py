@@ -115,7 +115,7 @@ def main(src: Path, dst: Path):
                 entry["mfma_pipe_busy_fraction"] = per_launch["SQ_VALU_MFMA_BUSY_CYCLES"] / (cycles * 256 * 4)
         kernels[trim(name)] = entry
     summary = {
-        "command": "rocprofv3 --pmc <counter set> --output-format csv -- python bench.py --steps 1 --warmup 0 --cpu-batch 0"
+        "command": "rocprofv3 --pmc <counter set> --output-format csv -- python bench.py --steps 1 --warmup 0 --full --cpu-batch 0"
                    "   (one pass per counter set; tools/profile_round.sh); clock = GRBM_GUI_ACTIVE / 8 / duration of the "
                    "same kernel's longest launch in the kernel-trace pass (profiled passes clock slightly lower)",
         "correction": "MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE reports 1/2 of the bytes of a coalesced "
