@@ -88,7 +88,8 @@ class OdeArgs(ctypes.Structure):
 
 
 STATUS_NAN, STATUS_BAD_SLOT = 1, 2          # FF_STATUS_*
-SCHED_FLOW, SCHED_VE, SCHED_VP, SCHED_SUBVP = 0, 1, 2, 3     # FF_SCHED_*
+SCHED_FLOW, SCHED_VE, SCHED_VP, SCHED_SUBVP, SCHED_FOURIER = 0, 1, 2, 3, 4     # FF_SCHED_*
+PAIR_KERNEL_BASE = 0x10000                                  # FF_PAIR_KERNEL_BASE
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -260,6 +261,19 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_adapt_host_row.restype = ctypes.c_int
     L.ff_adapt_host_row.argtypes = [ctypes.POINTER(AdaptConfig), ctypes.c_float, ctypes.POINTER(ctypes.c_float),
                                     ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
+    L.ff_pair_kernel_count.restype = ctypes.c_int
+    L.ff_pair_kernel_name.restype = ctypes.c_char_p
+    L.ff_pair_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_pair_plan.restype = ctypes.c_int
+    L.ff_mlp_pair_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                   ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pair_wpack_floats.restype = ctypes.c_size_t
+    L.ff_mlp_pair_wpack_floats.argtypes = [ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pair_wpack.restype = ctypes.c_int
+    L.ff_mlp_pair_wpack.argtypes = [ctypes.POINTER(PlanStruct)] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [
+        ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    L.ff_mlp_row_width.restype = ctypes.c_int
+    L.ff_mlp_row_width.argtypes = [ctypes.POINTER(PlanStruct)]
     L.ff_adapt_host_transition.restype = ctypes.c_int
     L.ff_adapt_host_transition.argtypes = [ctypes.POINTER(AdaptConfig), ctypes.POINTER(AdaptState), ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_float)]
@@ -320,6 +334,51 @@ def kernel_name(plan: PlanStruct) -> str:
     """ff_plan_kernel_name: the instantiation a plan selects."""
     n = lib().ff_plan_kernel_name(ctypes.byref(plan))
     return n.decode() if n else "?"
+
+
+def make_pair_plan(dim: int, cond_dim: int, hidden: List[int]) -> PlanStruct:
+    """ff_mlp_pair_plan: the two-network kernel for a state of ``dim`` = 2D dimensions (raises if none holds it)."""
+    p = PlanStruct()
+    arr = (ctypes.c_int * len(hidden))(*hidden)
+    rc = lib().ff_mlp_pair_plan(dim, cond_dim, len(hidden), arr, ctypes.byref(p))
+    if rc == FF_ERR_UNSUPPORTED:
+        raise NotImplementedError(
+            f"no gfx950 two-network kernel for a state of {dim} dimensions, cond_dim={cond_dim}, units={hidden}: the "
+            "compiled pair kernels hold states of up to 32 dimensions (16 per half), up to 16 conditional inputs and "
+            "hidden widths up to 256 (SiLU)")
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_pair_plan")
+    return p
+
+
+def is_pair_plan(plan: PlanStruct) -> bool:
+    return int(plan.kernel_id) >= PAIR_KERNEL_BASE
+
+
+def row_width(plan: PlanStruct) -> int:
+    """ff_mlp_row_width: first-layer bias words per evaluation row (2 x width for a pair plan)."""
+    return int(lib().ff_mlp_row_width(ctypes.byref(plan)))
+
+
+def pack_pair_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[int], x_col0: int, c_col0: int) -> torch.Tensor:
+    """ff_mlp_pair_wpack on host copies of the two networks' nn.Linear parameters; returns the packed CPU tensor."""
+    L = lib()
+    n = L.ff_mlp_pair_wpack_floats(ctypes.byref(plan))
+    out = torch.empty(n, dtype=torch.float32)
+    host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
+    keep, ptrs = [], []
+    for layers in (q_layers, p_layers):
+        ws = [host(l.weight) for l in layers]
+        bs = [host(l.bias) for l in layers]
+        keep += ws + bs
+        ptrs.append((ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws]))
+        ptrs.append((ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs]))
+    hw = (ctypes.c_int * len(hidden))(*hidden)
+    rc = L.ff_mlp_pair_wpack(ctypes.byref(plan), ptrs[0], ptrs[1], ptrs[2], ptrs[3], hw, int(q_layers[0].weight.shape[1]),
+                             x_col0, c_col0, out.data_ptr())
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_pair_wpack")
+    return out
 
 
 LAUNCH_ONE_WAVE, LAUNCH_TWIN, LAUNCH_ONE_WAVE_AND_TWIN = 0, 1, 2      # FF_LAUNCH_*
@@ -557,7 +616,7 @@ def mlp_ode(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[torch
         raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
     if probe is not None and tuple(probe.shape) != (B, D):
         raise RuntimeError(f"probe has shape {tuple(probe.shape)}, expected {(B, D)}")
-    if etab.shape[1] != 32 + p.width:
+    if etab.shape[1] != 32 + row_width(p):
         raise RuntimeError("evaluation table width does not match the plan")
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -616,7 +675,7 @@ def mlp_ode_step(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[
         a.aux_lp_out[j] = aux_lp[j].data_ptr() if mode != MODE_STATE else 0
     a.n_aux = n_aux
     a.stage_slots = _slots_hint(plan)
-    if etab.shape[1] != 32 + p.width or a.n_evals < 0:
+    if etab.shape[1] != 32 + row_width(p) or a.n_evals < 0:
         raise RuntimeError("evaluation table does not match the plan")
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream

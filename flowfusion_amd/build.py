@@ -91,6 +91,21 @@ def _wide_name(tile, h, d, c, t) -> str:
     return f"mlp_ode_m{tile}_h{h}_d{d}_c{c}_t{t}_wide"
 
 
+# Two-network kernels (ff_mlp_pair.hpp: the symplectic flows' right-hand side, two networks of one shape per evaluation):
+# (TILE, H, DREGS, CREGS, WPS, RING), state-only, SiLU, one wavefront per tile.  States of up to 32 dimensions (16 per
+# half), up to 16 conditional inputs; the widths of the single-network kernels with their tiles and occupancy.  A family
+# of its own: not in the ff_kernel_count / ff_kernel_name table.
+PAIR_INSTANCES = [
+    (16, 256, 8, 4, 2, 8),
+    (16, 128, 8, 4, 3, 4),
+    (32, 64, 16, 8, 1, 8),
+]
+
+
+def _pair_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_pair_m{tile}_h{h}_d{d}_c{c}" + (f"_w{wps}" if wps != 1 else "")
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -180,12 +195,13 @@ def _write(path: Path, text: str) -> Path:
     return path
 
 
-def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None) -> list[Path]:
+def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None) -> list[Path]:
     """The translation units of a library: the product's (default arguments) or a test variant's instance lists."""
     GEN = gen if gen is not None else globals()["GEN"]
     INSTANCES = instances if instances is not None else globals()["INSTANCES"]
     WIDE_INSTANCES = wide if wide is not None else globals()["WIDE_INSTANCES"]
     SPLIT_INSTANCES = split if split is not None else globals()["SPLIT_INSTANCES"]
+    PAIR_INSTANCES = pair if pair is not None else globals()["PAIR_INSTANCES"]
     GEN.mkdir(parents=True, exist_ok=True)
     files = []
     tf = lambda t: "true" if t else "false"
@@ -206,12 +222,20 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None)
         name = _split_name(nh, t, parts, dt, width)
         files.append(_write(GEN / f"{name}.hip", _launcher_unit(
             name, "ff_mlp_ode_split.hpp", f"split::mlp_ode_split_kernel<{nh}, {t}, {parts}, {dt}, {width}>")))
+    for tile, h, d, c, wps, ring in PAIR_INSTANCES:
+        name = _pair_name(tile, h, d, c, wps, ring)
+        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
+            name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}>")))
     decls = "\n".join(
         [f"int launch_{_inst_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES] +
         [f"int launch_{_inst_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES
          if _has_coop(i[1], i[7])] +
         [f"int launch_{_wide_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in WIDE_INSTANCES] +
-        [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES]
+        [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES] +
+        [f"int launch_{_pair_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES]
+    )
+    pair_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pair_name(*i)}, "{_pair_name(*i)}"}}' for i in PAIR_INSTANCES
     )
     split_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_split_name(*i)}, "{_split_name(*i)}"}}' for i in SPLIT_INSTANCES
@@ -229,6 +253,8 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None)
         )
     if not SPLIT_INSTANCES:          # (a test variant without the family: one inert row, count 0 -- no zero-length array)
         split_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
+    if not PAIR_INSTANCES:           # (the test variants carry no pair kernels)
+        pair_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 namespace ff {{
@@ -241,6 +267,10 @@ const SplitKernelEntry g_split_kernels[] = {{
 {split_rows}
 }};
 const int g_n_split_kernels = {len(SPLIT_INSTANCES)};
+const PairKernelEntry g_pair_kernels[] = {{
+{pair_rows}
+}};
+const int g_n_pair_kernels = {len(PAIR_INSTANCES)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -265,6 +295,8 @@ def _cost(src: Path) -> float:
         return 95 if "_t1" in n else 55
     if "_h512_" in n:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
+    if n.startswith("mlp_pair_"):
+        return 30 if "_h256_" in n else 12
     if "_h256_" in n:
         return 5 if "_coop" in n else 16
     return 6
@@ -347,7 +379,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
         for name, v in VARIANTS.items():
             gen, obj = PKG / "_build" / f"gen_{name}", PKG / "_build" / f"obj_{name}"
             obj.mkdir(parents=True, exist_ok=True)
-            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"])
+            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=[])
             extra[name] = (vs, obj, tuple(v["defines"]))
             units += [(s, obj, tuple(v["defines"])) for s in vs]
     jobs = jobs or min(8, os.cpu_count() or 1)

@@ -43,7 +43,7 @@ enum Rows : int { kRowsNone = 0, kRowsDerivAtH0 = 1, kRowsAttempt = 2 };
 FF_HD void schedule_ab(const ff_adapt_config& c, float t, float* a_out, float* b_out)
 {
 #pragma clang fp contract(off)
-    if (c.sched == FF_SCHED_FLOW) { *a_out = 0.f; *b_out = 1.f; return; }
+    if (c.sched == FF_SCHED_FLOW || c.sched == FF_SCHED_FOURIER) { *a_out = 0.f; *b_out = 1.f; return; }
     float a, g, sigma;
     if (c.sched == FF_SCHED_VE) {
         const float smin = (float)c.p[0], smax = (float)c.p[1], T = (float)c.p[2];
@@ -72,7 +72,8 @@ FF_HD void schedule_ab(const ff_adapt_config& c, float t, float* a_out, float* b
 }
 
 // ---- first-layer time part c1[h] at real time t ----------------------------------------------------------------------
-// time feature k < n_tcols: score networks [sin(arg_e) | cos(arg_e)], arg_e = ((t W_e) 2) pi (MLP.forward :109-110);
+// time feature k < n_tcols: score networks and symplectic flows [sin(arg_e) | cos(arg_e)], arg_e = ((t W_e) 2) pi
+// (MLP.forward :109-110; SymplecticMLP.forward symplectic.py:98-99);
 // flows: t itself (flow.py:112-115)
 FF_HD float time_feature(const ff_adapt_config& c, float t, int k)
 {

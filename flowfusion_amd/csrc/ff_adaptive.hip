@@ -360,7 +360,7 @@ struct Driver {
             grid = ff::norm_args_from_terms(k.norm, terms, n_terms, cfg->atol, cfg->rtol, check, n_check, nullptr, b->norm_workspace);
             if (grid == 0) return FF_ERR_BADARG;
         }
-        k.cfg = *cfg; k.state = b->state; k.etab = b->etab; k.etab_stride = FF_ROW_HDR + plan->width;
+        k.cfg = *cfg; k.state = b->state; k.etab = b->etab; k.etab_stride = FF_ROW_HDR + ff_mlp_row_width(plan);
         k.phase = phase; k.t0 = t0; k.t_end = t_end;
         if (b->exchange && (n_terms > 0 || n_check > 0)) {
             // this rank's sums of squares -> summed over the ranks (enqueued by the caller's hook) -> the controller
@@ -417,7 +417,7 @@ struct Driver {
             if (rc != FF_OK) return rc;
             ff::LpCombineArgs c;
             memset(&c, 0, sizeof(c));
-            c.gate = gate; c.etab = b->etab; c.etab_stride = FF_ROW_HDR + plan->width; c.n_evals = n_evals; c.n_aux = n_aux;
+            c.gate = gate; c.etab = b->etab; c.etab_stride = FF_ROW_HDR + ff_mlp_row_width(plan); c.n_evals = n_evals; c.n_aux = n_aux;
             c.div = b->est_div; c.kl1 = with_k1 ? b->fl0 : nullptr; c.lp0 = b->lp; c.n = B;
             for (int j = 0; j < n_aux; ++j) c.out[j] = out_lp[j];
             hipLaunchKernelGGL(ff::adapt_lp_combine_kernel, dim3(ff::copy_grid(4 * B)), dim3(256), 0, stream, c);
@@ -443,8 +443,8 @@ extern "C" int ff_mlp_ode_adaptive(const ff_mlp_plan_t* plan, const ff_ode_args*
 {
     if (!plan || !base || !cfg || !b || n_attempts < 0) return FF_ERR_BADARG;
     if (cfg->n_stages < 2 || cfg->n_stages > FF_MAX_SLOTS || cfg->order < 1) return FF_ERR_BADARG;
-    if (cfg->sched < FF_SCHED_FLOW || cfg->sched > FF_SCHED_SUBVP || !cfg->w0t || !cfg->b0) return FF_ERR_BADARG;
-    if (cfg->h_real < 1 || cfg->h_real > plan->width || cfg->n_tcols < 1 || cfg->n_tcols > ff::kMaxTimeCols) return FF_ERR_UNSUPPORTED;
+    if (cfg->sched < FF_SCHED_FLOW || cfg->sched > FF_SCHED_FOURIER || !cfg->w0t || !cfg->b0) return FF_ERR_BADARG;
+    if (cfg->h_real < 1 || cfg->h_real > ff_mlp_row_width(plan) || cfg->n_tcols < 1 || cfg->n_tcols > ff::kMaxTimeCols) return FF_ERR_UNSUPPORTED;
     if (cfg->sched != FF_SCHED_FLOW && (!cfg->emb_w || cfg->n_tcols != 2 * cfg->n_emb)) return FF_ERR_BADARG;
     if (cfg->sched == FF_SCHED_FLOW && cfg->n_tcols != 1) return FF_ERR_BADARG;
     const bool has_lp = base->mode != FF_MODE_STATE;

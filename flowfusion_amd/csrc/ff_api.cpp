@@ -168,11 +168,78 @@ static ff::Layout plan_layout(const ff_mlp_plan_t* p)
     return ff::make_layout(p->tile, p->width, p->dregs, p->cregs, p->n_hidden);
 }
 
+// a pair plan (ff_mlp_pair_plan): kernel ids FF_PAIR_KERNEL_BASE + i, a range no other plan uses
+static bool plan_ok_pair(const ff_mlp_plan_t* p)
+{
+    if (!p || p->precision != FF_PREC_F32 || p->kernel_id < FF_PAIR_KERNEL_BASE ||
+        p->kernel_id >= FF_PAIR_KERNEL_BASE + ff::g_n_pair_kernels)
+        return false;
+    const ff::PairKernelEntry& k = ff::g_pair_kernels[p->kernel_id - FF_PAIR_KERNEL_BASE];
+    const int per_reg = 64 / k.tile;
+    return k.H == p->width && k.dregs == p->dregs && k.cregs == p->cregs && k.tile == p->tile && p->n_hidden >= 1 &&
+           p->activation == FF_ACT_SILU && p->dim >= 2 && p->dim % 2 == 0 && p->dim <= per_reg * p->dregs &&
+           p->cond_dim >= 0 && p->cond_dim <= per_reg * p->cregs;
+}
+
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
 {
     if (plan_ok_split(plan)) return ff::g_split_kernels[plan->kernel_id].name;
     if (plan_ok(plan)) return ff::g_kernels[plan->kernel_id].name;
+    if (plan_ok_pair(plan)) return ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE].name;
     return NULL;
+}
+
+extern "C" int ff_pair_kernel_count(void) { return ff::g_n_pair_kernels; }
+
+extern "C" const char* ff_pair_kernel_name(int index)
+{
+    return index >= 0 && index < ff::g_n_pair_kernels ? ff::g_pair_kernels[index].name : NULL;
+}
+
+extern "C" int ff_mlp_row_width(const ff_mlp_plan_t* plan)
+{
+    if (!plan) return -1;
+    return plan_ok_pair(plan) ? 2 * plan->width : plan->width;
+}
+
+extern "C" int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
+{
+    if (!plan || !hidden_widths || dim < 2 || dim % 2 != 0 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
+    int wmax = 0;
+    for (int i = 0; i < n_hidden; ++i) {
+        if (hidden_widths[i] < 1) return FF_ERR_BADARG;
+        if (hidden_widths[i] > wmax) wmax = hidden_widths[i];
+    }
+    // the preference of ff_mlp_plan_prec: narrowest width, then the 16-column tile, then fewer first-layer k-steps
+    int best = -1;
+    for (int i = 0; i < ff::g_n_pair_kernels; ++i) {
+        const ff::PairKernelEntry& k = ff::g_pair_kernels[i];
+        const int need_d = ff::regs_for(k.tile, dim);
+        const int need_c = cond_dim > 0 ? ff::regs_for(k.tile, cond_dim) : 0;
+        if (k.H < wmax || k.dregs < need_d || k.cregs < need_c) continue;
+        if (best < 0) { best = i; continue; }
+        const ff::PairKernelEntry& b = ff::g_pair_kernels[best];
+        const int kc = (k.dregs + k.cregs) * (64 / k.tile), bc = (b.dregs + b.cregs) * (64 / b.tile);
+        if (k.H < b.H || (k.H == b.H && (k.tile < b.tile || (k.tile == b.tile && kc < bc)))) best = i;
+    }
+    if (best < 0) return FF_ERR_UNSUPPORTED;
+    memset(plan, 0, sizeof(*plan));
+    plan->dim = dim;
+    plan->cond_dim = cond_dim;
+    plan->n_hidden = n_hidden;
+    plan->width = ff::g_pair_kernels[best].H;
+    plan->dregs = ff::g_pair_kernels[best].dregs;
+    plan->cregs = ff::g_pair_kernels[best].cregs;
+    plan->kernel_id = FF_PAIR_KERNEL_BASE + best;
+    plan->tile = ff::g_pair_kernels[best].tile;
+    plan->activation = FF_ACT_SILU;
+    return FF_OK;
+}
+
+extern "C" size_t ff_mlp_pair_wpack_floats(const ff_mlp_plan_t* plan)
+{
+    if (!plan_ok_pair(plan)) return 0;
+    return 2 * plan_layout(plan).total_floats;
 }
 
 extern "C" size_t ff_mlp_wpack_floats(const ff_mlp_plan_t* plan)
@@ -277,6 +344,9 @@ static int wpack_split(const ff_mlp_plan_t* plan, const float* const* W, const f
     return group == (size_t)sp::granules_per_eval(NH, DT, H) * sp::granule_groups(H) ? FF_OK : FF_ERR_BADARG;
 }
 
+static int wpack_f32(const ff::Layout& L, int D, int C, const float* const* W, const float* const* b,
+                     const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out);
+
 extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, const float* const* b,
                             const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out)
 {
@@ -299,8 +369,16 @@ extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, co
         if (hidden_widths[i] < 1 || hidden_widths[i] > H) return FF_ERR_BADARG;
     for (int i = 0; i <= NH; ++i)
         if (!W[i] || (i > 0 && !b[i])) return FF_ERR_BADARG;
-    const ff::Layout L = plan_layout(plan);
-    const int TL = plan->tile, PHYS = ff::tile_phys(TL), CF = L.chunk_fl;
+    return wpack_f32(plan_layout(plan), D, C, W, b, hidden_widths, in_features0, x_col0, c_col0, out);
+}
+
+// The fp32 packing of one network of layout L (arguments checked by the callers): D state / network outputs, C conditional
+// inputs (ff_layout.h: the chunks of every layer in consumption order, then the biases).
+static int wpack_f32(const ff::Layout& L, int D, int C, const float* const* W, const float* const* b,
+                     const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out)
+{
+    const int NH = L.n_hidden;
+    const int TL = L.tile, PHYS = ff::tile_phys(TL), CF = L.chunk_fl;
     memset(out, 0, L.total_floats * sizeof(float));
 
     // Fill the chunks of one layer in consumption order (ff_layout.h).  `kcol(r, h)` maps operand
@@ -320,11 +398,11 @@ extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, co
     };
     // first layer: operand registers = [state | conditional]
     fill(L.g1, out, W[0], hidden_widths[0], in_features0, [&](int r, int h) {
-        if (r < plan->dregs) {
+        if (r < L.dregs) {
             const int d = ff::feat_of_reg(TL, r, h);
             return d < D ? x_col0 + d : -1;
         }
-        const int d = ff::feat_of_reg(TL, r - plan->dregs, h);
+        const int d = ff::feat_of_reg(TL, r - L.dregs, h);
         return d < C ? c_col0 + d : -1;
     });
     // hidden -> hidden
@@ -350,8 +428,58 @@ extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, co
     return FF_OK;
 }
 
+// Pair packing: each reference network becomes an ordinary network over the whole state [q | p] (its first layer reads
+// its own half -- p for mlp_q, q for mlp_p -- and has zero columns on the other; its output layer writes its own half,
+// negated for mlp_p, and zero rows on the other), packed by wpack_f32; net A's pack, then net B's.
+extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq,
+                                 const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
+                                 int x_col0, int c_col0, float* out)
+{
+    if (!plan_ok_pair(plan) || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
+    const int D2 = plan->dim, Dh = D2 / 2, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
+    if (x_col0 < 0 || x_col0 + Dh > in_features0) return FF_ERR_BADARG;
+    if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
+    for (int i = 0; i < NH; ++i)
+        if (hidden_widths[i] < 1 || hidden_widths[i] > H) return FF_ERR_BADARG;
+    for (int i = 0; i <= NH; ++i)
+        if (!Wq[i] || !Wp[i] || (i > 0 && (!bq[i] || !bp[i]))) return FF_ERR_BADARG;
+    const ff::Layout L = plan_layout(plan);
+    const int h0 = hidden_widths[0], hl = hidden_widths[NH - 1], in1 = D2 + C;
+    float* const w1 = (float*)calloc((size_t)h0 * in1, sizeof(float));
+    float* const wo = (float*)calloc((size_t)D2 * hl, sizeof(float));
+    float* const bo = (float*)calloc((size_t)D2, sizeof(float));
+    const float** const Wl = (const float**)calloc((size_t)NH + 1, sizeof(float*));
+    const float** const bl = (const float**)calloc((size_t)NH + 1, sizeof(float*));
+    int rc = (w1 && wo && bo && Wl && bl) ? FF_OK : FF_ERR_BADARG;
+    for (int half = 0; half < 2 && rc == FF_OK; ++half) {
+        const float* const* W = half ? Wp : Wq;
+        const float* const* b = half ? bp : bq;
+        const int in_col = half ? 0 : Dh;        // state columns this network reads: p (mlp_q) or q (mlp_p)
+        const int out_row = half ? Dh : 0;       // state rows it writes
+        const float sgn = half ? -1.f : 1.f;
+        memset(w1, 0, (size_t)h0 * in1 * sizeof(float));
+        memset(wo, 0, (size_t)D2 * hl * sizeof(float));
+        memset(bo, 0, (size_t)D2 * sizeof(float));
+        for (int r = 0; r < h0; ++r) {
+            for (int d = 0; d < Dh; ++d) w1[(size_t)r * in1 + in_col + d] = W[0][(size_t)r * in_features0 + x_col0 + d];
+            for (int c = 0; c < C; ++c) w1[(size_t)r * in1 + D2 + c] = W[0][(size_t)r * in_features0 + c_col0 + c];
+        }
+        for (int r = 0; r < Dh; ++r) {
+            for (int k = 0; k < hl; ++k) wo[(size_t)(out_row + r) * hl + k] = sgn * W[NH][(size_t)r * hl + k];
+            bo[out_row + r] = sgn * b[NH][r];
+        }
+        Wl[0] = w1; bl[0] = nullptr;
+        for (int l = 1; l < NH; ++l) { Wl[l] = W[l]; bl[l] = b[l]; }
+        Wl[NH] = wo; bl[NH] = bo;
+        rc = wpack_f32(L, D2, C, Wl, bl, hidden_widths, in1, 0, D2, out + (size_t)half * L.total_floats);
+    }
+    free(w1); free(wo); free(bo); free(Wl); free(bl);
+    return rc;
+}
+
 extern "C" int ff_mlp_samples_per_workgroup(const ff_mlp_plan_t* plan, int mode)
 {
+    if (plan_ok_pair(plan)) return mode == FF_MODE_STATE ? 4 * plan->tile : FF_ERR_BADARG;
     if (plan_ok_split(plan)) {
         const int kt = ff::g_split_kernels[plan->kernel_id].tangents;
         if (mode == FF_MODE_STATE && kt == 0) return 128;
@@ -470,6 +598,7 @@ static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, boo
 extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int32_t mode, int32_t tangent_count, int32_t jac_out)
 {
     if (plan_ok_split(plan)) return FF_LAUNCH_ONE_WAVE;
+    if (plan_ok_pair(plan)) return batch >= 0 && mode == FF_MODE_STATE && !jac_out ? FF_LAUNCH_ONE_WAVE : FF_ERR_BADARG;
     if (!plan_ok(plan) || batch < 0) return FF_ERR_BADARG;
     int nt, unit;
     const int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
@@ -481,9 +610,46 @@ extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int3
     return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
 }
 
+// pair plans (ff_mlp_pair.hpp): state-only integration of a table whose rows carry c1 of both networks
+static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
+{
+    if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
+    if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
+    if (a->mode != FF_MODE_STATE || a->jac_out) return FF_ERR_BADARG;      // divergence-free by construction: no tangents
+    if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
+    if (a->n_aux < 0 || a->n_aux > FF_MAX_AUX) return FF_ERR_BADARG;
+    if (a->noise && a->noise_stride < a->batch * (int64_t)plan->dim) return FF_ERR_BADARG;
+    if (a->batch == 0) return FF_OK;
+    const ff::PairKernelEntry& k = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE];
+    ff::KernelArgs ka;
+    memset(&ka, 0, sizeof(ka));
+    ka.gate = a->gate;
+    ka.x_in = a->x_in; ka.x_out = a->x_out; ka.cond = a->cond;
+    ka.noise = a->noise; ka.wpack = a->wpack; ka.etab = a->etab;
+    ka.in_shift = a->in_shift; ka.in_scale = a->in_scale; ka.out_scale = a->out_scale; ka.out_shift = a->out_shift;
+    ka.status = a->status; ka.batch = a->batch; ka.noise_stride = a->noise_stride;
+    ka.n_evals = a->n_evals; ka.n_hidden = plan->n_hidden; ka.dim = plan->dim; ka.cond_dim = plan->cond_dim;
+    ka.k1_in = a->k1_in; ka.n_aux = a->n_aux;
+    for (int j = 0; j < FF_MAX_AUX; ++j) ka.aux_out[j] = a->aux_out[j];
+    ka.rng_seed = a->rng_seed; ka.rng_sample_offset = a->rng_sample_offset; ka.rng_noise_base = a->rng_noise_base;
+    ka.etab_stride = FF_ROW_HDR + 2 * plan->width;
+    const ff::Layout L = plan_layout(plan);
+    if (2 * L.total_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
+    if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
+    ka.wpack_floats = (int)(2 * L.total_floats);
+    const long long tiles = (a->batch + plan->tile - 1) / plan->tile;
+    const long long grid = (tiles + 3) / 4;
+    if (grid > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
+    const unsigned lds = 4u * ff::kSlots * (plan->dregs / 4) * 64 * 16;
+    const int herr = k.launch(&ka, (unsigned)grid, lds, (hipStream_t)hip_stream);
+    if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
+    return FF_OK;
+}
+
 extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
 {
     if (a && plan_ok_split(plan)) return launch_split(plan, a, hip_stream);
+    if (a && plan_ok_pair(plan)) return launch_pair(plan, a, hip_stream);
     if (!plan_ok(plan) || !a) return FF_ERR_BADARG;
     if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;

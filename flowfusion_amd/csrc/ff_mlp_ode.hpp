@@ -328,7 +328,8 @@ constexpr int kTailSlots = 2 * kActStages;   // slots granted after a layer's la
 // MFMAs (40-cycle latency, 32-cycle issue) from following each other directly.
 //
 //   sbyte          byte offset of this layer's chunk 0 in the stream (wave-uniform)
-//   WRAP           the stream ends with this layer: prefetch wraps to offset 0 (next evaluation)
+//   WRAP           the stream ends with this layer: prefetch wraps to byte offset `wrap_byte` (0: the next evaluation;
+//                  the pair kernel, ff_mlp_pair.hpp, wraps its first network's output layer to the second network)
 //   pre_block(ob)  called at the first phase-B chunk of block ob (bias prefetch)
 //   slot(M, acc)   called after the M-th MFMA of the layer has been issued, and kTailSlots more
 //                  times after the last one: the caller hangs the activation stages of finished
@@ -344,7 +345,7 @@ template <int TILE, int RING, int KR, int NOB, bool WRAP, bool ZERO_INIT, int LA
           class SlotFn, class LastFn>
 __device__ __forceinline__ void run_layer(f32x4 (&ring)[RING][Tile<TILE>::PHYS], const Stream& ws, int lane16,
                                           int sbyte, const float (&B)[KR], BlockAcc<TILE> (&acc)[NOB],
-                                          PreFn&& pre_block, SlotFn&& slot_fn, LastFn&& last)
+                                          PreFn&& pre_block, SlotFn&& slot_fn, LastFn&& last, int wrap_byte = 0)
 {
     typedef Tile<TILE> T;
     constexpr LayerGeom L = layer_geom(KR, NOB, T::RB / 4);
@@ -385,7 +386,7 @@ __device__ __forceinline__ void run_layer(f32x4 (&ring)[RING][Tile<TILE>::PHYS],
         static_for<T::PHYS>([&](auto pp) {
             constexpr int p = decltype(pp)::value;
             if constexpr (WRAP && nxt >= L.CPAD)
-                ring[slot][p] = sload(ws, lane16, (nxt - L.CPAD) * CB + p * 1024);
+                ring[slot][p] = sload(ws, lane16, wrap_byte + (nxt - L.CPAD) * CB + p * 1024);
             else
                 ring[slot][p] = sload(ws, lane16, sbyte + nxt * CB + p * 1024);
         });

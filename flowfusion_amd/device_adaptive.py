@@ -164,7 +164,7 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
     cond_d = f32(cond) if net.cond_dim > 0 else None
     probe_d = f32(probe)
     wpack = net.wpack(dev, mode)
-    width = plan.width
+    width = net.width(mode)         # first-layer bias words per evaluation row (plan.width; twice that on a pair plan)
     nBD, nB = B * D, B
     # one work allocation: state words (32), y, f0, aux[4], scratch_x, etab, then the divergence arrays; the results
     # are tensors of their own (the caller keeps them, the work buffers go back to the allocator)

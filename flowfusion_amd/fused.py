@@ -49,10 +49,11 @@ class FusedEnvelopeWarning(UserWarning):
     """A network no compiled kernel can hold is evaluated by torch on the GPU (stepping stays native)."""
 
 
-def within_envelope(owner, key, build: Callable[[], "FusedNet"]) -> bool:
-    """True if a compiled kernel holds the network ``build()`` describes (plans for the state-only and the
-    divergence-capable kernels exist).  The reference puts no limit on width, dimension, conditional inputs or
-    activation (flowfusion/diffusion.py:59-72, flow.py:61-74); outside the compiled shapes the front ends keep the
+def within_envelope(owner, key, build: Callable[[], "FusedNet"], modes=(MODE_STATE, MODE_EXACT)) -> bool:
+    """True if a compiled kernel holds the network ``build()`` describes (plans exist in every mode of ``modes``: the
+    state-only and the divergence-capable kernels, or the state only for the two-network kernels of the symplectic flows).
+    The reference puts no limit on width, dimension, conditional inputs or activation (flowfusion/diffusion.py:59-72,
+    flow.py:61-74); outside the compiled shapes the front ends keep the
     solve on the GPU by handing the network to ``generic.py`` -- the module evaluated by torch, every Runge-Kutta
     combination, error norm and noise update by the library's kernels -- and say so once per network
     (``FusedEnvelopeWarning``).  The answer is cached on ``owner`` under ``key`` (identity of the layers)."""
@@ -61,8 +62,8 @@ def within_envelope(owner, key, build: Callable[[], "FusedNet"]) -> bool:
         return cached[1]
     try:
         net = build()
-        net.plan(MODE_STATE)
-        net.plan(MODE_EXACT)
+        for mode in modes:
+            net.plan(mode)
         ok = True
     except NotImplementedError as e:
         warnings.warn(f"{e} -- outside the fused kernels' envelope: this network is evaluated by torch on the GPU, "
@@ -221,7 +222,7 @@ class FusedNet:
         in reversed time with the right-hand side negated).  ``launcher`` replaces the GPU launch in
         the CPU tests (kernel-semantics emulator)."""
         plan = self.plan(mode)
-        width = plan.width
+        width = self.width(mode)        # first-layer bias words per row (two networks' worth on a pair plan)
         f32 = lambda t: None if t is None else t.detach().to(device, torch.float32).contiguous()
         cond_d = f32(cond) if self.cond_dim > 0 else None
         probe_d = f32(probe)
@@ -290,6 +291,87 @@ class FusedNet:
                 f"precision={self.precision!r} with {self.dim} state dimensions keeps {self.stage_slots(mode)} Runge-Kutta stage "
                 f"slots on chip and {what} needs {used}: use euler / midpoint / heun3 / rk4 / rk4_classic (or bosh3 / fehlberg2 "
                 "/ adaptive_heun), or precision='f32'")
+
+
+class FusedPair(FusedNet):
+    """Kernel-side view of the two networks of a symplectic flow (flowfusion_amd/symplectic.py): ``mlp_q`` reading the p
+    half of the state [q | p] and ``mlp_p`` reading the q half, each ``Linear -> SiLU -> ... -> Linear`` with first-layer
+    input ``[state half | cond | time features]``, on one two-network kernel (csrc/ff_mlp_pair.hpp).  State-only: the
+    field is divergence-free by construction.  ``dim`` is the whole state (2D); evaluation rows carry the c1 of net A
+    (mlp_q), then net B's (mlp_p), ``width`` words each."""
+
+    def __init__(self, q_linears: Sequence[nn.Linear], p_linears: Sequence[nn.Linear], dim: int, cond_dim: int,
+                 x_col0: int, c_col0: int):
+        super().__init__(q_linears, dim // 2, cond_dim, x_col0, c_col0)
+        self.p_linears = list(p_linears)
+        if [int(l.out_features) for l in self.p_linears] != [int(l.out_features) for l in self.linears] or \
+                len(self.p_linears) != len(self.linears):
+            raise NotImplementedError("the two networks of a pair must have the same shape")
+        for l in self.p_linears:
+            if l.bias is None:
+                raise NotImplementedError("Linear layers without bias are not supported")
+        self.dim = int(dim)
+
+    def serves(self, linears, act, precision: str = "f32", p_linears=()) -> bool:
+        return (super().serves(linears, act, precision) and len(p_linears) == len(self.p_linears)
+                and all(a is b for a, b in zip(p_linears, self.p_linears)))
+
+    def plan(self, mode: int) -> _native.PlanStruct:
+        if mode != MODE_STATE:
+            raise NotImplementedError("the two-network kernels integrate the state only (the field is divergence-free)")
+        if 0 not in self._plans:
+            self._plans[0] = _native.make_pair_plan(self.dim, self.cond_dim, self.hidden)
+        return self._plans[0]
+
+    def _param_key(self, device, plan) -> Tuple:
+        vers = tuple((p.data_ptr(), p._version) for l in self.linears + self.p_linears for p in (l.weight, l.bias))
+        return (str(device), plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden), vers
+
+    def wpack(self, device, mode: int) -> torch.Tensor:
+        plan = self.plan(mode)
+        layout, vers = self._param_key(device, plan)
+        hit = self._wpack.get(layout)
+        if hit is None or hit[0] != vers:
+            packed = _native.pack_pair_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
+            hit = (vers, packed.to(device))
+            self._wpack[layout] = hit
+        return hit[1]
+
+    def cached_table(self, key, device, build):
+        q0, p0 = self.linears[0], self.p_linears[0]
+        key = (key, p0.weight.data_ptr(), p0.weight._version, p0.bias._version)
+        return super().cached_table(key, device, build)
+
+    def first_layers_cpu(self):
+        """Host copies of both first layers: ((W_q, b_q), (W_p, b_p))."""
+        return tuple((l.weight.detach().to("cpu", torch.float32), l.bias.detach().to("cpu", torch.float32))
+                     for l in (self.linears[0], self.p_linears[0]))
+
+    def time_columns(self, device, c0: int, c1: int):
+        """Both first layers' columns [c0, c1) and biases, stacked as the device controller takes them for a pair plan:
+        ``[net A rows | zero pad | net B rows | zero pad]``, ``width`` rows each."""
+        layers = (self.linears[0], self.p_linears[0])
+        key = (str(device), c0, c1) + tuple((l.weight.data_ptr(), l.weight._version, l.bias.data_ptr(), l.bias._version)
+                                            for l in layers)
+        hit = self.__dict__.get("_time_cols")
+        if hit is None or hit[0] != key:
+            H = int(self.plan(MODE_STATE).width)
+            w = torch.zeros(2 * H, c1 - c0, dtype=torch.float32)
+            b = torch.zeros(2 * H, dtype=torch.float32)
+            for i, l in enumerate(layers):
+                h = int(l.out_features)
+                w[i * H:i * H + h] = l.weight.detach()[:, c0:c1].to("cpu", torch.float32)
+                b[i * H:i * H + h] = l.bias.detach().to("cpu", torch.float32)
+            hit = (key, w.to(device).contiguous(), b.to(device).contiguous())
+            self._time_cols = hit
+        return hit[1], hit[2]
+
+    def width(self, mode: int = MODE_STATE) -> int:
+        """First-layer bias words per evaluation row: two networks' worth."""
+        return 2 * int(self.plan(mode).width)
+
+    def stage_slots(self, mode: int = MODE_STATE) -> int:
+        return 7
 
 
 def require_fp32(module, *tensors, what="this solve"):

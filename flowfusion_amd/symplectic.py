@@ -1,0 +1,224 @@
+"""Symplectic flows on MI355X: the reference's ``flowfusion.symplectic`` API (``SymplecticMLP`` symplectic.py:11-122,
+``SymplecticFlowModel`` :124-253) with ``sample`` and ``log_prob`` running on the library's two-network kernel.
+
+The dynamics of a state ``[q | p]`` (2D dimensions) are ``v = [mlp_q(p, cond, t), -mlp_p(q, cond, t)]`` (:80-122): two
+networks of one shape on complementary halves, so the field is divergence-free by construction and ``log_prob`` is a
+state-only solve.  Each right-hand side is ONE evaluation of ``mlp_pair_kernel`` (csrc/ff_mlp_pair.hpp): net A = mlp_q,
+net B = mlp_p with its output negated, both per evaluation inside one launch; the symplectic structure lives in the host
+packer (``ff_mlp_pair_wpack``).  ``state_dict`` keys match the reference: ``shift``, ``scale``, ``conditional_shift``,
+``conditional_scale`` (buffers, any of them may be None), ``model.W``, ``model.mlp_{q,p}_dynamics.{0,2,..}.*``.
+
+Routes (odeint.py): ``sample`` is torchdiffeq-style fixed-grid Euler on the reference's ``linspace(1, 0, num_steps + 1)``
+grid (one fused launch); ``log_prob`` is adaptive dopri5 on the device controller.  Networks outside the compiled pair
+shapes, non-SiLU activations and any other ``model`` with the same ``forward(t, state, conditional)`` are evaluated by
+torch with the stepping in the library (generic.py; ``FusedEnvelopeWarning`` for the first two).  GPU only: CPU tensors
+raise.  The reference draws a tqdm progress bar in ``sample``; this module does not.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import _native, device_adaptive, odeint, solvers
+from .fused import FusedPair, MODE_STATE, activation_spec, within_envelope
+
+
+class SymplecticMLP(nn.Module):
+    """Two networks for the position and momentum dynamics (reference: symplectic.py:11-122).
+
+    ``mlp_q_dynamics`` / ``mlp_p_dynamics``: ``Linear(D + C + E -> units[0])``, activation, ..., ``Linear(-> D)``, the
+    same ``activation`` instance in every hidden layer of both; buffer ``W = randn(E // 2) * 16``.  Parameters are drawn
+    in the reference's order (mlp_q, mlp_p, then W), so a seeded construction gives the reference's weights."""
+
+    def __init__(self, n_data_dims, n_conditionals, embedding_dimensions, units, activation=nn.SiLU()):
+        super().__init__()
+        input_dim = n_data_dims + n_conditionals + embedding_dimensions
+        self.mlp_q_dynamics = self._create_mlp(input_dim, n_data_dims, units, activation)
+        self.mlp_p_dynamics = self._create_mlp(input_dim, n_data_dims, units, activation)
+        self.register_buffer("W", torch.randn(embedding_dimensions // 2) * 16.0)
+
+    def _create_mlp(self, input_dim, output_dim, units, activation):
+        layers = []
+        current = input_dim
+        for unit_count in units:
+            layers.append(nn.Linear(current, unit_count))
+            layers.append(activation)
+            current = unit_count
+        layers.append(nn.Linear(current, output_dim))
+        return nn.Sequential(*layers)
+
+    def forward(self, t, state, conditional):
+        """(dq/dt, dp/dt) = (mlp_q([p, cond, emb]), -mlp_p([q, cond, emb])), emb = [sin | cos]((t W) 2 pi); a 0-dim ``t``
+        is expanded to the batch (plain torch, symplectic.py:80-122)."""
+        q, p = torch.chunk(state, 2, dim=-1)
+        if t.dim() == 0:
+            t = t.expand(q.shape[0])
+        t_projected = t[:, None] * self.W[None, :] * 2 * math.pi
+        t_embedded = torch.cat([torch.sin(t_projected), torch.cos(t_projected)], dim=1)
+        if conditional is not None:
+            input_q = torch.cat([p, conditional, t_embedded], dim=1)
+            input_p = torch.cat([q, conditional, t_embedded], dim=1)
+        else:
+            input_q = torch.cat([p, t_embedded], dim=1)
+            input_p = torch.cat([q, t_embedded], dim=1)
+        v_q = self.mlp_q_dynamics(input_q)
+        v_p = -self.mlp_p_dynamics(input_p)
+        return torch.cat([v_q, v_p], dim=-1)
+
+
+class SymplecticFlowModel(nn.Module):
+    """Symplectic flow: a fast sampler and an exact log-density without a divergence term (reference:
+    symplectic.py:124-253).  ``shift`` / ``scale`` / ``conditional_shift`` / ``conditional_scale`` are buffers (None
+    allowed, as in the reference)."""
+
+    def __init__(self, model, shift, scale, conditional_shift, conditional_scale):
+        super().__init__()
+        self.model = model
+        self.register_buffer("shift", shift)
+        self.register_buffer("scale", scale)
+        self.register_buffer("conditional_shift", conditional_shift)
+        self.register_buffer("conditional_scale", conditional_scale)
+
+    # -- public API (the reference's signatures) ------------------------------------------------
+    @torch.no_grad()
+    def sample(self, shape, conditional=None, num_steps=1):
+        """``num_steps`` Euler steps from t = 1 to t = 0 of the joint state [q | p], started from ``randn(shape[0],
+        2 shape[1])`` on the model's device; returns ``q * scale + shift`` [B, D] (symplectic.py:166-202).  No progress
+        bar (the reference draws one with tqdm)."""
+        device = next(self.model.parameters()).device
+        x = torch.randn(shape[0], shape[1] * 2, device=device)
+        return self._sample_from(x, conditional, num_steps)
+
+    @torch.no_grad()
+    def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5):
+        """``log N(z1) - log N(p0) - sum log scale`` with z1 the dopri5 solution over t: 0 -> 1 of [q0 | p0],
+        q0 = (x - shift) / scale, p0 = randn_like(q0) (symplectic.py:204-253)."""
+        p0 = torch.randn_like(x)
+        return self._log_prob_from(x, p0, conditional, atol, rtol)
+
+    # -- with the random draws supplied (tests feed the reference's draws) ----------------------------
+    def _norm_cond(self, conditional):
+        if conditional is None:
+            return None
+        return (conditional - self.conditional_shift) / self.conditional_scale
+
+    @torch.no_grad()
+    def _sample_from(self, x, conditional=None, num_steps=1):
+        """``sample`` from the prior draw ``x`` [B, 2D]: the reference's grid ``linspace(1, 0, num_steps + 1)`` built on the
+        state's device, ``x + v(t_k, x) (t_{k+1} - t_k)`` per step -- torchdiffeq's fixed-grid Euler on that grid."""
+        conditional = self._norm_cond(conditional)
+        time_steps = torch.linspace(1.0, 0.0, num_steps + 1, device=x.device)
+        if num_steps > 0:
+            x, _ = odeint.solve(self, x, time_steps.cpu(), "euler", None, MODE_STATE, None, None, cond=conditional)
+        q, _ = torch.chunk(x, 2, dim=-1)
+        return q * self.scale + self.shift
+
+    @torch.no_grad()
+    def _log_prob_from(self, x, p0, conditional=None, atol=1e-5, rtol=1e-5, method="dopri5", options=None):
+        """``log_prob`` with the momentum draw ``p0`` supplied; ``method`` / ``options`` as torchdiffeq takes them (the
+        reference always runs its default, dopri5)."""
+        q0 = (x - self.shift) / self.scale
+        conditional = self._norm_cond(conditional)
+        z0 = torch.cat([q0, p0], dim=-1)
+        t_span = torch.tensor([0.0, 1.0])
+        z1, _ = odeint.solve(self, z0, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional)
+        normal = torch.distributions.Normal(0, 1)
+        log_p_z1 = normal.log_prob(z1).sum(dim=-1)
+        log_p_p0 = normal.log_prob(p0).sum(dim=-1)
+        return log_p_z1 - log_p_p0 - torch.sum(torch.log(self.scale))
+
+    # -- what odeint.solve asks of a front end -------------------------------------------------------
+    def _layers(self):
+        m = self.model
+        return list(m.mlp_q_dynamics), list(m.mlp_p_dynamics)
+
+    def _fusable(self) -> bool:
+        """The dynamics are a SymplecticMLP whose two networks a compiled pair kernel holds (shape, SiLU).  Another
+        module with the same ``forward(t, state, conditional)`` is stepped by generic.py; so is a SymplecticMLP outside
+        the compiled shapes or with another activation (with a ``FusedEnvelopeWarning``)."""
+        if not isinstance(self.model, SymplecticMLP):
+            return False
+        q, p = self._layers()
+        key = tuple(id(l) for l in q + p) + tuple(repr(l) for l in q + p if not isinstance(l, nn.Linear))
+        return within_envelope(self, key, self._net, modes=(MODE_STATE,))
+
+    def _net(self) -> FusedPair:
+        m = self.model
+        q, p = self._layers()
+        acts = {activation_spec(l) for l in q + p if not isinstance(l, nn.Linear)}
+        if acts != {(_native.ACT_SILU, 0.0, 0.0)}:
+            raise NotImplementedError(f"activations {sorted(acts)}: the two-network kernels are compiled for SiLU only")
+        ql = [l for l in q if isinstance(l, nn.Linear)]
+        pl = [l for l in p if isinstance(l, nn.Linear)]
+        cached = self.__dict__.get("_fused")
+        if cached is None or not cached.serves(ql, (_native.ACT_SILU, 0.0, 0.0), "f32", pl):
+            D = int(ql[-1].out_features)
+            E = 2 * int(m.W.numel())
+            C = int(ql[0].in_features) - D - E
+            # first-layer columns of each network: [its half of the state (D) | cond (C) | time features (E)]
+            cached = FusedPair(ql, pl, 2 * D, C, x_col0=0, c_col0=D)
+            object.__setattr__(self, "_fused", cached)
+        return cached
+
+    def _time_cols(self):
+        net = self._net()
+        D, C = net.dim // 2, net.cond_dim
+        return D + C, D + C + 2 * int(self.model.W.numel())
+
+    def _device_schedule(self, device):
+        """``device_adaptive.ScheduleSpec`` of the device controller: a = 0, b = 1, c1 = [sin | cos]((t W) 2 pi) through
+        both first layers' time columns (FF_SCHED_FOURIER), stacked [net A | net B]."""
+        m = self.model
+        if m.W.numel() == 0:
+            return None
+        c0, c1 = self._time_cols()
+        w0t, b0 = self._net().time_columns(device, c0, c1)
+        emb_w = m.W.detach().to(device, torch.float32).contiguous()
+        return device_adaptive.ScheduleSpec(_native.SCHED_FOURIER, (0.0, 0.0, 0.0), True, emb_w, math.pi, w0t, b0)
+
+    def _schedule_inputs(self):
+        """Host copies of what ``_schedule`` reads: W and both first layers (taken once per solve)."""
+        return (self.model.W.detach().to("cpu", torch.float32),) + self._net().first_layers_cpu()
+
+    def _schedule(self, t: torch.Tensor, host=None):
+        """(a, b, c1) for real times ``t`` (fp32, CPU): a = 0, b = 1, c1 = [c1 of mlp_q | c1 of mlp_p], each the first
+        layer's time columns times [sin | cos]((t W) 2 pi) plus its bias, zero-padded to the on-chip width."""
+        W, (wq, bq), (wp, bp) = host if host is not None else self._schedule_inputs()
+        c0, c1c = self._time_cols()
+        H = int(self._net().plan(MODE_STATE).width)
+        with solvers.host_threads():
+            arg = t[:, None] * W[None, :] * 2 * math.pi
+            emb = torch.cat([torch.sin(arg), torch.cos(arg)], dim=1)
+            c1 = torch.zeros(t.numel(), 2 * H, dtype=torch.float32)
+            for i, (w0, b0) in enumerate(((wq, bq), (wp, bp))):
+                # products rounded, summed in column order, then the bias (the device controller's order)
+                acc = torch.zeros(t.numel(), w0.shape[0], dtype=torch.float32)
+                for k in range(c1c - c0):
+                    acc = acc + emb[:, k:k + 1] * w0[None, :, c0 + k]
+                c1[:, i * H:i * H + w0.shape[0]] = acc + b0
+            return torch.zeros_like(t), torch.ones_like(t), c1
+
+    def _host_schedule(self):
+        host = self._schedule_inputs()
+        return lambda tr: self._schedule(tr, host)
+
+    def _ode_table(self, t_span, method, options, mode, y0=None):
+        plan = solvers.plan_ode(t_span, method, options, y0=y0)
+        a, b, c1 = self._schedule(plan.t_eval)
+        return solvers.build_table(plan, a, b, c1, self._net().width(mode))
+
+    def _schedule_key(self):
+        """Besides the first layers: the embedding frequencies."""
+        W = self.model.W
+        return (W.data_ptr(), W._version)
+
+    def _module_rhs(self, mode, cond, probe):
+        """``self.model`` evaluated by torch for the generic route: ``t`` expanded to the batch as the reference's
+        callers do (symplectic.py:192, 236-238); no divergence (the field is divergence-free)."""
+        def rhs(t, y):
+            with torch.no_grad():
+                return self.model(t.reshape(()).to(y.dtype).expand(y.shape[0]), y, cond), None
+        return rhs

@@ -272,6 +272,35 @@ int ff_mlp_samples_per_workgroup(const ff_mlp_plan_t* plan, int mode);
 /* hipError_t of the most recent failing launch on this thread (0 if none). */
 int ff_last_hip_error(void);
 
+/* ---- two-network plans: the symplectic flows (flowfusion_amd/symplectic.py) ----------------------------------------
+ * Right-hand side  a_e y + b_e (NET_A(y, cond; c1A_e) + NET_B(y, cond; c1B_e))  with two networks of one shape over a
+ * state of `dim` = 2D dimensions [q | p].  The reference's v = [mlp_q(p, cond, t), -mlp_p(q, cond, t)]
+ * (symplectic.py:80-122) is packed by ff_mlp_pair_wpack: NET_A = mlp_q reading the p half and writing rows 0..D-1,
+ * NET_B = mlp_p reading the q half and writing rows D..2D-1 with its output layer negated.  State-only (FF_MODE_STATE:
+ * the field is divergence-free by construction), SiLU.  A pair plan is an ff_mlp_plan_t whose kernel_id is
+ * FF_PAIR_KERNEL_BASE + an index into the pair family; ff_mlp_ode_launch, ff_mlp_ode_adaptive, ff_plan_kernel_name,
+ * ff_mlp_launch_kind and ff_mlp_samples_per_workgroup accept it.  Its evaluation rows carry FF_ROW_HDR header words,
+ * then c1 of net A (plan.width words), then c1 of net B (plan.width words): ff_mlp_row_width(plan) = 2 * plan.width. */
+#define FF_PAIR_KERNEL_BASE 0x10000
+/* Number of compiled pair instantiations and the name of each (index 0 .. count - 1). */
+int ff_pair_kernel_count(void);
+const char* ff_pair_kernel_name(int index);
+/* Choose the pair instantiation for a state of `dim` (even) dimensions, `cond_dim` conditional inputs and the
+ * reference's `units` (hidden_widths of each network); FF_ERR_UNSUPPORTED if none holds it. */
+int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan_out);
+/* Floats in the packed weights of a pair plan: two single-network packs back to back; 0 for any other plan. */
+size_t ff_mlp_pair_wpack_floats(const ff_mlp_plan_t* plan);
+/* Pack the two reference networks (HOST pointers, nn.Linear layout as in ff_mlp_wpack): Wq / bq = mlp_q_dynamics,
+ * Wp / bp = mlp_p_dynamics, first layers of `in_features0` columns of which [x_col0, x_col0 + dim/2) multiply that
+ * network's half of the state (p for mlp_q, q for mlp_p) and [c_col0, c_col0 + cond_dim) the conditional; the other
+ * columns (the time features) and the first biases go into c1.  `out` holds ff_mlp_pair_wpack_floats(plan) floats. */
+int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq,
+                      const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
+                      int x_col0, int c_col0, float* out);
+/* Words of first-layer bias per evaluation row (an etab row is FF_ROW_HDR + this many floats): plan.width, or
+ * 2 * plan.width for a pair plan.  -1 for NULL. */
+int ff_mlp_row_width(const ff_mlp_plan_t* plan);
+
 /* ---- streaming helpers beside the fused integrator (csrc/ff_aux.hip) --------------------------------- */
 
 /* Noise index reserved for the prior draw of a sample in the counter-based stream (never used by the
@@ -391,6 +420,8 @@ int ff_trace_estimate_host(const ff_trace_args* args);
 #define FF_SCHED_VE     1   /* VESDE (diffusion.py:818-1003):    p = {sigma_min, sigma_max, T}               */
 #define FF_SCHED_VP     2   /* VPSDE (diffusion.py:1006-1180):   p = {beta_min, beta_max, T}                 */
 #define FF_SCHED_SUBVP  3   /* SUBVPSDE (diffusion.py:1183-1366): p = {beta_min, beta_max, T}                */
+#define FF_SCHED_FOURIER 4  /* a = 0, b = 1, c1 = [sin | cos] Fourier features through w0t + b0 (symplectic.py:98-99);
+                               a pair plan takes w0t / b0 stacked as [net A rows | pad | net B rows | pad], h_real = 2 width */
 
 #define FF_ADAPT_OK            0
 #define FF_ADAPT_ERR_UNDERFLOW 1   /* torchdiffeq: AssertionError "underflow in dt {dt}" (state.dt holds it)   */
