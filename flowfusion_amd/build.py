@@ -94,7 +94,9 @@ def _wide_name(tile, h, d, c, t) -> str:
 # Two-network kernels (ff_mlp_pair.hpp: the symplectic flows' right-hand side, two networks of one shape per evaluation):
 # (TILE, H, DREGS, CREGS, WPS, RING), state-only, SiLU, one wavefront per tile.  States of up to 32 dimensions (16 per
 # half), up to 16 conditional inputs; the widths of the single-network kernels with their tiles and occupancy.  A family
-# of its own: not in the ff_kernel_count / ff_kernel_name table.
+# of its own: not in the ff_kernel_count / ff_kernel_name table.  The 256- and 128-wide ones get a cooperative twin for
+# small batches (a translation unit of its own, two wavefronts per SIMD, four chunks in flight, like the single-network
+# twins); a twin is not an entry of the table.
 PAIR_INSTANCES = [
     (16, 256, 8, 4, 2, 8),
     (16, 128, 8, 4, 3, 4),
@@ -129,10 +131,15 @@ SPLIT_INSTANCES = [(nh, 0, 3, 1, 256) for nh in (1, 2, 3, 4)] + \
 #               split-precision kernel
 #   skew_unfix  the same twin with round 3's two synchronisation fixes removed again (-DFF_DEBUG_UNFIX): what the test must
 #               see FAIL, or it guards nothing
+# Both also hold the 128-wide two-network kernel and its twin (tests/test_gpu_symplectic_skew.py; ff_mlp_pair.hpp): under
+# `skew` the twin as the product has it, under `skew_unfix` with net A's output parked in the shared stage slot.
 _SKEW_TWIN = [(16, 256, 4, 0, t, 2, 8, 0) for t in (0, 1)]
+_SKEW_PAIR = [(16, 128, 8, 4, 3, 4)]
 VARIANTS = {
-    "skew": dict(defines=["-DFF_DEBUG_SKEW=0"], instances=_SKEW_TWIN, wide=[(16, 256, 8, 4, 0)], split=[(3, 0, 2, 1, 128)]),
-    "skew_unfix": dict(defines=["-DFF_DEBUG_SKEW=0", "-DFF_DEBUG_UNFIX=1"], instances=_SKEW_TWIN, wide=[], split=[]),
+    "skew": dict(defines=["-DFF_DEBUG_SKEW=0"], instances=_SKEW_TWIN, wide=[(16, 256, 8, 4, 0)], split=[(3, 0, 2, 1, 128)],
+                 pair=_SKEW_PAIR),
+    "skew_unfix": dict(defines=["-DFF_DEBUG_SKEW=0", "-DFF_DEBUG_UNFIX=1"], instances=_SKEW_TWIN, wide=[], split=[],
+                       pair=_SKEW_PAIR),
 }
 
 
@@ -226,16 +233,22 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
         name = _pair_name(tile, h, d, c, wps, ring)
         files.append(_write(GEN / f"{name}.hip", _launcher_unit(
             name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}>")))
+        if _has_coop(h):
+            files.append(_write(GEN / f"{name}_coop.hip", _launcher_unit(
+                f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4, true>")))
     decls = "\n".join(
         [f"int launch_{_inst_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES] +
         [f"int launch_{_inst_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES
          if _has_coop(i[1], i[7])] +
         [f"int launch_{_wide_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in WIDE_INSTANCES] +
         [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES] +
-        [f"int launch_{_pair_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES]
+        [f"int launch_{_pair_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES] +
+        [f"int launch_{_pair_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES
+         if _has_coop(i[1])]
     )
     pair_rows = ",\n".join(
-        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pair_name(*i)}, "{_pair_name(*i)}"}}' for i in PAIR_INSTANCES
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pair_name(*i)}, "{_pair_name(*i)}", '
+        + (f"launch_{_pair_name(*i)}_coop" if _has_coop(i[1]) else "nullptr") + "}" for i in PAIR_INSTANCES
     )
     split_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_split_name(*i)}, "{_split_name(*i)}"}}' for i in SPLIT_INSTANCES
@@ -254,7 +267,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     if not SPLIT_INSTANCES:          # (a test variant without the family: one inert row, count 0 -- no zero-length array)
         split_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
     if not PAIR_INSTANCES:           # (the test variants carry no pair kernels)
-        pair_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
+        pair_rows = '    {0, 0, 0, 0, 0, nullptr, "", nullptr}'
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 namespace ff {{
@@ -296,7 +309,7 @@ def _cost(src: Path) -> float:
     if "_h512_" in n:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
     if n.startswith("mlp_pair_"):
-        return 30 if "_h256_" in n else 12
+        return (12 if "_h256_" in n else 5) if "_coop" in n else (30 if "_h256_" in n else 12)
     if "_h256_" in n:
         return 5 if "_coop" in n else 16
     return 6
@@ -379,7 +392,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
         for name, v in VARIANTS.items():
             gen, obj = PKG / "_build" / f"gen_{name}", PKG / "_build" / f"obj_{name}"
             obj.mkdir(parents=True, exist_ok=True)
-            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=[])
+            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"])
             extra[name] = (vs, obj, tuple(v["defines"]))
             units += [(s, obj, tuple(v["defines"])) for s in vs]
     jobs = jobs or min(8, os.cpu_count() or 1)

@@ -559,6 +559,10 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
 //   twin, n tiles:                  max(least, c0 + n / (0.95 chip)),  chip = 1024 wps tiles in flight,
 //                                   c0 = 0.10 (0.20 at one wavefront per SIMD), least = 0.22 / 0.30 / 0.35 for wps = 3 / 2 / 1
 // The twin serves whatever it is faster at.
+// Two-network kernels (`pair`; profiles/pair_twin.txt, the same units): at two wavefronts per SIMD (width 256) the constants
+// above pick the faster kernel at every measured tile count and stay.  At three (width 128) the twin's line is steeper and
+// starts lower -- c0 = 0.03, 0.85 of a chip's worth per round: with 0.10 / 0.95 the rule took the one-wavefront kernel at
+// 768 tiles (5 % slower there) and the twin at 2560 (7 % slower).
 // The tail of a launch.  The chip runs 1024 * wps tiles at once; the tiles left over after the full rounds run as a last
 // round with w = ceil(leftover / 1024) wavefronts per SIMD, which takes w / wps of a full round's time (measured: the
 // dispatcher fills SIMDs evenly, a wavefront does not finish sooner for having fewer neighbours than wps allows).
@@ -572,14 +576,15 @@ struct LaunchChoice {
     long long tail_tiles;      // tiles of a second launch on the twin (0 = none)
 };
 
-static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, bool jac_out)
+static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, bool jac_out, bool pair = false)
 {
     const long long chip = 1024ll * (k.wps > 0 ? k.wps : 1);
     auto twin_wins = [&](long long n) {
         const int wps = k.wps > 0 ? k.wps : 1;
         const double one_wave = (double)((n + 1023) / 1024) / (double)wps;
         const double least = wps >= 3 ? 0.22 : (wps == 2 ? 0.30 : 0.35);
-        const double line = (wps == 1 ? 0.20 : 0.10) + n / (0.95 * (double)chip);
+        const bool pair3 = pair && wps >= 3;
+        const double line = (wps == 1 ? 0.20 : (pair3 ? 0.03 : 0.10)) + n / ((pair3 ? 0.85 : 0.95) * (double)chip);
         return (line > least ? line : least) < one_wave;
     };
     bool coop = k.launch_coop != nullptr && tiles <= chip && twin_wins(tiles);
@@ -594,11 +599,26 @@ static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, boo
     return LaunchChoice{coop, tiles - tail_tiles, tail_tiles};
 }
 
+// A two-network kernel as choose_launch sees it: the same rule in the same units (an evaluation is two networks on the
+// one-wavefront kernel and on the twin alike), with constants of its own where the measurement asked for them.
+static ff::KernelEntry pair_as_entry(const ff::PairKernelEntry& p)
+{
+    ff::KernelEntry k = {};
+    k.tile = p.tile; k.H = p.H; k.dregs = p.dregs; k.cregs = p.cregs;
+    k.launch = p.launch; k.name = p.name; k.launch_coop = p.launch_coop; k.wps = p.wps;
+    return k;
+}
+
 // What ff_mlp_ode_launch would enqueue for `batch` samples in `mode`: FF_LAUNCH_* (see the header).
 extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int32_t mode, int32_t tangent_count, int32_t jac_out)
 {
     if (plan_ok_split(plan)) return FF_LAUNCH_ONE_WAVE;
-    if (plan_ok_pair(plan)) return batch >= 0 && mode == FF_MODE_STATE && !jac_out ? FF_LAUNCH_ONE_WAVE : FF_ERR_BADARG;
+    if (plan_ok_pair(plan)) {
+        if (batch < 0 || mode != FF_MODE_STATE || jac_out) return FF_ERR_BADARG;
+        const ff::PairKernelEntry& pk = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE];
+        const LaunchChoice ch = choose_launch(pair_as_entry(pk), (batch + plan->tile - 1) / plan->tile, false, true);
+        return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
+    }
     if (!plan_ok(plan) || batch < 0) return FF_ERR_BADARG;
     int nt, unit;
     const int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
@@ -637,11 +657,33 @@ static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hi
     if (2 * L.total_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)(2 * L.total_floats);
-    const long long tiles = (a->batch + plan->tile - 1) / plan->tile;
-    const long long grid = (tiles + 3) / 4;
+    // one-wavefront kernel, cooperative twin, or full rounds on the first and the leftover rows on the twin (choose_launch)
+    const long long spt = plan->tile;
+    const LaunchChoice ch = choose_launch(pair_as_entry(k), (a->batch + spt - 1) / spt, false, true);
+    const bool coop = ch.coop;
+    const long long main_tiles = ch.main_tiles, tail_tiles = ch.tail_tiles;
+    const unsigned slots = ff::kSlots * (plan->dregs / 4) * 64 * 16;
+    const unsigned kh = (plan->width / 32) * ff::tile_rb(plan->tile);                 // operand registers of a hidden layer
+    const unsigned lds_coop = slots + 2u * (kh / 4) * 64 * 16, lds_wave = 4u * slots;
+    if ((coop || tail_tiles ? lds_coop : 0u) > 160u * 1024u || (!coop ? lds_wave : 0u) > 160u * 1024u) return FF_ERR_UNSUPPORTED;
+    const long long grid = coop ? main_tiles : (main_tiles + 3) / 4;
     if (grid > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
-    const unsigned lds = 4u * ff::kSlots * (plan->dregs / 4) * 64 * 16;
-    const int herr = k.launch(&ka, (unsigned)grid, lds, (hipStream_t)hip_stream);
+    if (tail_tiles) ka.batch = main_tiles * spt;                                       // (full tiles only: < a->batch)
+    int herr = (coop ? k.launch_coop : k.launch)(&ka, (unsigned)grid, coop ? lds_coop : lds_wave, (hipStream_t)hip_stream);
+    if (herr == 0 && tail_tiles) {
+        // the same launch over rows [row0, batch), as in ff_mlp_ode_launch
+        const long long row0 = main_tiles * spt, D = plan->dim, C = plan->cond_dim;
+        ff::KernelArgs t = ka;
+        t.batch = a->batch - row0;
+        t.x_in += row0 * D; t.x_out += row0 * D;
+        if (t.cond) t.cond += row0 * C;
+        if (t.noise) t.noise += row0 * D;
+        if (t.k1_in) t.k1_in += row0 * D;
+        for (int j = 0; j < FF_MAX_AUX; ++j)
+            if (t.aux_out[j]) t.aux_out[j] += row0 * D;
+        t.rng_sample_offset += row0;
+        herr = k.launch_coop(&t, (unsigned)tail_tiles, lds_coop, (hipStream_t)hip_stream);
+    }
     if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
     return FF_OK;
 }

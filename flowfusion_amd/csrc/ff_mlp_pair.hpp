@@ -13,15 +13,28 @@
 // layers, then net B's, whose output is added to A's.  The weight ring runs across the A -> B boundary (A's output layer
 // prefetches B's first chunks) and B's output layer wraps to A's first layer of the next evaluation, so the pair costs
 // what one network of twice the depth costs; the stage bookkeeping runs once, after B.
+//
+// COOP (small batches; widths whose layers split four ways): one tile per WORKGROUP, as in mlp_ode_kernel<..., COOP>.  Each of
+// the four wavefronts computes NB / 4 logical blocks of every hidden layer of net A, then of net B, trading activations through
+// two alternating LDS buffers with one barrier per layer; both output layers are computed by every wavefront; wavefront 0
+// writes the outputs.  Same packed weights, same table, the same fp32 FMA chain per output row: bitwise the one-wavefront
+// kernel's results.  The stage slots are ONE copy shared by the four wavefronts, which brings three hazards:
+//   * the zero fill of the slots needs a barrier before k1_in is stored (a late wavefront would wipe it);
+//   * the exchange-buffer index alternates over the whole launch, not per evaluation or per network;
+//   * net A's output is NOT parked in the row's stage slot while net B runs (no barrier lies between a fast wavefront's store
+//     of the finished right-hand side into that slot and a slow wavefront's read of the parked value): it stays in registers.
+// tests/test_gpu_symplectic_skew.py holds a wavefront back at each of the three (ff_skew.h; -DFF_DEBUG_UNFIX parks net A in
+// the shared slot again, so that the test can see the third go wrong).
 #pragma once
 #include "ff_mlp_ode.hpp"
 
 namespace ff {
 
-template <int TILE, int H, int DREGS, int CREGS, int WPS, int RING>
+template <int TILE, int H, int DREGS, int CREGS, int WPS, int RING, bool COOP = false>
 __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs args)
 {
     static_assert(kChunkPad % RING == 0, "ring must divide the chunk padding");
+    static_assert(!COOP || (H / 32) % 4 == 0, "the cooperative twin splits the blocks of a layer four ways");
     typedef Tile<TILE> T;
     constexpr int NB = H / 32;                       // logical blocks per hidden layer
     constexpr int RB = T::RB;                        // registers per logical block
@@ -40,7 +53,9 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     const int col = lane & (TILE - 1);
     const int lane16 = lane * 16;
     const int q16 = qd * 16;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    // tile index: one per wavefront, or one per workgroup in the cooperative twin
+    const long long wave = COOP ? (long long)blockIdx.x : (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    [[maybe_unused]] const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wavefront of the workgroup
     const int D = args.dim;
     const int C = args.cond_dim;
     const ActSpec aspec = {0.f, 0.f, 0.f, 0};
@@ -70,13 +85,19 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
         }
     }
 
-    // Runge-Kutta stage slots in LDS, one set per wavefront (each lane touches only its own words)
+    // Runge-Kutta stage slots in LDS, one set per wavefront (each lane touches only its own words); the cooperative twin
+    // keeps one copy (its four wavefronts hold the same tile and store the same values), followed by two exchange buffers
     extern __shared__ __attribute__((aligned(16))) f32x4 lds_slots[];
-    f32x4* const ks = lds_slots + (size_t)(threadIdx.x >> 6) * kSlots * R4 * 64 + lane;
+    f32x4* const ks = lds_slots + (size_t)(COOP ? 0 : (threadIdx.x >> 6)) * kSlots * R4 * 64 + lane;
+    [[maybe_unused]] f32x4* const exch = lds_slots + (size_t)kSlots * R4 * 64 + lane;      // COOP: 2 x (KH / 4) x 64 words of 16 bytes
+    FF_SKEW_HOLD(COOP && wv == kSkewWave, 1);          // (test builds: this wavefront starts late ...)
 #pragma unroll
     for (int s = 0; s < kSlots; ++s)
 #pragma unroll
         for (int j = 0; j < R4; ++j) ks[(s * R4 + j) * 64] = f32x4{0.f, 0.f, 0.f, 0.f};
+    FF_SKEW_HOLD(COOP && wv == kSkewWave, 2);          // (... and lingers between its zero fill and its first store)
+    // all zero fills before anybody stores the caller's first stage (mlp_ode_kernel has the story)
+    if constexpr (COOP) __syncthreads();
     if (args.k1_in) {            // first stage supplied by the caller (FSAL of the previous step)
 #pragma unroll
         for (int j = 0; j < R4; ++j) {
@@ -89,6 +110,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
             ks[j * 64] = v;
         }
     }
+    FF_SKEW_HOLD(COOP && wv != kSkewWave, 2);          // (test builds: the others wait between that store and their first read)
 
     const Layout L = make_layout(TILE, H, DREGS, CREGS, args.n_hidden);
     constexpr int CB = 1024 * T::PHYS;               // bytes per chunk
@@ -98,20 +120,36 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     const int out_sbyte = L.chunk_off_out() * CB;
     const int out_bias_byte = (int)(L.bias_off_out() * 4);
 
-    // prefetch ring: the first RING chunks of net A's layer 1
+    // cooperative twin: wavefront wv owns logical blocks [wv * NBW, (wv + 1) * NBW) of every hidden layer and visits its
+    // chunks of a layer group-major, every visiting list padded to a multiple of RING (mlp_ode_kernel's scheme)
+    constexpr int NBW = COOP ? NB / 4 : NB;
+    [[maybe_unused]] const int ob0 = wv * NBW;
+    constexpr LayerGeom CG1 = layer_geom(K1, NB, RB / 4), CGH = layer_geom(KH, NB, RB / 4), CGO = layer_geom(KH, NOB_OUT, RB / 4);
+    constexpr int CN1 = (CG1.G * NBW + RING - 1) / RING * RING;          // padded visits of layer 1
+    auto coop_byte = [&](const LayerGeom& G, int sbyte, int i, int nm, int b0) __attribute__((always_inline)) {
+        const int g = i / nm, j = i % nm;
+        return sbyte + chunk_index(G, g < G.G ? g : 0, b0 + j) * CB;      // (padding visits re-read a real chunk)
+    };
+
+    // prefetch ring: the first RING chunks of net A's layer 1 (of this wavefront's visiting list in the cooperative twin)
     f32x4 ring[RING][T::PHYS];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
 #pragma unroll
-        for (int p = 0; p < T::PHYS; ++p) ring[i][p] = sload(ws, lane16, i * CB + p * 1024);
+        for (int p = 0; p < T::PHYS; ++p)
+            ring[i][p] = sload(ws, lane16, (COOP ? coop_byte(CG1, 0, i, NBW, ob0) : i * CB) + p * 1024);
 
     float P[KH];                 // operand registers of a hidden layer
     // hidden accumulators: they hold the bias of the layer about to run (row 0's c1 of net A to start with)
-    BlockAcc<TILE> hacc[NB];
+    BlockAcc<TILE> hacc[COOP ? 1 : NB];
+    if constexpr (!COOP) {
 #pragma unroll
-    for (int o = 0; o < NB; ++o) hacc[o] = load_bias_acc<TILE>(ts, q16, 128 + o * 128);
+        for (int o = 0; o < NB; ++o) hacc[o] = load_bias_acc<TILE>(ts, q16, 128 + o * 128);
+    }
 
     bool bad_slot = false;
+    // cooperative twin: the exchange buffer of the NEXT activation hand-over; it alternates over the whole launch
+    [[maybe_unused]] int xbuf = 0;
     for (int e = 0; e < args.n_evals; ++e) {
         const int row_byte = e * args.etab_stride * 4;
         HdrPtr hdr = (HdrPtr)(args.etab + (size_t)e * args.etab_stride);
@@ -134,11 +172,164 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
             for (int r = 0; r < CREGS; ++r) y[DREGS + r] = cnd[r];
         }
 
-        // NET_A + NET_B (the rows of the other half are exact zeros in each).  Net A's output is parked in this row's
-        // stage slot while net B runs (nothing reads that slot before the row stores its right-hand side there), so
-        // that it holds no registers across the second network.
+        // NET_A + NET_B (the rows of the other half are exact zeros in each).
         const bool slot_ok = (unsigned)slot < (unsigned)kSlots;
         float net[NOB_OUT * RB];
+        if constexpr (COOP) {
+            // ---- cooperative evaluation: NB / 4 blocks of every layer per wavefront, activations exchanged through LDS --
+            constexpr int RBQ = RB / 4;
+            // one layer of this wavefront's share: acc[j] += W[block b0 + j, :] . Bop over the layer's groups in ascending
+            // group order (the one-wavefront kernel's order: the same FMA chain per output row).
+            // next(k, slot): request visit k of the NEXT layer into ring slot `slot`.
+            auto coop_layer = [&](auto tag, const auto& Bop, auto& acc, int sbyte, int b0, auto&& next) __attribute__((always_inline)) {
+                constexpr int KIND = decltype(tag)::value;          // 0 = layer 1, 1 = hidden, 2 = output
+                constexpr LayerGeom G = KIND == 0 ? CG1 : (KIND == 1 ? CGH : CGO);
+                constexpr int NM = KIND == 2 ? NOB_OUT : NBW;
+                constexpr int NV = KIND == 0 ? CN1 : G.G * NM;
+                static_assert(NV % RING == 0, "visiting lists are multiples of the ring length");
+                constexpr int OUT_LAST = (DREGS * T::NQ - (NOB_OUT - 1) * 32 + TILE - 1) / TILE;
+                constexpr int LAST_PHYS = KIND == 2 ? (OUT_LAST < T::PHYS ? OUT_LAST : T::PHYS) : T::PHYS;
+                static_for<NV>([&](auto ii) {
+                    constexpr int i = decltype(ii)::value;
+                    constexpr int rs = i % RING, g = i / NM, j = i % NM;
+                    if constexpr (g < G.G) {
+                        static_for<4>([&](auto qq) {
+                            constexpr int q = decltype(qq)::value;
+                            static_for<T::PHYS>([&](auto pp) {
+                                constexpr int p = decltype(pp)::value;
+                                if constexpr (KIND == 2 && j == NM - 1 && p >= LAST_PHYS) {
+                                    if constexpr (g == 0 && q == 0) acc[j].v[p] = T::zero();
+                                } else if constexpr (KIND == 2 && g == 0 && q == 0)
+                                    acc[j].v[p] = T::mfma(ring[rs][p][q], Bop[4 * g + q], T::zero());
+                                else
+                                    acc[j].v[p] = T::mfma(ring[rs][p][q], Bop[4 * g + q], acc[j].v[p]);
+                            });
+                        });
+                    }
+                    constexpr int nxt = i + RING;
+                    if constexpr (nxt < NV) {
+                        static_for<T::PHYS>([&](auto pp) {
+                            constexpr int p = decltype(pp)::value;
+                            ring[rs][p] = sload(ws, lane16, coop_byte(G, sbyte, nxt, NM, b0) + p * 1024);
+                        });
+                    } else {
+                        next(std::integral_constant<int, nxt - NV>{}, std::integral_constant<int, rs>{});
+                    }
+                    __builtin_amdgcn_sched_barrier(0x2 | 0x4 | 0x400 | 0x80);
+                });
+            };
+            // activate this wavefront's blocks and trade them for everybody else's: P <- all KH operand registers
+            auto coop_exchange = [&](const BlockAcc<TILE> (&acc)[NBW], int buf) __attribute__((always_inline)) {
+                f32x4* const xb = exch + (size_t)buf * (KH / 4) * 64;
+                static_for<NBW>([&](auto jj) {
+                    constexpr int j = decltype(jj)::value;
+                    static_for<RBQ>([&](auto rr) {
+                        constexpr int r4 = decltype(rr)::value;
+                        ActGroup g4;
+                        float out[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) g4.pre[i] = acc[j].reg(4 * r4 + i);
+                        static_for<kActStages>([&](auto kk) {
+                            act_stage<false, 0, decltype(kk)::value>(g4, out, false, 0, aspec);
+                        });
+                        xb[((ob0 + j) * RBQ + r4) * 64] = f32x4{out[0], out[1], out[2], out[3]};
+                    });
+                });
+                __syncthreads();
+                FF_SKEW_HOLD(wv == kSkewWave, 2);       // (test builds: late to read what the others are about to overwrite)
+#pragma unroll
+                for (int k4 = 0; k4 < KH / 4; ++k4) {
+                    const f32x4 v = xb[k4 * 64];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) P[4 * k4 + i] = v[i];
+                }
+            };
+            // Net A's output while net B runs.  In registers: the stage slots are shared, and a fast wavefront stores the
+            // row's finished right-hand side into the slot before a slow one would have read a value parked there.
+            [[maybe_unused]] float net_a[DREGS];
+            static_for<NSUB>([&](auto ss) {
+                constexpr int sub = decltype(ss)::value;
+                const int sb = sub * sub_bytes;          // this network's pack in the weight stream
+                auto next_hidden_or_out = [&](int l_next, auto kk, auto sl) __attribute__((always_inline)) {
+                    // visit k of the layer after a hidden-side layer: hidden layer l_next, or the output layer
+                    constexpr int k = decltype(kk)::value, rs = decltype(sl)::value;
+                    const bool is_hid = l_next < args.n_hidden - 1;
+                    const int byte = is_hid ? coop_byte(CGH, sb + L.chunk_off_hid(l_next) * CB, k, NBW, ob0)
+                                            : coop_byte(CGO, sb + out_sbyte, k, NOB_OUT, 0);
+                    static_for<T::PHYS>([&](auto pp) {
+                        constexpr int p = decltype(pp)::value;
+                        ring[rs][p] = sload(ws, lane16, byte + p * 1024);
+                    });
+                };
+                BlockAcc<TILE> cacc[NBW];
+                // layer 1: bias c1 of this network from the evaluation row
+                const int c1_byte = row_byte + 128 + sub * H * 4;
+#pragma unroll
+                for (int j = 0; j < NBW; ++j) cacc[j] = load_bias_acc<TILE>(ts, q16, c1_byte + (ob0 + j) * 128);
+                coop_layer(std::integral_constant<int, 0>{}, y, cacc, sb, ob0,
+                           [&](auto kk, auto sl) { next_hidden_or_out(0, kk, sl); });
+                for (int l = 0; l < args.n_hidden - 1; ++l) {
+                    BlockAcc<TILE> nacc[NBW];                            // this layer's bias: requested before the exchange
+                    const int bbyte = sb + (int)(L.bias_off_hid(l) * 4);
+#pragma unroll
+                    for (int j = 0; j < NBW; ++j) nacc[j] = load_bias_acc<TILE>(ws, q16, bbyte + (ob0 + j) * 128);
+                    coop_exchange(cacc, xbuf);
+                    xbuf ^= 1;
+#pragma unroll
+                    for (int j = 0; j < NBW; ++j) cacc[j] = nacc[j];
+                    coop_layer(std::integral_constant<int, 1>{}, P, cacc, sb + L.chunk_off_hid(l) * CB, ob0,
+                               [&](auto kk, auto sl) { next_hidden_or_out(l + 1, kk, sl); });
+                }
+                BiasBlk<TILE> obias[NOB_OUT];
+#pragma unroll
+                for (int o = 0; o < NOB_OUT; ++o) obias[o] = load_bias<TILE>(ws, q16, sb + out_bias_byte + o * 128);
+                coop_exchange(cacc, xbuf);
+                xbuf ^= 1;
+                // output layer: every wavefront computes all of it; the ring moves on to net B's layer 1 (after net A) or
+                // to net A's layer 1 of the next evaluation
+                BlockAcc<TILE> oacc[NOB_OUT];
+                coop_layer(std::integral_constant<int, 2>{}, P, oacc, sb + out_sbyte, 0, [&](auto kk, auto sl) {
+                    constexpr int k = decltype(kk)::value, rs = decltype(sl)::value;
+                    static_for<T::PHYS>([&](auto pp) {
+                        constexpr int p = decltype(pp)::value;
+                        ring[rs][p] = sload(ws, lane16, coop_byte(CG1, sub == 0 ? sub_bytes : 0, k, NBW, ob0) + p * 1024);
+                    });
+                });
+#pragma unroll
+                for (int o = 0; o < NOB_OUT; ++o)
+#pragma unroll
+                    for (int r = 0; r < RB; ++r) net[o * RB + r] = oacc[o].reg(r) + obias[o].reg(r);
+                if constexpr (sub == 0) {
+#if defined(FF_DEBUG_UNFIX)
+                    // (test builds: the one-wavefront kernel's parking place, which four wavefronts share here)
+                    if (slot_ok) {
+#pragma unroll
+                        for (int j = 0; j < R4; ++j)
+                            ks[(slot * R4 + j) * 64] = f32x4{net[4 * j], net[4 * j + 1], net[4 * j + 2], net[4 * j + 3]};
+                    }
+#else
+#pragma unroll
+                    for (int r = 0; r < DREGS; ++r) net_a[r] = net[r];
+#endif
+                }
+            });
+            FF_SKEW_HOLD(wv == kSkewWave, 2);           // (test builds: late to pick net A's output up again)
+            if (slot_ok) {
+#if defined(FF_DEBUG_UNFIX)
+#pragma unroll
+                for (int j = 0; j < R4; ++j) {
+                    const f32x4 na = ks[(slot * R4 + j) * 64];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) net[4 * j + i] = na[i] + net[4 * j + i];
+                }
+#else
+#pragma unroll
+                for (int r = 0; r < DREGS; ++r) net[r] = net_a[r] + net[r];
+#endif
+            }
+        } else {
+        // One wavefront per tile.  Net A's output is parked in this row's stage slot while net B runs (nothing reads that
+        // slot before the row stores its right-hand side there), so that it holds no registers across the second network.
         // the activation pipeline of mlp_ode_kernel's one-wavefront path: `pend` = the previous layer's parked last
         // block, activated into P[(NB-1)*RB ..] behind the first MFMAs of the next layer
         float pend[RB];
@@ -264,6 +455,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                 for (int i = 0; i < 4; ++i) net[4 * j + i] = na[i] + net[4 * j + i];
             }
         }
+        }   // !COOP
 
         // ---- RHS and stage bookkeeping: once per evaluation, after both networks ---------------------------------
         float rhs[DREGS];
@@ -313,7 +505,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     }
 
     // ---- epilogue: auxiliary outputs (adaptive attempts), final state -----------------------------------------------
-    const bool writer = col_live;
+    const bool writer = col_live && (!COOP || wv == 0);
     if (args.n_aux > 0) {
         HdrPtr t0h = (HdrPtr)(args.etab + (size_t)args.n_evals * args.etab_stride);
         HdrPtr t1h = (HdrPtr)(args.etab + (size_t)(args.n_evals + 1) * args.etab_stride);

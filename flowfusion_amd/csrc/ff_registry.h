@@ -40,8 +40,8 @@ struct SplitKernelEntry {
 extern const SplitKernelEntry g_split_kernels[];
 extern const int g_n_split_kernels;
 
-// two-network family (ff_mlp_pair.hpp, ff_mlp_pair_plan): state-only, SiLU, one wavefront per tile; a pair plan's
-// kernel_id is FF_PAIR_KERNEL_BASE + the index into this table
+// two-network family (ff_mlp_pair.hpp, ff_mlp_pair_plan): state-only, SiLU; a pair plan's kernel_id is
+// FF_PAIR_KERNEL_BASE + the index into this table
 struct PairKernelEntry {
     int tile;       // MFMA columns per wavefront
     int H;          // hidden width on chip (each network)
@@ -50,6 +50,7 @@ struct PairKernelEntry {
     int wps;        // wavefronts per SIMD (launch bound)
     LaunchFn launch;
     const char* name;
+    LaunchFn launch_coop;   // cooperative twin for small batches (one tile per workgroup) or NULL
 };
 extern const PairKernelEntry g_pair_kernels[];
 extern const int g_n_pair_kernels;

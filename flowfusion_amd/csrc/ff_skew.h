@@ -8,6 +8,9 @@
 //     barrier of every activation exchange and its reads of the exchange buffer -- while the OTHER wavefronts wait between
 //     storing the caller's first stage and reading it back, so that the late zero fill falls into that window
 //     deterministically, not once in a thousand runs;
+//   * mlp_pair_kernel<..., COOP> (ff_mlp_pair.hpp; tests/test_gpu_symplectic_skew.py): the same places, and between the end of
+//     net B and the point where net A's output is picked up again -- with -DFF_DEBUG_UNFIX that output waits in the shared
+//     stage slot, where the other wavefronts have stored the finished right-hand side by then;
 //   * split::mlp_ode_split_kernel (ff_mlp_ode_split.hpp): before its first weight DMA and behind the barrier of every weight
 //     granule, i.e. late to read a buffer the others' next DMAs must not touch yet.
 // With correct synchronisation the results are bitwise those of the un-skewed kernels.  -DFF_DEBUG_UNFIX removes round 3's two

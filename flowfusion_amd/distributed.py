@@ -305,3 +305,70 @@ def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: O
     if not gather:
         return local, (lo, hi)
     return gather_rows(local, n, group) if world > 1 else local
+
+
+# ---- the symplectic flows (flowfusion/symplectic.py:166-253) ------------------------------------------------------------------
+def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: Optional[torch.Tensor] = None,
+                              num_steps: int = 1, group=None, gather: bool = True,
+                              local_conditional: Optional[torch.Tensor] = None):
+    """``SymplecticFlowModel.sample`` of ``n_total`` prior draws over all ranks.  This rank's rows of the prior [q | p]
+    are standard normals of the library's counter-based stream keyed by ``seed`` and the GLOBAL row (``ff_normal_fill``
+    with its default noise index, the one reserved for prior draws) -- NOT torch's generator, which the unsharded
+    ``sample`` keeps drawing from as the reference does -- so every world size transports the same points and a rank only
+    ever touches its own rows.  ``symplectic_log_prob_sharded`` draws its momenta from the same stream and index: pass
+    different seeds where the two draws must be unrelated.  The grid is fixed (``num_steps`` Euler steps), so there is no
+    collective but the final all-gather (``gather=False`` keeps the shard and returns its bounds); a rank without rows is
+    fine.  ``conditional`` is the raw [n_total, C] tensor (every rank slices its rows) or ``local_conditional`` this
+    rank's rows.  More than one rank over RCCL has not been run on hardware, like everything else multi-rank here."""
+    from . import _native
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    n = int(n_total)
+    lo, hi = shard_bounds(n, world, rank)
+    dev = next(model.model.parameters()).device
+    # the joint state is [q | p]: 2 D columns (a model built without `shift` is asked for its networks' state width)
+    dim = 2 * int(model.shift.numel()) if model.shift is not None else int(model._net().dim)
+    x = _native.normal_fill(hi - lo, dim, int(seed), lo, dev)
+    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
+    local = model._sample_from(x, cond, int(num_steps))
+    if not gather:
+        return local, (lo, hi)
+    return gather_rows(local, n, group) if world > 1 else local
+
+
+def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,
+                                seed: int = 0, group=None, gather: bool = True, local_x: Optional[torch.Tensor] = None,
+                                n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None,
+                                global_control: bool = True, atol: float = 1e-5, rtol: float = 1e-5):
+    """``SymplecticFlowModel.log_prob`` of a [B, D] batch over all ranks; one all-gather of the [B] result at the end.
+    ``x`` (and ``conditional``) are the full tensors, every rank slicing its rows -- or ``local_x`` (and
+    ``local_conditional``) this rank's rows already, with ``n_total`` the size of the whole batch.  The momentum draw
+    ``p0`` comes from the library's counter-based stream keyed by ``seed`` and the GLOBAL row (``ff_normal_fill`` with its
+    default noise index, the one reserved for prior draws; not torch's generator, which the unsharded ``log_prob`` keeps
+    using as the reference does).  ``symplectic_sample_sharded`` draws from the same stream and index: pass different
+    seeds where the two draws must be unrelated.  The solve is adaptive dopri5: with ``global_control`` the step size
+    comes from the error norm of the WHOLE batch (``global_step_control``; every rank needs at least one row), so every
+    rank takes the same steps and a row's result does not depend on the world size beyond the rounding of those norms;
+    ``global_control=False``: every rank steps from its own rows and enters no exchange.  More than one rank over RCCL has
+    not been run on hardware, like everything else multi-rank here."""
+    from . import _native
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if (x is None) == (local_x is None):
+        raise ValueError("pass either the full batch `x` or this rank's rows `local_x` (with n_total)")
+    if x is None and n_total is None:
+        raise ValueError("local_x needs n_total")
+    n = int(x.shape[0] if x is not None else n_total)
+    lo, hi = shard_bounds(n, world, rank)
+    rows = _local_rows(x, local_x, lo, hi, "x")
+    if x is not None and local_conditional is not None:
+        raise ValueError("local_conditional goes with local_x")
+    if x is None and conditional is not None:
+        raise ValueError("local_x goes with local_conditional, not the full `conditional`")
+    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
+    p0 = _native.normal_fill(hi - lo, int(rows.shape[1]), int(seed), lo, rows.device)
+    with _step_control(n, world, group, global_control, "dopri5"):
+        local = model._log_prob_from(rows, p0, cond, atol, rtol, method="dopri5")
+    if not gather:
+        return local, (lo, hi)
+    return gather_rows(local, n, group) if world > 1 else local

@@ -260,7 +260,9 @@ int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* args, void* 
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
  * query, so that callers, benchmarks and tests can name the kernel that ran without timing it.  Honours FF_COOP /
- * FF_TAIL_SPLIT in the environment like the launcher does.  Negative: FF_ERR_*. */
+ * FF_TAIL_SPLIT in the environment like the launcher does.  Negative: FF_ERR_*.  Two-network (pair) plans follow the
+ * same rule -- the 256- and 128-wide pair kernels have a twin, the 64-wide one answers FF_LAUNCH_ONE_WAVE always -- and
+ * take FF_MODE_STATE without a Jacobian output only (anything else: FF_ERR_BADARG). */
 #define FF_LAUNCH_ONE_WAVE          0   /* the one-wavefront-per-tile kernel                                         */
 #define FF_LAUNCH_TWIN              1   /* its cooperative small-batch twin (or a wide catch-all): a tile per workgroup */
 #define FF_LAUNCH_ONE_WAVE_AND_TWIN 2   /* full rounds on the first, the leftover rows on the twin (two launches)     */
@@ -277,7 +279,8 @@ int ff_last_hip_error(void);
  * state of `dim` = 2D dimensions [q | p].  The reference's v = [mlp_q(p, cond, t), -mlp_p(q, cond, t)]
  * (symplectic.py:80-122) is packed by ff_mlp_pair_wpack: NET_A = mlp_q reading the p half and writing rows 0..D-1,
  * NET_B = mlp_p reading the q half and writing rows D..2D-1 with its output layer negated.  State-only (FF_MODE_STATE:
- * the field is divergence-free by construction), SiLU.  A pair plan is an ff_mlp_plan_t whose kernel_id is
+ * the field is divergence-free by construction), SiLU; small batches and the leftover rows of a longer launch run on a
+ * cooperative twin as for the single-network kernels (bitwise the same results; FF_COOP / FF_TAIL_SPLIT).  A pair plan is an ff_mlp_plan_t whose kernel_id is
  * FF_PAIR_KERNEL_BASE + an index into the pair family; ff_mlp_ode_launch, ff_mlp_ode_adaptive, ff_plan_kernel_name,
  * ff_mlp_launch_kind and ff_mlp_samples_per_workgroup accept it.  Its evaluation rows carry FF_ROW_HDR header words,
  * then c1 of net A (plan.width words), then c1 of net B (plan.width words): ff_mlp_row_width(plan) = 2 * plan.width. */
