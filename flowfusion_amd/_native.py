@@ -90,6 +90,7 @@ class OdeArgs(ctypes.Structure):
 STATUS_NAN, STATUS_BAD_SLOT = 1, 2          # FF_STATUS_*
 SCHED_FLOW, SCHED_VE, SCHED_VP, SCHED_SUBVP, SCHED_FOURIER = 0, 1, 2, 3, 4     # FF_SCHED_*
 PAIR_KERNEL_BASE = 0x10000                                  # FF_PAIR_KERNEL_BASE
+PAIR_SELECT_KERNEL_BASE = 0x20000                           # FF_PAIR_SELECT_KERNEL_BASE
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -267,6 +268,8 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_pair_plan.restype = ctypes.c_int
     L.ff_mlp_pair_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                    ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pair_select_plan.restype = ctypes.c_int
+    L.ff_mlp_pair_select_plan.argtypes = L.ff_mlp_pair_plan.argtypes
     L.ff_mlp_pair_wpack_floats.restype = ctypes.c_size_t
     L.ff_mlp_pair_wpack_floats.argtypes = [ctypes.POINTER(PlanStruct)]
     L.ff_mlp_pair_wpack.restype = ctypes.c_int
@@ -336,11 +339,12 @@ def kernel_name(plan: PlanStruct) -> str:
     return n.decode() if n else "?"
 
 
-def make_pair_plan(dim: int, cond_dim: int, hidden: List[int]) -> PlanStruct:
-    """ff_mlp_pair_plan: the two-network kernel for a state of ``dim`` = 2D dimensions (raises if none holds it)."""
+def make_pair_plan(dim: int, cond_dim: int, hidden: List[int], select: bool = False) -> PlanStruct:
+    """ff_mlp_pair_plan: the two-network kernel for a state of ``dim`` = 2D dimensions (raises if none holds it);
+    ``select``: ff_mlp_pair_select_plan, its row-select variant (one network per evaluation row)."""
     p = PlanStruct()
     arr = (ctypes.c_int * len(hidden))(*hidden)
-    rc = lib().ff_mlp_pair_plan(dim, cond_dim, len(hidden), arr, ctypes.byref(p))
+    rc = (lib().ff_mlp_pair_select_plan if select else lib().ff_mlp_pair_plan)(dim, cond_dim, len(hidden), arr, ctypes.byref(p))
     if rc == FF_ERR_UNSUPPORTED:
         raise NotImplementedError(
             f"no gfx950 two-network kernel for a state of {dim} dimensions, cond_dim={cond_dim}, units={hidden}: the "
@@ -355,8 +359,12 @@ def is_pair_plan(plan: PlanStruct) -> bool:
     return int(plan.kernel_id) >= PAIR_KERNEL_BASE
 
 
+def is_select_plan(plan: PlanStruct) -> bool:
+    return int(plan.kernel_id) >= PAIR_SELECT_KERNEL_BASE
+
+
 def row_width(plan: PlanStruct) -> int:
-    """ff_mlp_row_width: first-layer bias words per evaluation row (2 x width for a pair plan)."""
+    """ff_mlp_row_width: first-layer bias words per evaluation row (2 x width for a pair plan, width for a select plan)."""
     return int(lib().ff_mlp_row_width(ctypes.byref(plan)))
 
 

@@ -108,6 +108,16 @@ def _pair_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_pair_m{tile}_h{h}_d{d}_c{c}" + (f"_w{wps}" if wps != 1 else "")
 
 
+# Row-select variants of the two-network kernels (ff_mlp_pair.hpp SELECT; ff_mlp_pair_select_plan): a row runs one of the
+# two networks -- the leapfrog of the symplectic flows.  One per pair instance, with the pair twins' twins; carried as
+# further launchers of the pair table's rows, not as rows of any table.
+PAIR_SELECT_INSTANCES = list(PAIR_INSTANCES)
+
+
+def _pairsel_name(tile, h, d, c, wps, ring) -> str:
+    return _pair_name(tile, h, d, c, wps, ring).replace("mlp_pair_", "mlp_pairsel_", 1)
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -133,11 +143,13 @@ SPLIT_INSTANCES = [(nh, 0, 3, 1, 256) for nh in (1, 2, 3, 4)] + \
 #               see FAIL, or it guards nothing
 # Both also hold the 128-wide two-network kernel and its twin (tests/test_gpu_symplectic_skew.py; ff_mlp_pair.hpp): under
 # `skew` the twin as the product has it, under `skew_unfix` with net A's output parked in the shared stage slot.
+# `skew` also holds the 128-wide row-select kernel and its twin (tests/test_gpu_symplectic_leapfrog_skew.py); `skew_unfix`
+# does not: the select twin parks nothing, so there is no hazard of its own to un-fix.
 _SKEW_TWIN = [(16, 256, 4, 0, t, 2, 8, 0) for t in (0, 1)]
 _SKEW_PAIR = [(16, 128, 8, 4, 3, 4)]
 VARIANTS = {
     "skew": dict(defines=["-DFF_DEBUG_SKEW=0"], instances=_SKEW_TWIN, wide=[(16, 256, 8, 4, 0)], split=[(3, 0, 2, 1, 128)],
-                 pair=_SKEW_PAIR),
+                 pair=_SKEW_PAIR, select=_SKEW_PAIR),
     "skew_unfix": dict(defines=["-DFF_DEBUG_SKEW=0", "-DFF_DEBUG_UNFIX=1"], instances=_SKEW_TWIN, wide=[], split=[],
                        pair=_SKEW_PAIR),
 }
@@ -202,13 +214,14 @@ def _write(path: Path, text: str) -> Path:
     return path
 
 
-def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None) -> list[Path]:
+def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None, select=None) -> list[Path]:
     """The translation units of a library: the product's (default arguments) or a test variant's instance lists."""
     GEN = gen if gen is not None else globals()["GEN"]
     INSTANCES = instances if instances is not None else globals()["INSTANCES"]
     WIDE_INSTANCES = wide if wide is not None else globals()["WIDE_INSTANCES"]
     SPLIT_INSTANCES = split if split is not None else globals()["SPLIT_INSTANCES"]
     PAIR_INSTANCES = pair if pair is not None else globals()["PAIR_INSTANCES"]
+    SELECT = select if select is not None else globals()["PAIR_SELECT_INSTANCES"]       # (a subset of PAIR_INSTANCES)
     GEN.mkdir(parents=True, exist_ok=True)
     files = []
     tf = lambda t: "true" if t else "false"
@@ -236,6 +249,13 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
         if _has_coop(h):
             files.append(_write(GEN / f"{name}_coop.hip", _launcher_unit(
                 f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4, true>")))
+    for tile, h, d, c, wps, ring in SELECT:
+        name = _pairsel_name(tile, h, d, c, wps, ring)
+        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
+            name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}, false, true>")))
+        if _has_coop(h):
+            files.append(_write(GEN / f"{name}_coop.hip", _launcher_unit(
+                f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4, true, true>")))
     decls = "\n".join(
         [f"int launch_{_inst_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES] +
         [f"int launch_{_inst_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES
@@ -244,11 +264,16 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
         [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES] +
         [f"int launch_{_pair_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES] +
         [f"int launch_{_pair_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES
+         if _has_coop(i[1])] +
+        [f"int launch_{_pairsel_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SELECT] +
+        [f"int launch_{_pairsel_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SELECT
          if _has_coop(i[1])]
     )
     pair_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pair_name(*i)}, "{_pair_name(*i)}", '
-        + (f"launch_{_pair_name(*i)}_coop" if _has_coop(i[1]) else "nullptr") + "}" for i in PAIR_INSTANCES
+        + (f"launch_{_pair_name(*i)}_coop" if _has_coop(i[1]) else "nullptr") + ", "
+        + (f"launch_{_pairsel_name(*i)}" if i in SELECT else "nullptr") + ", "
+        + (f"launch_{_pairsel_name(*i)}_coop" if i in SELECT and _has_coop(i[1]) else "nullptr") + "}" for i in PAIR_INSTANCES
     )
     split_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_split_name(*i)}, "{_split_name(*i)}"}}' for i in SPLIT_INSTANCES
@@ -267,7 +292,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     if not SPLIT_INSTANCES:          # (a test variant without the family: one inert row, count 0 -- no zero-length array)
         split_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
     if not PAIR_INSTANCES:           # (the test variants carry no pair kernels)
-        pair_rows = '    {0, 0, 0, 0, 0, nullptr, "", nullptr}'
+        pair_rows = '    {0, 0, 0, 0, 0, nullptr, "", nullptr, nullptr, nullptr}'
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 namespace ff {{
@@ -308,6 +333,8 @@ def _cost(src: Path) -> float:
         return 95 if "_t1" in n else 55
     if "_h512_" in n:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
+    if n.startswith("mlp_pairsel_"):
+        return (7 if "_h256_" in n else 3) if "_coop" in n else (16 if "_h256_" in n else 7)
     if n.startswith("mlp_pair_"):
         return (12 if "_h256_" in n else 5) if "_coop" in n else (30 if "_h256_" in n else 12)
     if "_h256_" in n:
@@ -392,7 +419,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
         for name, v in VARIANTS.items():
             gen, obj = PKG / "_build" / f"gen_{name}", PKG / "_build" / f"obj_{name}"
             obj.mkdir(parents=True, exist_ok=True)
-            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"])
+            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"], select=v.get("select", []))
             extra[name] = (vs, obj, tuple(v["defines"]))
             units += [(s, obj, tuple(v["defines"])) for s in vs]
     jobs = jobs or min(8, os.cpu_count() or 1)

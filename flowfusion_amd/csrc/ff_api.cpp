@@ -168,17 +168,39 @@ static ff::Layout plan_layout(const ff_mlp_plan_t* p)
     return ff::make_layout(p->tile, p->width, p->dregs, p->cregs, p->n_hidden);
 }
 
-// a pair plan (ff_mlp_pair_plan): kernel ids FF_PAIR_KERNEL_BASE + i, a range no other plan uses
-static bool plan_ok_pair(const ff_mlp_plan_t* p)
+// a pair plan (ff_mlp_pair_plan): kernel ids FF_PAIR_KERNEL_BASE + i, a range no other plan uses; a select plan
+// (ff_mlp_pair_select_plan): FF_PAIR_SELECT_KERNEL_BASE + i, the same index into the same table
+static bool plan_ok_pair_at(const ff_mlp_plan_t* p, int base)
 {
-    if (!p || p->precision != FF_PREC_F32 || p->kernel_id < FF_PAIR_KERNEL_BASE ||
-        p->kernel_id >= FF_PAIR_KERNEL_BASE + ff::g_n_pair_kernels)
+    if (!p || p->precision != FF_PREC_F32 || p->kernel_id < base || p->kernel_id >= base + ff::g_n_pair_kernels)
         return false;
-    const ff::PairKernelEntry& k = ff::g_pair_kernels[p->kernel_id - FF_PAIR_KERNEL_BASE];
+    const ff::PairKernelEntry& k = ff::g_pair_kernels[p->kernel_id - base];
     const int per_reg = 64 / k.tile;
     return k.H == p->width && k.dregs == p->dregs && k.cregs == p->cregs && k.tile == p->tile && p->n_hidden >= 1 &&
            p->activation == FF_ACT_SILU && p->dim >= 2 && p->dim % 2 == 0 && p->dim <= per_reg * p->dregs &&
            p->cond_dim >= 0 && p->cond_dim <= per_reg * p->cregs;
+}
+
+static bool plan_ok_pair(const ff_mlp_plan_t* p) { return plan_ok_pair_at(p, FF_PAIR_KERNEL_BASE); }
+
+static bool plan_ok_select(const ff_mlp_plan_t* p)
+{
+    return plan_ok_pair_at(p, FF_PAIR_SELECT_KERNEL_BASE) &&
+           ff::g_pair_kernels[p->kernel_id - FF_PAIR_SELECT_KERNEL_BASE].launch_select != nullptr;
+}
+
+// "mlp_pair_<shape>" -> "mlp_pairsel_<shape>": the select kernels are named after the pair kernel of their shape
+static const char* select_kernel_name(int index)
+{
+    static char names[8][64];
+    if (index < 0 || index >= 8) return NULL;
+    if (!names[index][0]) {
+        const char* pn = ff::g_pair_kernels[index].name;
+        char buf[64];
+        snprintf(buf, sizeof(buf), "mlp_pairsel_%s", strncmp(pn, "mlp_pair_", 9) == 0 ? pn + 9 : pn);
+        memcpy(names[index], buf, sizeof(buf));
+    }
+    return names[index];
 }
 
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
@@ -186,6 +208,7 @@ extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
     if (plan_ok_split(plan)) return ff::g_split_kernels[plan->kernel_id].name;
     if (plan_ok(plan)) return ff::g_kernels[plan->kernel_id].name;
     if (plan_ok_pair(plan)) return ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE].name;
+    if (plan_ok_select(plan)) return select_kernel_name(plan->kernel_id - FF_PAIR_SELECT_KERNEL_BASE);
     return NULL;
 }
 
@@ -199,7 +222,17 @@ extern "C" const char* ff_pair_kernel_name(int index)
 extern "C" int ff_mlp_row_width(const ff_mlp_plan_t* plan)
 {
     if (!plan) return -1;
-    return plan_ok_pair(plan) ? 2 * plan->width : plan->width;
+    return plan_ok_pair(plan) ? 2 * plan->width : plan->width;      // (a select row carries one network's c1)
+}
+
+extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
+{
+    const int rc = ff_mlp_pair_plan(dim, cond_dim, n_hidden, hidden_widths, plan);      // one envelope, one preference
+    if (rc != FF_OK) return rc;
+    const int index = plan->kernel_id - FF_PAIR_KERNEL_BASE;
+    if (ff::g_pair_kernels[index].launch_select == nullptr) { memset(plan, 0, sizeof(*plan)); return FF_ERR_UNSUPPORTED; }
+    plan->kernel_id = FF_PAIR_SELECT_KERNEL_BASE + index;
+    return FF_OK;
 }
 
 extern "C" int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
@@ -238,7 +271,7 @@ extern "C" int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* 
 
 extern "C" size_t ff_mlp_pair_wpack_floats(const ff_mlp_plan_t* plan)
 {
-    if (!plan_ok_pair(plan)) return 0;
+    if (!plan_ok_pair(plan) && !plan_ok_select(plan)) return 0;
     return 2 * plan_layout(plan).total_floats;
 }
 
@@ -435,7 +468,7 @@ extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* 
                                  const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
                                  int x_col0, int c_col0, float* out)
 {
-    if (!plan_ok_pair(plan) || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
+    if ((!plan_ok_pair(plan) && !plan_ok_select(plan)) || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
     const int D2 = plan->dim, Dh = D2 / 2, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
     if (x_col0 < 0 || x_col0 + Dh > in_features0) return FF_ERR_BADARG;
     if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
@@ -479,7 +512,7 @@ extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* 
 
 extern "C" int ff_mlp_samples_per_workgroup(const ff_mlp_plan_t* plan, int mode)
 {
-    if (plan_ok_pair(plan)) return mode == FF_MODE_STATE ? 4 * plan->tile : FF_ERR_BADARG;
+    if (plan_ok_pair(plan) || plan_ok_select(plan)) return mode == FF_MODE_STATE ? 4 * plan->tile : FF_ERR_BADARG;
     if (plan_ok_split(plan)) {
         const int kt = ff::g_split_kernels[plan->kernel_id].tangents;
         if (mode == FF_MODE_STATE && kt == 0) return 128;
@@ -563,6 +596,10 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
 // above pick the faster kernel at every measured tile count and stay.  At three (width 128) the twin's line is steeper and
 // starts lower -- c0 = 0.03, 0.85 of a chip's worth per round: with 0.10 / 0.95 the rule took the one-wavefront kernel at
 // 768 tiles (5 % slower there) and the twin at 2560 (7 % slower).
+// Row-select kernels (profiles/pair_select.txt; a row is ONE network on the one-wavefront kernel and on the twin alike, so
+// the units carry over): they cross where the pair kernels of their width do.  Width 256 keeps the constants above (the
+// faster kernel at all ten measured sizes); width 128 with 0.10 / 0.95 took the one-wavefront kernel at 768 tiles, 6 %
+// slower there than the twin, and takes the pair instance's 0.03 / 0.85.
 // The tail of a launch.  The chip runs 1024 * wps tiles at once; the tiles left over after the full rounds run as a last
 // round with w = ceil(leftover / 1024) wavefronts per SIMD, which takes w / wps of a full round's time (measured: the
 // dispatcher fills SIMDs evenly, a wavefront does not finish sooner for having fewer neighbours than wps allows).
@@ -609,6 +646,14 @@ static ff::KernelEntry pair_as_entry(const ff::PairKernelEntry& p)
     return k;
 }
 
+// A select kernel as choose_launch sees it (its twin's line is the pair twin's: the comment above choose_launch).
+static ff::KernelEntry select_as_entry(const ff::PairKernelEntry& p)
+{
+    ff::KernelEntry k = pair_as_entry(p);
+    k.launch = p.launch_select; k.launch_coop = p.launch_select_coop;
+    return k;
+}
+
 // What ff_mlp_ode_launch would enqueue for `batch` samples in `mode`: FF_LAUNCH_* (see the header).
 extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int32_t mode, int32_t tangent_count, int32_t jac_out)
 {
@@ -617,6 +662,12 @@ extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int3
         if (batch < 0 || mode != FF_MODE_STATE || jac_out) return FF_ERR_BADARG;
         const ff::PairKernelEntry& pk = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE];
         const LaunchChoice ch = choose_launch(pair_as_entry(pk), (batch + plan->tile - 1) / plan->tile, false, true);
+        return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
+    }
+    if (plan_ok_select(plan)) {
+        if (batch < 0 || mode != FF_MODE_STATE || jac_out) return FF_ERR_BADARG;
+        const ff::PairKernelEntry& pk = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_SELECT_KERNEL_BASE];
+        const LaunchChoice ch = choose_launch(select_as_entry(pk), (batch + plan->tile - 1) / plan->tile, false, true);
         return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
     }
     if (!plan_ok(plan) || batch < 0) return FF_ERR_BADARG;
@@ -630,8 +681,9 @@ extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int3
     return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
 }
 
-// pair plans (ff_mlp_pair.hpp): state-only integration of a table whose rows carry c1 of both networks
-static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
+// pair plans (ff_mlp_pair.hpp): state-only integration of a table whose rows carry c1 of both networks; select plans: of
+// a table whose rows carry c1 of the one network they run (no first stage from the caller, no auxiliary outputs)
+static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream, bool select = false)
 {
     if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
@@ -639,8 +691,10 @@ static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hi
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->n_aux < 0 || a->n_aux > FF_MAX_AUX) return FF_ERR_BADARG;
     if (a->noise && a->noise_stride < a->batch * (int64_t)plan->dim) return FF_ERR_BADARG;
+    if (select && (a->k1_in || a->n_aux > 0)) return FF_ERR_BADARG;
     if (a->batch == 0) return FF_OK;
-    const ff::PairKernelEntry& k = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE];
+    const ff::PairKernelEntry& k = ff::g_pair_kernels[plan->kernel_id - (select ? FF_PAIR_SELECT_KERNEL_BASE : FF_PAIR_KERNEL_BASE)];
+    const ff::KernelEntry ke = select ? select_as_entry(k) : pair_as_entry(k);
     ff::KernelArgs ka;
     memset(&ka, 0, sizeof(ka));
     ka.gate = a->gate;
@@ -652,14 +706,14 @@ static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hi
     ka.k1_in = a->k1_in; ka.n_aux = a->n_aux;
     for (int j = 0; j < FF_MAX_AUX; ++j) ka.aux_out[j] = a->aux_out[j];
     ka.rng_seed = a->rng_seed; ka.rng_sample_offset = a->rng_sample_offset; ka.rng_noise_base = a->rng_noise_base;
-    ka.etab_stride = FF_ROW_HDR + 2 * plan->width;
+    ka.etab_stride = FF_ROW_HDR + (select ? 1 : 2) * plan->width;
     const ff::Layout L = plan_layout(plan);
     if (2 * L.total_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)(2 * L.total_floats);
     // one-wavefront kernel, cooperative twin, or full rounds on the first and the leftover rows on the twin (choose_launch)
     const long long spt = plan->tile;
-    const LaunchChoice ch = choose_launch(pair_as_entry(k), (a->batch + spt - 1) / spt, false, true);
+    const LaunchChoice ch = choose_launch(ke, (a->batch + spt - 1) / spt, false, true);
     const bool coop = ch.coop;
     const long long main_tiles = ch.main_tiles, tail_tiles = ch.tail_tiles;
     const unsigned slots = ff::kSlots * (plan->dregs / 4) * 64 * 16;
@@ -669,7 +723,7 @@ static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hi
     const long long grid = coop ? main_tiles : (main_tiles + 3) / 4;
     if (grid > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
     if (tail_tiles) ka.batch = main_tiles * spt;                                       // (full tiles only: < a->batch)
-    int herr = (coop ? k.launch_coop : k.launch)(&ka, (unsigned)grid, coop ? lds_coop : lds_wave, (hipStream_t)hip_stream);
+    int herr = (coop ? ke.launch_coop : ke.launch)(&ka, (unsigned)grid, coop ? lds_coop : lds_wave, (hipStream_t)hip_stream);
     if (herr == 0 && tail_tiles) {
         // the same launch over rows [row0, batch), as in ff_mlp_ode_launch
         const long long row0 = main_tiles * spt, D = plan->dim, C = plan->cond_dim;
@@ -682,7 +736,7 @@ static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hi
         for (int j = 0; j < FF_MAX_AUX; ++j)
             if (t.aux_out[j]) t.aux_out[j] += row0 * D;
         t.rng_sample_offset += row0;
-        herr = k.launch_coop(&t, (unsigned)tail_tiles, lds_coop, (hipStream_t)hip_stream);
+        herr = ke.launch_coop(&t, (unsigned)tail_tiles, lds_coop, (hipStream_t)hip_stream);
     }
     if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
     return FF_OK;
@@ -692,6 +746,7 @@ extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a
 {
     if (a && plan_ok_split(plan)) return launch_split(plan, a, hip_stream);
     if (a && plan_ok_pair(plan)) return launch_pair(plan, a, hip_stream);
+    if (a && plan_ok_select(plan)) return launch_pair(plan, a, hip_stream, true);
     if (!plan_ok(plan) || !a) return FF_ERR_BADARG;
     if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;

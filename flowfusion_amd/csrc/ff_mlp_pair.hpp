@@ -25,12 +25,24 @@
 //     of the finished right-hand side into that slot and a slow wavefront's read of the parked value): it stays in registers.
 // tests/test_gpu_symplectic_skew.py holds a wavefront back at each of the three (ff_skew.h; -DFF_DEBUG_UNFIX parks net A in
 // the shared slot again, so that the test can see the third go wrong).
+//
+// SELECT (row-select variant, ff_mlp_pair_select_plan): a row runs ONE network, chosen by the row -- net B if its flag word
+// has FF_ROW_NET_B, net A otherwise -- and carries only that network's c1 (row stride FF_ROW_HDR + width).  The other half
+// of the network output is exact zero (zero rows and zero bias in the pack), so with a_e = 0 the row's right-hand side and
+// its STEP_END update move one half of the state and leave the other bitwise alone: the shears of a kick-drift-kick
+// leapfrog (solvers.plan_leapfrog).  Same packed weights, same KernelArgs, same stage bookkeeping.  The weight ring's wrap
+// at the output layer and the pre-load of the next c1 target the NEXT ROW's network, whichever that is (rows need not
+// alternate): its flag word is read through the bounds-checked table stream, so the row after the last reads as zeros.
+// The cooperative SELECT twin shares the zero-fill barrier and the launch-wide exchange-buffer alternation with the pair
+// twin; the third hazard does not exist here: there is no second network per row, so nothing is parked.
 #pragma once
 #include "ff_mlp_ode.hpp"
 
 namespace ff {
 
-template <int TILE, int H, int DREGS, int CREGS, int WPS, int RING, bool COOP = false>
+constexpr uint32_t kRowNetB = 4u;                     // FF_ROW_NET_B (SELECT rows)
+
+template <int TILE, int H, int DREGS, int CREGS, int WPS, int RING, bool COOP = false, bool SELECT = false>
 __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs args)
 {
     static_assert(kChunkPad % RING == 0, "ring must divide the chunk padding");
@@ -43,7 +55,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     constexpr int K1 = DREGS + CREGS;
     constexpr int KH = NB * RB;                      // operand registers of a hidden layer
     constexpr int R4 = DREGS / 4;
-    constexpr int NSUB = 2;                          // networks per evaluation
+    constexpr int NSUB = SELECT ? 1 : 2;             // networks per evaluation row
     typedef const __attribute__((address_space(4))) RowHdr* HdrPtr;   // scalar (SMEM) loads
 
     if (args.gate && *(const volatile int*)args.gate == 0) return;
@@ -117,6 +129,15 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     const int sub_bytes = (int)(L.total_floats * 4);   // one network's pack: net B's starts here
     const Stream ws = make_stream(args.wpack, args.wpack_floats);
     const Stream ts = make_stream(args.etab, (long long)(args.n_evals + (args.n_aux > 0 ? 2 : 0)) * args.etab_stride);
+    // SELECT: the pack (byte offset in the weight stream) of the network that table row `e` runs.  Read through the
+    // bounds-checked table stream: the row after the last one reads as zeros (net A), whatever lies behind the buffer.
+    [[maybe_unused]] auto row_pack = [&](int e) __attribute__((always_inline)) {
+        const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)__builtin_amdgcn_raw_buffer_load_b32(ts.rsrc, 0, e * args.etab_stride * 4 + 12, 0));      // RowHdr::flags
+        return (f & kRowNetB) ? sub_bytes : 0;
+    };
+    [[maybe_unused]] int sb_row = 0;                   // SELECT: this row's network; the ring and hacc already hold its head
+    if constexpr (SELECT) sb_row = row_pack(0);
     const int out_sbyte = L.chunk_off_out() * CB;
     const int out_bias_byte = (int)(L.bias_off_out() * 4);
 
@@ -131,13 +152,14 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
         return sbyte + chunk_index(G, g < G.G ? g : 0, b0 + j) * CB;      // (padding visits re-read a real chunk)
     };
 
-    // prefetch ring: the first RING chunks of net A's layer 1 (of this wavefront's visiting list in the cooperative twin)
+    // prefetch ring: the first RING chunks of net A's layer 1 (of this wavefront's visiting list in the cooperative twin);
+    // SELECT: of the layer 1 of row 0's network
     f32x4 ring[RING][T::PHYS];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
 #pragma unroll
         for (int p = 0; p < T::PHYS; ++p)
-            ring[i][p] = sload(ws, lane16, (COOP ? coop_byte(CG1, 0, i, NBW, ob0) : i * CB) + p * 1024);
+            ring[i][p] = sload(ws, lane16, (COOP ? coop_byte(CG1, sb_row, i, NBW, ob0) : sb_row + i * CB) + p * 1024);
 
     float P[KH];                 // operand registers of a hidden layer
     // hidden accumulators: they hold the bias of the layer about to run (row 0's c1 of net A to start with)
@@ -156,6 +178,8 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
         const float a_e = hdr->a, b_e = hdr->b;
         const uint32_t flags = hdr->flags;
         const int slot = hdr->slot;
+        [[maybe_unused]] int sb_next = 0;            // SELECT: the NEXT row's network (prefetch target of the output layer)
+        if constexpr (SELECT) sb_next = row_pack(e + 1);
 
         // stage input  y = x + sum_s cin[s] * k[s]
         float y[K1];
@@ -249,7 +273,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
             [[maybe_unused]] float net_a[DREGS];
             static_for<NSUB>([&](auto ss) {
                 constexpr int sub = decltype(ss)::value;
-                const int sb = sub * sub_bytes;          // this network's pack in the weight stream
+                const int sb = SELECT ? sb_row : sub * sub_bytes;          // this network's pack in the weight stream
                 auto next_hidden_or_out = [&](int l_next, auto kk, auto sl) __attribute__((always_inline)) {
                     // visit k of the layer after a hidden-side layer: hidden layer l_next, or the output layer
                     constexpr int k = decltype(kk)::value, rs = decltype(sl)::value;
@@ -292,14 +316,14 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                     constexpr int k = decltype(kk)::value, rs = decltype(sl)::value;
                     static_for<T::PHYS>([&](auto pp) {
                         constexpr int p = decltype(pp)::value;
-                        ring[rs][p] = sload(ws, lane16, coop_byte(CG1, sub == 0 ? sub_bytes : 0, k, NBW, ob0) + p * 1024);
+                        ring[rs][p] = sload(ws, lane16, coop_byte(CG1, SELECT ? sb_next : (sub == 0 ? sub_bytes : 0), k, NBW, ob0) + p * 1024);
                     });
                 });
 #pragma unroll
                 for (int o = 0; o < NOB_OUT; ++o)
 #pragma unroll
                     for (int r = 0; r < RB; ++r) net[o * RB + r] = oacc[o].reg(r) + obias[o].reg(r);
-                if constexpr (sub == 0) {
+                if constexpr (sub == 0 && !SELECT) {
 #if defined(FF_DEBUG_UNFIX)
                     // (test builds: the one-wavefront kernel's parking place, which four wavefronts share here)
                     if (slot_ok) {
@@ -314,7 +338,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                 }
             });
             FF_SKEW_HOLD(wv == kSkewWave, 2);           // (test builds: late to pick net A's output up again)
-            if (slot_ok) {
+            if (!SELECT && slot_ok) {
 #if defined(FF_DEBUG_UNFIX)
 #pragma unroll
                 for (int j = 0; j < R4; ++j) {
@@ -380,7 +404,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
 
         static_for<NSUB>([&](auto ss) {
             constexpr int sub = decltype(ss)::value;
-            const int sb = sub * sub_bytes;          // this network's pack in the weight stream
+            const int sb = SELECT ? sb_row : sub * sub_bytes;          // this network's pack in the weight stream
             // ---- layer 1: [y | cond] -> H, bias c1 of this network (already in hacc) -----------------------------
             {
                 using G1 = GeomTag<TILE, K1, NB>;
@@ -405,8 +429,8 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
             }
             // ---- output layer ------------------------------------------------------------------------------------
             // the hidden accumulators take the next network's c1: net B's of this row after net A, net A's of the
-            // next row after net B (a row past the table reads as zeros)
-            const int c1_next = sub == 0 ? row_byte + 128 + H * 4 : row_byte + args.etab_stride * 4 + 128;
+            // next row after net B (a row past the table reads as zeros); SELECT: the next row's only c1
+            const int c1_next = (sub == 0 && !SELECT) ? row_byte + 128 + H * 4 : row_byte + args.etab_stride * 4 + 128;
 #pragma unroll
             for (int o = 0; o < NB; ++o) hacc[o] = load_bias_acc<TILE>(ts, q16, c1_next + o * 128);
             BlockAcc<TILE> oacc[NOB_OUT];
@@ -438,8 +462,8 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                     for (int r = 0; r < RB; ++r)
                         net[(NOB_OUT - 1) * RB + r] = acc.reg(r) + bias[(NOB_OUT - 1) & 1].reg(r);
                 },
-                sub == 0 ? sub_bytes : 0);
-            if constexpr (sub == 0) {
+                SELECT ? sb_next : (sub == 0 ? sub_bytes : 0));
+            if constexpr (sub == 0 && !SELECT) {
                 if (slot_ok) {
 #pragma unroll
                     for (int j = 0; j < R4; ++j)
@@ -447,7 +471,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                 }
             }
         });
-        if (slot_ok) {
+        if (!SELECT && slot_ok) {
 #pragma unroll
             for (int j = 0; j < R4; ++j) {
                 const f32x4 na = ks[(slot * R4 + j) * 64];
@@ -477,6 +501,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                 for (int i = 0; i < 4; ++i) x[4 * j + i] = v[i];
             }
         }
+        if constexpr (SELECT) sb_row = sb_next;
         if (flags & 2u) {
             // noise rows: read where they are used (two networks' worth of registers are live across the evaluation)
             float nz[DREGS];

@@ -51,6 +51,10 @@ struct PairKernelEntry {
     LaunchFn launch;
     const char* name;
     LaunchFn launch_coop;   // cooperative twin for small batches (one tile per workgroup) or NULL
+    // row-select variant of the same shape (ff_mlp_pair_select_plan: kernel_id FF_PAIR_SELECT_KERNEL_BASE + the index): a row
+    // runs one of the two networks.  Not entries of a table of their own; NULL where a library carries none.
+    LaunchFn launch_select;
+    LaunchFn launch_select_coop;
 };
 extern const PairKernelEntry g_pair_kernels[];
 extern const int g_n_pair_kernels;

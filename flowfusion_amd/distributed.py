@@ -310,13 +310,14 @@ def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: O
 # ---- the symplectic flows (flowfusion/symplectic.py:166-253) ------------------------------------------------------------------
 def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: Optional[torch.Tensor] = None,
                               num_steps: int = 1, group=None, gather: bool = True,
-                              local_conditional: Optional[torch.Tensor] = None):
+                              local_conditional: Optional[torch.Tensor] = None, method: str = "euler"):
     """``SymplecticFlowModel.sample`` of ``n_total`` prior draws over all ranks.  This rank's rows of the prior [q | p]
     are standard normals of the library's counter-based stream keyed by ``seed`` and the GLOBAL row (``ff_normal_fill``
     with its default noise index, the one reserved for prior draws) -- NOT torch's generator, which the unsharded
     ``sample`` keeps drawing from as the reference does -- so every world size transports the same points and a rank only
     ever touches its own rows.  ``symplectic_log_prob_sharded`` draws its momenta from the same stream and index: pass
-    different seeds where the two draws must be unrelated.  The grid is fixed (``num_steps`` Euler steps), so there is no
+    different seeds where the two draws must be unrelated.  The grid is fixed (``num_steps`` steps of ``method``: "euler" or
+    "leapfrog"), so there is no
     collective but the final all-gather (``gather=False`` keeps the shard and returns its bounds); a rank without rows is
     fine.  ``conditional`` is the raw [n_total, C] tensor (every rank slices its rows) or ``local_conditional`` this
     rank's rows.  More than one rank over RCCL has not been run on hardware, like everything else multi-rank here."""
@@ -330,7 +331,7 @@ def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: O
     dim = 2 * int(model.shift.numel()) if model.shift is not None else int(model._net().dim)
     x = _native.normal_fill(hi - lo, dim, int(seed), lo, dev)
     cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
-    local = model._sample_from(x, cond, int(num_steps))
+    local = model._sample_from(x, cond, int(num_steps), **({} if method == "euler" else {"method": method}))
     if not gather:
         return local, (lo, hi)
     return gather_rows(local, n, group) if world > 1 else local
@@ -339,7 +340,8 @@ def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: O
 def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,
                                 seed: int = 0, group=None, gather: bool = True, local_x: Optional[torch.Tensor] = None,
                                 n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None,
-                                global_control: bool = True, atol: float = 1e-5, rtol: float = 1e-5):
+                                global_control: bool = True, atol: float = 1e-5, rtol: float = 1e-5,
+                                method: str = "dopri5", num_steps: Optional[int] = None):
     """``SymplecticFlowModel.log_prob`` of a [B, D] batch over all ranks; one all-gather of the [B] result at the end.
     ``x`` (and ``conditional``) are the full tensors, every rank slicing its rows -- or ``local_x`` (and
     ``local_conditional``) this rank's rows already, with ``n_total`` the size of the whole batch.  The momentum draw
@@ -349,7 +351,10 @@ def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditi
     seeds where the two draws must be unrelated.  The solve is adaptive dopri5: with ``global_control`` the step size
     comes from the error norm of the WHOLE batch (``global_step_control``; every rank needs at least one row), so every
     rank takes the same steps and a row's result does not depend on the world size beyond the rounding of those norms;
-    ``global_control=False``: every rank steps from its own rows and enters no exchange.  More than one rank over RCCL has
+    ``global_control=False``: every rank steps from its own rows and enters no exchange.  ``method="leapfrog"`` with
+    ``num_steps``: the fixed flipped grid of ``sample(.., method="leapfrog")`` in one launch per rank -- no collective but the
+    final gather, ``global_control`` is ignored, ranks without rows are fine and a row's result is bitwise independent of
+    the world size.  More than one rank over RCCL has
     not been run on hardware, like everything else multi-rank here."""
     from . import _native
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -367,8 +372,9 @@ def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditi
         raise ValueError("local_x goes with local_conditional, not the full `conditional`")
     cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
     p0 = _native.normal_fill(hi - lo, int(rows.shape[1]), int(seed), lo, rows.device)
-    with _step_control(n, world, group, global_control, "dopri5"):
-        local = model._log_prob_from(rows, p0, cond, atol, rtol, method="dopri5")
+    with _step_control(n, world, group, global_control, method):
+        local = model._log_prob_from(rows, p0, cond, atol, rtol, method=method,
+                                     **({} if num_steps is None else {"num_steps": num_steps}))
     if not gather:
         return local, (lo, hi)
     return gather_rows(local, n, group) if world > 1 else local

@@ -164,10 +164,11 @@ class FusedNet:
                   cond: Optional[torch.Tensor] = None, probe: Optional[torch.Tensor] = None,
                   noise: Optional[torch.Tensor] = None,
                   in_shift=None, in_scale=None, out_scale=None, out_shift=None,
-                  rng: Optional[Tuple[int, int, int]] = None, stage_slots: int = 0):
+                  rng: Optional[Tuple[int, int, int]] = None, stage_slots: int = 0, plan=None):
         """Run the fused integration.  Returns (y_final [B,D], dlogp [B] or empty, status [1]).
         ``rng = (seed, global index of row 0, noise index of table row 0)`` selects in-kernel noise for
-        tables with noise rows (instead of a ``noise`` buffer)."""
+        tables with noise rows (instead of a ``noise`` buffer).  ``plan``: another plan of this network that shares the
+        mode's packed weights (``FusedPair``'s select plan); default ``self.plan(mode)``."""
         if not x.is_cuda:
             raise RuntimeError(
                 "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
@@ -175,7 +176,7 @@ class FusedNet:
         if x.dim() != 2 or x.shape[1] != self.dim:
             raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(x.shape)}")
         dev = x.device
-        plan = self.plan(mode)
+        plan = self.plan(mode) if plan is None else plan
         f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
         if self.cond_dim > 0:
             if cond is None:
@@ -298,7 +299,10 @@ class FusedPair(FusedNet):
     half of the state [q | p] and ``mlp_p`` reading the q half, each ``Linear -> SiLU -> ... -> Linear`` with first-layer
     input ``[state half | cond | time features]``, on one two-network kernel (csrc/ff_mlp_pair.hpp).  State-only: the
     field is divergence-free by construction.  ``dim`` is the whole state (2D); evaluation rows carry the c1 of net A
-    (mlp_q), then net B's (mlp_p), ``width`` words each."""
+    (mlp_q), then net B's (mlp_p), ``width`` words each.
+
+    A second plan kind, ``select=True`` (``ff_mlp_pair_select_plan``, the leapfrog route): the same shape and the same
+    packed weights on the row-select kernel, whose rows run one network each and carry that network's c1 only."""
 
     def __init__(self, q_linears: Sequence[nn.Linear], p_linears: Sequence[nn.Linear], dim: int, cond_dim: int,
                  x_col0: int, c_col0: int):
@@ -316,12 +320,20 @@ class FusedPair(FusedNet):
         return (super().serves(linears, act, precision) and len(p_linears) == len(self.p_linears)
                 and all(a is b for a, b in zip(p_linears, self.p_linears)))
 
-    def plan(self, mode: int) -> _native.PlanStruct:
+    def plan(self, mode: int, select: bool = False) -> _native.PlanStruct:
         if mode != MODE_STATE:
             raise NotImplementedError("the two-network kernels integrate the state only (the field is divergence-free)")
-        if 0 not in self._plans:
-            self._plans[0] = _native.make_pair_plan(self.dim, self.cond_dim, self.hidden)
-        return self._plans[0]
+        key = "select" if select else 0
+        if key not in self._plans:
+            self._plans[key] = _native.make_pair_plan(self.dim, self.cond_dim, self.hidden, select=select)
+        return self._plans[key]
+
+    def integrate_select(self, x, etab, cond=None, **maps):
+        """``integrate`` of a table of select rows (solvers.plan_leapfrog): on the select plan, and on nothing else."""
+        plan = self.plan(MODE_STATE, select=True)
+        if not _native.is_select_plan(plan):
+            raise RuntimeError("select rows need a select plan")
+        return self.integrate(x, etab, MODE_STATE, cond=cond, stage_slots=1, plan=plan, **maps)
 
     def _param_key(self, device, plan) -> Tuple:
         vers = tuple((p.data_ptr(), p._version) for l in self.linears + self.p_linears for p in (l.weight, l.bias))
@@ -366,9 +378,9 @@ class FusedPair(FusedNet):
             self._time_cols = hit
         return hit[1], hit[2]
 
-    def width(self, mode: int = MODE_STATE) -> int:
-        """First-layer bias words per evaluation row: two networks' worth."""
-        return 2 * int(self.plan(mode).width)
+    def width(self, mode: int = MODE_STATE, select: bool = False) -> int:
+        """First-layer bias words per evaluation row: two networks' worth; one network's on the select plan."""
+        return (1 if select else 2) * int(self.plan(mode).width)
 
     def stage_slots(self, mode: int = MODE_STATE) -> int:
         return 7

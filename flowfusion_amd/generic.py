@@ -17,7 +17,7 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from . import _native, solvers
-from .solvers import FLAG_STEP_END, MAX_SLOTS
+from .solvers import FLAG_NET_B, FLAG_STEP_END, MAX_SLOTS
 
 # rhs(t [0-dim fp32 tensor on the state's device, real time], y [B, D]) -> (ydot [B, D], div [B] or None)
 Rhs = Callable[[torch.Tensor, torch.Tensor], Tuple[torch.Tensor, Optional[torch.Tensor]]]
@@ -75,6 +75,20 @@ class ModuleStepper:
                 if self.has_lp:
                     lp = _combine(lp, kl, cout[e][:MAX_SLOTS], lp)
         return x, lp
+
+    def run_leapfrog(self, x: torch.Tensor, plan: solvers.EvalPlan):
+        """The rows of ``solvers.plan_leapfrog``: every row is one shear ``x += w * sign * f_half(t, x)``, where this
+        stepper's ``rhs(t, y, net_b)`` returns the derivative of the row's half of the state and exact zeros on the other
+        (one ff_stage_combine launch per row).  Returns the final state."""
+        _need_gpu(x)
+        x = x.detach().to(torch.float32).contiguous()
+        t_eval, flags, w = plan.t_eval.tolist(), plan.flags.tolist(), plan.cout[:, 0].tolist()
+        for e in range(len(t_eval)):
+            t = torch.tensor(t_eval[e], dtype=torch.float32, device=x.device)
+            k = self.rhs(t, x, bool(flags[e] & FLAG_NET_B)).detach().to(torch.float32).contiguous()
+            self.n_evals += 1
+            x = _combine(x, [k], [plan.sign * w[e]], x)
+        return x
 
     def make_step(self, sign: float):
         """Step function for ``adaptive.Dopri5`` (same contract as ``FusedNet.make_step``): the rows fill the stage

@@ -90,6 +90,26 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
     return y, lp
 
 
+def solve_leapfrog(front, x, grid, cond=None):
+    """Kick-drift-kick leapfrog of a separable front end (symplectic.py) over the nodes ``grid``; returns the state
+    [B, 2D] and sets ``front.last_solver_stats``.  Compiled shapes: ONE fused launch of the row-select kernel on the table
+    of ``solvers.plan_leapfrog``.  Everything else: the same rows stepped by the library around torch (generic.py), one
+    network -- or the needed half of a foreign module's output -- per row."""
+    require_fp32(front, x, cond, what="an ODE solve")
+    if front._fusable():
+        net = front._net()
+        key = ("leapfrog", tuple(float(v) for v in grid)) + front._schedule_key()
+        table = net.cached_table(key, x.device, lambda: front._leapfrog_table(grid))
+        y, _, _ = net.integrate_select(x, table, cond=cond)
+        front.last_solver_stats = {"evaluations": int(table.shape[0]), "launches": 1}
+        return y
+    _need_gpu(x)
+    stepper = ModuleStepper(front._module_half_rhs(cond), False)
+    y = stepper.run_leapfrog(x, solvers.plan_leapfrog(grid))
+    front.last_solver_stats = {"evaluations": stepper.n_evals}
+    return y
+
+
 def _host_adaptive(front, step, x, t, sign, method, options, mode, atol, rtol, norm_only):
     """The host controller around any of the three step functions (``FusedNet`` / ``RowStepper`` / ``ModuleStepper``)."""
     has_lp = mode != MODE_STATE

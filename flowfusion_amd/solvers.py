@@ -47,6 +47,7 @@ ROW_HDR = 32          # words in the row header (FF_ROW_HDR)
 MAX_SLOTS = 7         # stage slots on chip (FF_MAX_SLOTS)
 FLAG_STEP_END = 1
 FLAG_NOISE = 2
+FLAG_NET_B = 4        # select plans: the row runs net B (FF_ROW_NET_B)
 
 _one_third = 1.0 / 3.0
 _two_thirds = 2.0 / 3.0
@@ -210,6 +211,45 @@ def plan_ode(t_span: torch.Tensor, method: str, options: Optional[dict], y0=None
         cout=cout.reshape(n_evals, 8),
         n_steps=n_steps,
     )
+
+
+def plan_leapfrog(grid: torch.Tensor) -> EvalPlan:
+    """Rows of a kick-drift-kick leapfrog over the nodes ``grid`` = t_0 .. t_n (fp32, either direction) of a separable
+    field ``[net A(p half), net B(q half)]`` on a row-select plan: every row runs ONE network (``FLAG_NET_B`` = kick, else
+    drift), writes slot 0 and ends a step, so each row is a shear of one half of the state.
+
+    With h_k = t_{k+1} - t_k in solver time (a decreasing grid is negated, ``sign`` multiplies ``b`` as in ``plan_ode``):
+    kick h_0/2 at t_0; then per step a drift h_k at the midpoint (t_k + t_{k+1}) / 2 and a kick at t_{k+1} of weight
+    (h_k + h_{k+1}) / 2 -- the half-kicks of consecutive steps merged -- or h_{n-1}/2 after the last step: 2n + 1 rows.
+    Midpoints and merged weights are symmetric expressions of the nodes, so the table of the flipped grid holds bitwise
+    the same times and weights in reverse order: it undoes this one sub-step by sub-step."""
+    grid = torch.as_tensor(grid).detach().to("cpu", torch.float32).reshape(-1)
+    if grid.numel() < 2:
+        raise ValueError("time grid has fewer than two points")
+    sign = 1.0
+    if bool(grid[0] > grid[-1]):
+        sign = -1.0
+        grid = -grid
+    if not bool((grid[1:] > grid[:-1]).all()):
+        raise ValueError("leapfrog needs a strictly monotonic time grid")
+    n = int(grid.numel()) - 1
+    h = grid[1:] - grid[:-1]
+    rows = 2 * n + 1
+    t = torch.empty(rows, dtype=torch.float32)
+    w = torch.empty(rows, dtype=torch.float32)
+    t[0::2] = grid                                   # kicks at the nodes
+    t[1::2] = (grid[:-1] + grid[1:]) / 2             # drifts at the midpoints
+    w[1::2] = h
+    w[0] = h[0] / 2
+    w[2 * n] = h[n - 1] / 2
+    if n > 1:
+        w[2:2 * n:2] = (h[:-1] + h[1:]) / 2
+    flags = torch.full((rows,), FLAG_STEP_END, dtype=torch.int32)
+    flags[0::2] |= FLAG_NET_B
+    cout = torch.zeros(rows, 8, dtype=torch.float32)
+    cout[:, 0] = w
+    return EvalPlan(t_eval=sign * t, sign=sign, slot=torch.zeros(rows, dtype=torch.int32), flags=flags,
+                    cin=torch.zeros(rows, 8, dtype=torch.float32), cout=cout, n_steps=n)
 
 
 def build_table(plan: EvalPlan, a: torch.Tensor, b: torch.Tensor, c1: torch.Tensor, width: int,

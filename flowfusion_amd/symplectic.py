@@ -9,7 +9,11 @@ packer (``ff_mlp_pair_wpack``).  ``state_dict`` keys match the reference: ``shif
 ``conditional_scale`` (buffers, any of them may be None), ``model.W``, ``model.mlp_{q,p}_dynamics.{0,2,..}.*``.
 
 Routes (odeint.py): ``sample`` is torchdiffeq-style fixed-grid Euler on the reference's ``linspace(1, 0, num_steps + 1)``
-grid (one fused launch); ``log_prob`` is adaptive dopri5 on the device controller.  Networks outside the compiled pair
+grid (one fused launch); ``log_prob`` is adaptive dopri5 on the device controller.  ``sample_leapfrog`` / ``log_prob_leapfrog`` (extensions;
+``method="leapfrog"`` of ``_sample_from`` / ``_log_prob_from`` / ``_integrate``) integrate the same grid with
+kick-drift-kick leapfrog on the row-select kernel: every sub-step moves one half of the state under the network that reads
+the other half, so the discrete map preserves volume and ``log_prob_leapfrog(x, num_steps=n)`` -- the flipped grid, one
+launch, no step controller -- is the exact density of what ``sample_leapfrog(shape, num_steps=n)`` applies.  Networks outside the compiled pair
 shapes, non-SiLU activations and any other ``model`` with the same ``forward(t, state, conditional)`` are evaluated by
 torch with the stepping in the library (generic.py; ``FusedEnvelopeWarning`` for the first two).  GPU only: CPU tensors
 raise.  The reference draws a tqdm progress bar in ``sample``; this module does not.
@@ -99,32 +103,82 @@ class SymplecticFlowModel(nn.Module):
         p0 = torch.randn_like(x)
         return self._log_prob_from(x, p0, conditional, atol, rtol)
 
+    # -- extensions: kick-drift-kick leapfrog.  Methods of their own: the signatures of ``sample`` / ``log_prob`` are the
+    # reference's, and the golden fixtures pin them ------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample_leapfrog(self, shape, conditional=None, num_steps=1):
+        """``sample`` with ``num_steps`` leapfrog steps instead of Euler steps: the same prior draw, the same grid
+        ``linspace(1, 0, num_steps + 1)``, the same return value; second order, volume-preserving and exactly invertible
+        (``log_prob_leapfrog`` with the same ``num_steps`` is the density of this map)."""
+        device = next(self.model.parameters()).device
+        x = torch.randn(shape[0], shape[1] * 2, device=device)
+        return self._sample_from(x, conditional, num_steps, method="leapfrog")
+
+    @torch.no_grad()
+    def log_prob_leapfrog(self, x, conditional=None, num_steps=None):
+        """``log_prob`` with z1 the leapfrog solution on ``linspace(1, 0, num_steps + 1).flip(0)`` -- the exact inverse of
+        what ``sample_leapfrog(..., num_steps)`` applies -- in one launch: no tolerances, no step controller."""
+        p0 = torch.randn_like(x)
+        return self._log_prob_from(x, p0, conditional, method="leapfrog", num_steps=num_steps)
+
     # -- with the random draws supplied (tests feed the reference's draws) ----------------------------
     def _norm_cond(self, conditional):
         if conditional is None:
             return None
         return (conditional - self.conditional_shift) / self.conditional_scale
 
+    SAMPLE_METHODS = ("euler", "leapfrog")
+
     @torch.no_grad()
-    def _sample_from(self, x, conditional=None, num_steps=1):
+    def _integrate(self, z, time_steps, conditional_normalised=None, method="euler"):
+        """The whole state [B, 2D] after integrating ``z`` over the nodes ``time_steps`` (either direction) with the
+        fixed-grid ``method``: ``"euler"`` (torchdiffeq's, on the pair kernel) or ``"leapfrog"`` (kick-drift-kick on the
+        row-select kernel; odeint.solve_leapfrog)."""
+        if method not in self.SAMPLE_METHODS:
+            raise ValueError(f"method={method!r}: the fixed-grid methods of a symplectic flow are 'euler' and 'leapfrog'")
+        time_steps = time_steps.detach().to("cpu", torch.float32)
+        if method == "leapfrog":
+            return odeint.solve_leapfrog(self, z, time_steps, cond=conditional_normalised)
+        z, _ = odeint.solve(self, z, time_steps, "euler", None, MODE_STATE, None, None, cond=conditional_normalised)
+        return z
+
+    @torch.no_grad()
+    def _sample_from(self, x, conditional=None, num_steps=1, *, method="euler"):
         """``sample`` from the prior draw ``x`` [B, 2D]: the reference's grid ``linspace(1, 0, num_steps + 1)`` built on the
-        state's device, ``x + v(t_k, x) (t_{k+1} - t_k)`` per step -- torchdiffeq's fixed-grid Euler on that grid."""
+        state's device, ``x + v(t_k, x) (t_{k+1} - t_k)`` per step -- torchdiffeq's fixed-grid Euler on that grid -- or
+        leapfrog steps on the same grid."""
+        if method not in self.SAMPLE_METHODS:
+            raise ValueError(f"method={method!r}: sample takes 'euler' or 'leapfrog'")
         conditional = self._norm_cond(conditional)
         time_steps = torch.linspace(1.0, 0.0, num_steps + 1, device=x.device)
         if num_steps > 0:
-            x, _ = odeint.solve(self, x, time_steps.cpu(), "euler", None, MODE_STATE, None, None, cond=conditional)
+            x = self._integrate(x, time_steps.cpu(), conditional, method)
         q, _ = torch.chunk(x, 2, dim=-1)
         return q * self.scale + self.shift
 
     @torch.no_grad()
-    def _log_prob_from(self, x, p0, conditional=None, atol=1e-5, rtol=1e-5, method="dopri5", options=None):
+    def _log_prob_from(self, x, p0, conditional=None, atol=1e-5, rtol=1e-5, method="dopri5", options=None, *,
+                       num_steps=None):
         """``log_prob`` with the momentum draw ``p0`` supplied; ``method`` / ``options`` as torchdiffeq takes them (the
-        reference always runs its default, dopri5)."""
+        reference always runs its default, dopri5), or ``method="leapfrog"`` with ``num_steps``: the flipped grid of
+        ``sample``, no tolerances."""
+        if method == "leapfrog":
+            if num_steps is None or int(num_steps) < 1:
+                raise ValueError("method='leapfrog' needs num_steps >= 1 (the steps of the sample it inverts)")
+        elif num_steps is not None:
+            raise ValueError(f"num_steps belongs to method='leapfrog'; method={method!r} chooses its own steps")
+        elif method not in solvers.FIXED_METHODS and method not in solvers.ADAPTIVE_METHODS:
+            raise ValueError(f"method={method!r}: log_prob takes 'dopri5' (the default), 'leapfrog' with num_steps, or another "
+                             f"torchdiffeq method ({sorted(solvers.FIXED_METHODS)}, {solvers.ALL_ADAPTIVE})")
         q0 = (x - self.shift) / self.scale
         conditional = self._norm_cond(conditional)
         z0 = torch.cat([q0, p0], dim=-1)
-        t_span = torch.tensor([0.0, 1.0])
-        z1, _ = odeint.solve(self, z0, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional)
+        if method == "leapfrog":
+            grid = torch.linspace(1.0, 0.0, int(num_steps) + 1).flip(0)
+            z1 = self._integrate(z0, grid, conditional, "leapfrog")
+        else:
+            t_span = torch.tensor([0.0, 1.0])
+            z1, _ = odeint.solve(self, z0, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional)
         normal = torch.distributions.Normal(0, 1)
         log_p_z1 = normal.log_prob(z1).sum(dim=-1)
         log_p_p0 = normal.log_prob(p0).sum(dim=-1)
@@ -210,10 +264,46 @@ class SymplecticFlowModel(nn.Module):
         a, b, c1 = self._schedule(plan.t_eval)
         return solvers.build_table(plan, a, b, c1, self._net().width(mode))
 
+    def _leapfrog_table(self, grid):
+        """The select plan's table of ``solvers.plan_leapfrog(grid)``: every row carries the c1 of the network it runs."""
+        plan = solvers.plan_leapfrog(grid)
+        a, b, c1 = self._schedule(plan.t_eval)
+        H = self._net().width(MODE_STATE, select=True)
+        net_b = (plan.flags & solvers.FLAG_NET_B) != 0
+        return solvers.build_table(plan, a, b, torch.where(net_b[:, None], c1[:, H:], c1[:, :H]), H)
+
     def _schedule_key(self):
         """Besides the first layers: the embedding frequencies."""
         W = self.model.W
         return (W.data_ptr(), W._version)
+
+    def _module_half_rhs(self, cond):
+        """One half of the field for the generic leapfrog (generic.ModuleStepper.run_leapfrog): ``rhs(t, y, net_b)`` is
+        ``[0 | -mlp_p(q)]`` for a kick, ``[mlp_q(p) | 0]`` for a drift.  A SymplecticMLP evaluates only that network; any
+        other module is evaluated whole and the needed half taken."""
+        m = self.model
+
+        def rhs(t, y, net_b):
+            with torch.no_grad():
+                tb = t.reshape(()).to(y.dtype).expand(y.shape[0])
+                D = y.shape[1] // 2
+                out = torch.zeros_like(y)
+                if isinstance(m, SymplecticMLP):
+                    q, p = torch.chunk(y, 2, dim=-1)
+                    arg = tb[:, None] * m.W[None, :] * 2 * math.pi
+                    tail = [torch.sin(arg), torch.cos(arg)] if cond is None else [cond, torch.sin(arg), torch.cos(arg)]
+                    if net_b:
+                        out[:, D:] = -m.mlp_p_dynamics(torch.cat([q] + tail, dim=1))
+                    else:
+                        out[:, :D] = m.mlp_q_dynamics(torch.cat([p] + tail, dim=1))
+                else:
+                    v = m(tb, y, cond)
+                    if net_b:
+                        out[:, D:] = v[:, D:]
+                    else:
+                        out[:, :D] = v[:, :D]
+                return out
+        return rhs
 
     def _module_rhs(self, mode, cond, probe):
         """``self.model`` evaluated by torch for the generic route: ``t`` expanded to the batch as the reference's

@@ -103,6 +103,9 @@ extern "C" {
 /* evaluation-row flag bits (word 3 of the row header) */
 #define FF_ROW_STEP_END    1u   /* after this evaluation: y += sum_s cout[s] * k[s]        */
 #define FF_ROW_NOISE       2u   /* after the step update: y += gn * noise[noise_index]     */
+#define FF_ROW_NET_B       4u   /* select plans (ff_mlp_pair_select_plan) only: this row runs
+                                   net B (-mlp_p, state rows D..2D-1); without it, net A
+                                   (mlp_q, rows 0..D-1).  Other plans ignore the bit           */
 
 /*
  * Kernel plan for one network shape: which compiled instantiation serves it and how its
@@ -301,8 +304,25 @@ int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const f
                       const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
                       int x_col0, int c_col0, float* out);
 /* Words of first-layer bias per evaluation row (an etab row is FF_ROW_HDR + this many floats): plan.width, or
- * 2 * plan.width for a pair plan.  -1 for NULL. */
+ * 2 * plan.width for a pair plan (plan.width for a select plan).  -1 for NULL. */
 int ff_mlp_row_width(const ff_mlp_plan_t* plan);
+
+/* ---- row-select plans: one network per evaluation row (kick-drift-kick leapfrog of the symplectic flows) ------------
+ * The two networks of a pair plan, same shapes, same packed weights (ff_mlp_pair_wpack[_floats] take either plan), but an
+ * evaluation row runs ONE of them: net B if its flag word has FF_ROW_NET_B, net A otherwise.  The other half of the
+ * network output is exact zero, so with a = 0 a row's right-hand side and its FF_ROW_STEP_END update move one half of the
+ * state and leave the other bitwise untouched -- a shear.  A row carries only its own network's c1: the row stride is
+ * FF_ROW_HDR + plan.width (ff_mlp_row_width = plan.width).  Rows may select the networks in any order.
+ * ff_mlp_pair_select_plan has the envelope and the preference of ff_mlp_pair_plan; the plan's kernel_id is
+ * FF_PAIR_SELECT_KERNEL_BASE + the same index (kernel names mlp_pairsel_...; the select kernels are not entries of
+ * ff_kernel_count or ff_pair_kernel_count).  ff_plan_kernel_name, ff_mlp_row_width, ff_mlp_samples_per_workgroup,
+ * ff_mlp_launch_kind and ff_mlp_ode_launch accept it; ff_mlp_ode_adaptive refuses it (FF_ERR_BADARG).
+ * ff_mlp_ode_launch on a select plan: FF_MODE_STATE only; the affine maps, `gate`, `status` and noise rows (FF_ROW_NOISE,
+ * from a buffer or in-kernel: the code is the pair kernel's) work as for a pair plan; `k1_in`, `n_aux` > 0 and `jac_out`
+ * are refused with FF_ERR_BADARG.  The launcher's rule (twin for small batches and leftover tiles; FF_COOP /
+ * FF_TAIL_SPLIT) is the one of the pair plans, with the pair instances' constants. */
+#define FF_PAIR_SELECT_KERNEL_BASE 0x20000
+int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan_out);
 
 /* ---- streaming helpers beside the fused integrator (csrc/ff_aux.hip) --------------------------------- */
 
