@@ -147,8 +147,10 @@ def test_host_c1_is_the_first_layer_time_part(name):
         assert c1[:, i * H + h:(i + 1) * H].eq(0).all()
 
 
-def _emulate_pair(plan, wpack, table, x, cond):
-    """The pair kernel's evaluation loop in float64, each half decoded by tests/_emulator.decode_wpack."""
+def _emulate_pair(plan, wpack, table, x, cond, k1=None, n_aux=0):
+    """The pair kernel's evaluation loop in float64, each half decoded by tests/_emulator.decode_wpack.  ``k1``: stage slot
+    0 as the caller supplies it (k1_in).  ``n_aux`` = 1: the table's last two rows are the auxiliary rows of an adaptive
+    attempt, not evaluations, and the return value is (x, aux_0) with aux_0 = use_y x + sum_s cin[s] k[s] of the first."""
     words = _native.plan_words(plan)
     n = wpack.numel() // 2
     halves = [decode_wpack(words, wpack[:n]), decode_wpack(words, wpack[n:])]
@@ -157,8 +159,11 @@ def _emulate_pair(plan, wpack, table, x, cond):
     ints = table.view(torch.int32)
     B = x.shape[0]
     ks = torch.zeros(7, B, D2, dtype=torch.float64)
+    if k1 is not None:
+        ks[0] = k1.double()
     x = x.double()
-    for e in range(table.shape[0]):
+    n_evals = table.shape[0] - (2 if n_aux else 0)
+    for e in range(n_evals):
         y = x + sum(rows[e, 8 + s] * ks[s] for s in range(7))
         net = torch.zeros(B, D2, dtype=torch.float64)
         for i, (W1, hidden, Wo, bo, dx) in enumerate(halves):
@@ -175,6 +180,9 @@ def _emulate_pair(plan, wpack, table, x, cond):
         ks[int(ints[e, 4])] = rows[e, 0] * y + rows[e, 1] * net
         if int(ints[e, 3]) & 1:
             x = x + sum(rows[e, 16 + s] * ks[s] for s in range(7))
+    if n_aux:
+        use_y = float(int(ints[n_evals, 3]) & 1)
+        return x, use_y * x + sum(rows[n_evals, 8 + s] * ks[s] for s in range(7))
     return x
 
 
