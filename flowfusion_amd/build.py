@@ -223,64 +223,43 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     PAIR_INSTANCES = pair if pair is not None else globals()["PAIR_INSTANCES"]
     SELECT = select if select is not None else globals()["PAIR_SELECT_INSTANCES"]       # (a subset of PAIR_INSTANCES)
     GEN.mkdir(parents=True, exist_ok=True)
-    files = []
     tf = lambda t: "true" if t else "false"
+    # every launcher of the library: (name, header, kernel expression) -> a translation unit, a declaration, a table cell
+    units = []
     for tile, h, d, c, t, wps, ring, act in INSTANCES:
         name = _inst_name(tile, h, d, c, t, wps, ring, act)
-        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
-            name, "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, {wps}, {ring}, {act}>")))
+        units.append((name, "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, {wps}, {ring}, {act}>"))
         if _has_coop(h, act):
             # cooperative twin (small batches): same layout, one tile per workgroup; a translation unit of its own
             cwps = 2 if h <= 256 else 1
-            files.append(_write(GEN / f"{name}_coop.hip", _launcher_unit(
-                f"{name}_coop", "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, {cwps}, 4, {act}, true>")))
+            units.append((f"{name}_coop", "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, {cwps}, 4, {act}, true>"))
     for tile, h, d, c, t in WIDE_INSTANCES:
-        name = _wide_name(tile, h, d, c, t)
-        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
-            name, "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, 1, 4, 0, true, true>")))
+        units.append((_wide_name(tile, h, d, c, t), "ff_mlp_ode.hpp", f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, {tf(t)}, 1, 4, 0, true, true>"))
     for nh, t, parts, dt, width in SPLIT_INSTANCES:
-        name = _split_name(nh, t, parts, dt, width)
-        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
-            name, "ff_mlp_ode_split.hpp", f"split::mlp_ode_split_kernel<{nh}, {t}, {parts}, {dt}, {width}>")))
-    for tile, h, d, c, wps, ring in PAIR_INSTANCES:
-        name = _pair_name(tile, h, d, c, wps, ring)
-        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
-            name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}>")))
-        if _has_coop(h):
-            files.append(_write(GEN / f"{name}_coop.hip", _launcher_unit(
-                f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4, true>")))
-    for tile, h, d, c, wps, ring in SELECT:
-        name = _pairsel_name(tile, h, d, c, wps, ring)
-        files.append(_write(GEN / f"{name}.hip", _launcher_unit(
-            name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}, false, true>")))
-        if _has_coop(h):
-            files.append(_write(GEN / f"{name}_coop.hip", _launcher_unit(
-                f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4, true, true>")))
-    decls = "\n".join(
-        [f"int launch_{_inst_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES] +
-        [f"int launch_{_inst_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in INSTANCES
-         if _has_coop(i[1], i[7])] +
-        [f"int launch_{_wide_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in WIDE_INSTANCES] +
-        [f"int launch_{_split_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SPLIT_INSTANCES] +
-        [f"int launch_{_pair_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES] +
-        [f"int launch_{_pair_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in PAIR_INSTANCES
-         if _has_coop(i[1])] +
-        [f"int launch_{_pairsel_name(*i)}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SELECT] +
-        [f"int launch_{_pairsel_name(*i)}_coop(const KernelArgs*, unsigned, unsigned, hipStream_t);" for i in SELECT
-         if _has_coop(i[1])]
-    )
+        units.append((_split_name(nh, t, parts, dt, width), "ff_mlp_ode_split.hpp",
+                      f"split::mlp_ode_split_kernel<{nh}, {t}, {parts}, {dt}, {width}>"))
+    # the pair kernels, then their row-select variants (template arguments COOP, SELECT behind the pair kernel's own)
+    for namer, insts, one_wave, coop in ((_pair_name, PAIR_INSTANCES, "", ", true"), (_pairsel_name, SELECT, ", false, true", ", true, true")):
+        for tile, h, d, c, wps, ring in insts:
+            name = namer(tile, h, d, c, wps, ring)
+            units.append((name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}{one_wave}>"))
+            if _has_coop(h):
+                units.append((f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4{coop}>"))
+    files = [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr)) for name, header, expr in units]
+    decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
+    have = {name for name, _, _ in units}
+    fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
+    launchers = lambda name: f'{{{fn(name)}, {fn(name + "_coop")}, "{name if name in have else ""}"}}'
     pair_rows = ",\n".join(
-        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pair_name(*i)}, "{_pair_name(*i)}", '
-        + (f"launch_{_pair_name(*i)}_coop" if _has_coop(i[1]) else "nullptr") + ", "
-        + (f"launch_{_pairsel_name(*i)}" if i in SELECT else "nullptr") + ", "
-        + (f"launch_{_pairsel_name(*i)}_coop" if i in SELECT and _has_coop(i[1]) else "nullptr") + "}" for i in PAIR_INSTANCES
+        f"    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, {launchers(_pair_name(*i))}, {launchers(_pairsel_name(*i))}}}"
+        for i in PAIR_INSTANCES
     )
     split_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_split_name(*i)}, "{_split_name(*i)}"}}' for i in SPLIT_INSTANCES
     )
     rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, {i[7]}, launch_{_inst_name(*i)}, "{_inst_name(*i)}", '
-        + (f"launch_{_inst_name(*i)}_coop" if _has_coop(i[1], i[7]) else "nullptr") + f", {i[5]}}}"
+        + fn(_inst_name(*i) + "_coop") + f", {i[5]}}}"
         for i in INSTANCES
     )
     # wide catch-alls: no one-wavefront kernel (launch = nullptr), the cooperative launcher serves every batch size
@@ -292,7 +271,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     if not SPLIT_INSTANCES:          # (a test variant without the family: one inert row, count 0 -- no zero-length array)
         split_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
     if not PAIR_INSTANCES:           # (the test variants carry no pair kernels)
-        pair_rows = '    {0, 0, 0, 0, 0, nullptr, "", nullptr, nullptr, nullptr}'
+        pair_rows = '    {0, 0, 0, 0, 0, {nullptr, nullptr, ""}, {nullptr, nullptr, ""}}'
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 namespace ff {{

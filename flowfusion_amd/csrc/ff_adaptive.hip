@@ -339,6 +339,7 @@ static unsigned copy_grid(long long n)
 } // namespace ff
 
 extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream);
+namespace ff { bool plan_steps_adaptively(const ff_mlp_plan_t* plan); }      // ff_api.cpp: a valid plan, and not a select plan
 
 namespace {
 
@@ -442,7 +443,7 @@ extern "C" int ff_mlp_ode_adaptive(const ff_mlp_plan_t* plan, const ff_ode_args*
                                    void* hip_stream)
 {
     if (!plan || !base || !cfg || !b || n_attempts < 0) return FF_ERR_BADARG;
-    if (plan->kernel_id >= FF_PAIR_SELECT_KERNEL_BASE) return FF_ERR_BADARG;      // select plans: fixed tables only
+    if (!ff::plan_steps_adaptively(plan)) return FF_ERR_BADARG;      // select plans: fixed tables only
     if (cfg->n_stages < 2 || cfg->n_stages > FF_MAX_SLOTS || cfg->order < 1) return FF_ERR_BADARG;
     if (cfg->sched < FF_SCHED_FLOW || cfg->sched > FF_SCHED_FOURIER || !cfg->w0t || !cfg->b0) return FF_ERR_BADARG;
     if (cfg->h_real < 1 || cfg->h_real > ff_mlp_row_width(plan) || cfg->n_tcols < 1 || cfg->n_tcols > ff::kMaxTimeCols) return FF_ERR_UNSUPPORTED;

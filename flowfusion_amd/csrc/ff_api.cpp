@@ -43,6 +43,53 @@ static int tangents_of_mode(int mode, int dim, int tile, int* n_tangent, int* un
 
 static inline int split_parts(int precision) { return precision == FF_PREC_BF16X2 ? 2 : 3; }
 
+// the widest hidden layer, or -1 if a width is not positive
+static int widest(int n_hidden, const int* hidden_widths)
+{
+    int wmax = 0;
+    for (int i = 0; i < n_hidden; ++i) {
+        if (hidden_widths[i] < 1) return -1;
+        if (hidden_widths[i] > wmax) wmax = hidden_widths[i];
+    }
+    return wmax;
+}
+
+static int fill_plan(ff_mlp_plan_t* plan, int dim, int cond_dim, int n_hidden, int width, int dregs, int cregs, int kernel_id,
+                     int tile, int activation)
+{
+    memset(plan, 0, sizeof(*plan));
+    plan->dim = dim;
+    plan->cond_dim = cond_dim;
+    plan->n_hidden = n_hidden;
+    plan->width = width;
+    plan->dregs = dregs;
+    plan->cregs = cregs;
+    plan->kernel_id = kernel_id;
+    plan->tile = tile;
+    plan->activation = activation;
+    return FF_OK;
+}
+
+// The entry of an fp32 table (single-network or pair) that serves a network, or -1.  Preference among the entries that
+// fit (and that `also` accepts): narrowest width first (it dominates the FLOPs); at equal width the 16x16x4
+// two-waves-per-SIMD kernels (measured ~3% faster than 32x32x2 at width 256), then fewer first-layer k-steps.
+template <class Entry, class Also>
+static int best_entry(const Entry* table, int n, int dim, int cond_dim, int wmax, Also also)
+{
+    int best = -1;
+    for (int i = 0; i < n; ++i) {
+        const Entry& k = table[i];
+        const int need_d = ff::regs_for(k.tile, dim);
+        const int need_c = cond_dim > 0 ? ff::regs_for(k.tile, cond_dim) : 0;
+        if (k.H < wmax || k.dregs < need_d || k.cregs < need_c || !also(k)) continue;
+        if (best < 0) { best = i; continue; }
+        const Entry& b = table[best];
+        const int kc = (k.dregs + k.cregs) * (64 / k.tile), bc = (b.dregs + b.cregs) * (64 / b.tile);     // first-layer features covered
+        if (k.H < b.H || (k.H == b.H && (k.tile < b.tile || (k.tile == b.tile && kc < bc)))) best = i;
+    }
+    return best;
+}
+
 // FF_PREC_BF16X3 / FF_PREC_BF16X2: the split-precision family (ff_mlp_ode_split.hpp) -- SiLU, width <= 256, dim <= 16,
 // cond_dim <= 16, state-only or Hutchinson, the number of hidden layers compiled in
 static int plan_split(int dim, int cond_dim, int n_hidden, const int* hidden_widths, int mode, int activation,
@@ -53,11 +100,8 @@ static int plan_split(int dim, int cond_dim, int n_hidden, const int* hidden_wid
     if (activation < 0 || activation >= FF_ACT_COUNT) return FF_ERR_BADARG;
     if (activation != FF_ACT_SILU || dim > 32 || cond_dim > 16) return FF_ERR_UNSUPPORTED;
     const int need_dt = dim > 16 ? 2 : 1;              // 16-dimension tiles of the state
-    int wmax = 0;
-    for (int i = 0; i < n_hidden; ++i) {
-        if (hidden_widths[i] < 1) return FF_ERR_BADARG;
-        if (hidden_widths[i] > wmax) wmax = hidden_widths[i];
-    }
+    const int wmax = widest(n_hidden, hidden_widths);
+    if (wmax < 0) return FF_ERR_BADARG;
     if (wmax > ff::split::kWidth) return FF_ERR_UNSUPPORTED;
     const int need_t = mode == FF_MODE_STATE ? 0 : (mode == FF_MODE_HUTCH ? 1 : 2);
     int best = -1;                                     // the narrowest instantiation that holds the network
@@ -68,16 +112,10 @@ static int plan_split(int dim, int cond_dim, int n_hidden, const int* hidden_wid
             best = i;
     }
     if (best < 0) return FF_ERR_UNSUPPORTED;
-    memset(plan, 0, sizeof(*plan));
-    plan->dim = dim;
-    plan->cond_dim = cond_dim;
-    plan->n_hidden = n_hidden;
-    plan->width = ff::g_split_kernels[best].width;
-    plan->dregs = 8 * need_dt;                         // 4 dimensions x 2 column blocks per lane and 16-dimension tile
-    plan->cregs = cond_dim > 0 ? 8 : 0;
-    plan->kernel_id = best;
-    plan->tile = need_t == 2 ? 16 : 32;                // exact trace: a sample and its unit tangents share a column block of 16
-    plan->activation = FF_ACT_SILU;
+    // 4 dimensions x 2 column blocks per lane and 16-dimension tile; exact trace: a sample and its unit tangents share a
+    // column block of 16
+    fill_plan(plan, dim, cond_dim, n_hidden, ff::g_split_kernels[best].width, 8 * need_dt, cond_dim > 0 ? 8 : 0, best,
+              need_t == 2 ? 16 : 32, FF_ACT_SILU);
     plan->precision = precision;
     return FF_OK;
 }
@@ -102,65 +140,104 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
     if (!plan || !hidden_widths || dim < 1 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
     if (activation < 0 || activation >= FF_ACT_COUNT) return FF_ERR_BADARG;
     if (mode != FF_MODE_STATE && mode != FF_MODE_HUTCH && mode != FF_MODE_EXACT) return FF_ERR_BADARG;
-    int wmax = 0;
-    for (int i = 0; i < n_hidden; ++i) {
-        if (hidden_widths[i] < 1) return FF_ERR_BADARG;
-        if (hidden_widths[i] > wmax) wmax = hidden_widths[i];
-    }
+    const int wmax = widest(n_hidden, hidden_widths);
+    if (wmax < 0) return FF_ERR_BADARG;
     const int need_t = mode != FF_MODE_STATE;
-    // Preference among kernels that fit: narrowest width first (it dominates the FLOPs); at equal
-    // width the 16x16x4 two-waves-per-SIMD kernels (measured ~3% faster than 32x32x2 at width 256),
-    // then fewer first-layer k-steps.
-    int best = -1;
-    for (int i = 0; i < ff::g_n_kernels; ++i) {
-        const ff::KernelEntry& k = ff::g_kernels[i];
-        const int need_d = ff::regs_for(k.tile, dim);
-        const int need_c = cond_dim > 0 ? ff::regs_for(k.tile, cond_dim) : 0;
-        if (k.H < wmax || k.dregs < need_d || k.cregs < need_c || k.tangents != need_t ||
-            !(k.act == activation || (k.act == 9 && activation != FF_ACT_SILU))) continue;
-        if (best < 0) { best = i; continue; }
-        const ff::KernelEntry& b = ff::g_kernels[best];
-        const int kc = k.dregs * (64 / k.tile) + k.cregs * (64 / k.tile);     // first-layer features covered
-        const int bc = b.dregs * (64 / b.tile) + b.cregs * (64 / b.tile);
-        if (k.H < b.H || (k.H == b.H && (k.tile < b.tile || (k.tile == b.tile && kc < bc)))) best = i;
-    }
+    const int best = best_entry(ff::g_kernels, ff::g_n_kernels, dim, cond_dim, wmax, [&](const ff::KernelEntry& k) {
+        return k.tangents == need_t && (k.act == activation || (k.act == 9 && activation != FF_ACT_SILU));
+    });
     if (best < 0) return FF_ERR_UNSUPPORTED;
-    memset(plan, 0, sizeof(*plan));
-    plan->dim = dim;
-    plan->cond_dim = cond_dim;
-    plan->n_hidden = n_hidden;
-    plan->width = ff::g_kernels[best].H;
-    plan->dregs = ff::g_kernels[best].dregs;
-    plan->cregs = ff::g_kernels[best].cregs;
-    plan->kernel_id = best;
-    plan->tile = ff::g_kernels[best].tile;
-    plan->activation = activation;
+    const ff::KernelEntry& k = ff::g_kernels[best];
+    fill_plan(plan, dim, cond_dim, n_hidden, k.H, k.dregs, k.cregs, best, k.tile, activation);
     if (act_param) { plan->act_param[0] = act_param[0]; plan->act_param[1] = act_param[1]; }
     return FF_OK;
 }
 
-static bool plan_ok_split(const ff_mlp_plan_t* p)
+// ---- what a plan launches, as data ------------------------------------------------------------------------------------
+// describe() validates a plan once and says everything the code below needs to know about its family: the launcher,
+// ff_mlp_launch_kind and the small queries read the description and never ask which family they serve.
+enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect };
+
+struct LaunchDesc {
+    PlanFamily family;
+    const char* name;          // of the kernel (the one-wavefront kernel's where there are two)
+    ff::LaunchFn one_wave;     // a wavefront per tile, four tiles per workgroup; NULL: the wide catch-all, cooperative always
+    ff::LaunchFn coop;         // the cooperative twin, a tile per workgroup; NULL: none
+    int wps;                   // wavefronts per SIMD of the one-wavefront kernel: 1024 * wps tiles run at once
+    double c0, per_round, least;   // the twin's line (choose_launch): max(least, c0 + tiles / (per_round * chip))
+    int tangents;              // != 0: the kernel carries tangent columns and serves FF_MODE_HUTCH / FF_MODE_EXACT, not FF_MODE_STATE
+    bool state_only;           // a family without a divergence: FF_MODE_STATE without jac_out is all it takes, and probe, dlogp_*,
+                               // kl1_in and aux_lp_out do not reach the kernel
+    int nets;                  // networks in the packed weights (wpack_floats = nets x the layout's)
+    int row_nets;              // c1 vectors in an evaluation row (etab_stride = FF_ROW_HDR + row_nets x width)
+    int exchange;              // exchange buffers of the cooperative kernel in LDS
+    // what the family's argument check refuses (kept per family as found; CHANGELOG.md lists the asymmetries)
+    int max_aux;               // largest n_aux
+    bool takes_k1;             // k1_in
+    bool checks_noise_stride;  // noise_stride >= batch * dim where `noise` is set
+    bool empty_batch_first;    // an empty batch is FF_OK before n_aux, k1_in, noise_stride and jac_out are looked at
+    const ff::SplitKernelEntry* split;      // kSplit: the entry (that family keeps its own launch geometry, launch_split)
+};
+
+static bool shape_ok(const ff_mlp_plan_t* p, int tile, int H, int dregs, int cregs)
 {
-    if (!p || (p->precision != FF_PREC_BF16X3 && p->precision != FF_PREC_BF16X2) || p->kernel_id < 0 ||
-        p->kernel_id >= ff::g_n_split_kernels)
-        return false;
-    const ff::SplitKernelEntry& k = ff::g_split_kernels[p->kernel_id];
-    return k.parts == split_parts(p->precision) && p->width == k.width && p->tile == (k.tangents == 2 ? 16 : 32) &&
-           p->dregs == 8 * k.dt &&
-           p->cregs == (p->cond_dim > 0 ? 8 : 0) &&
-           p->n_hidden == k.n_hidden && p->activation == FF_ACT_SILU && p->dim >= 1 && p->dim <= 16 * k.dt &&
-           p->cond_dim >= 0 && p->cond_dim <= 16;
+    const int per_reg = 64 / tile;
+    return H == p->width && dregs == p->dregs && cregs == p->cregs && tile == p->tile && p->n_hidden >= 1 && p->dim >= 1 &&
+           p->dim <= per_reg * p->dregs && p->cond_dim >= 0 && p->cond_dim <= per_reg * p->cregs;
 }
 
-static bool plan_ok(const ff_mlp_plan_t* p)
+// the twin's line of a single-network kernel (the comment above choose_launch)
+static void twin_line(LaunchDesc* d, int wps)
 {
-    if (!p || p->precision != FF_PREC_F32) return false;
-    if (p->kernel_id < 0 || p->kernel_id >= ff::g_n_kernels) return false;
-    const ff::KernelEntry& k = ff::g_kernels[p->kernel_id];
-    const int per_reg = 64 / k.tile;
-    return k.H == p->width && k.dregs == p->dregs && k.cregs == p->cregs && k.tile == p->tile && p->n_hidden >= 1 &&
-           p->activation >= 0 && p->activation < FF_ACT_COUNT && (p->activation == k.act || (k.act == 9 && p->activation != FF_ACT_SILU)) &&
-           p->dim >= 1 && p->dim <= per_reg * p->dregs && p->cond_dim >= 0 && p->cond_dim <= per_reg * p->cregs;
+    d->wps = wps;
+    d->least = wps >= 3 ? 0.22 : (wps == 2 ? 0.30 : 0.35);
+    d->c0 = wps == 1 ? 0.20 : 0.10;
+    d->per_round = 0.95;
+}
+
+// false: not a plan of this library.  Kernel ids: [0, g_n_kernels) fp32 or, by the plan's precision, [0, g_n_split_kernels);
+// FF_PAIR_KERNEL_BASE + i a pair plan, FF_PAIR_SELECT_KERNEL_BASE + i a select plan, the same index into the pair table.
+static bool describe(const ff_mlp_plan_t* p, LaunchDesc* d)
+{
+    memset(d, 0, sizeof(*d));
+    if (!p || p->kernel_id < 0) return false;
+    if (p->precision == FF_PREC_BF16X3 || p->precision == FF_PREC_BF16X2) {
+        if (p->kernel_id >= ff::g_n_split_kernels) return false;
+        const ff::SplitKernelEntry& k = ff::g_split_kernels[p->kernel_id];
+        if (!(k.parts == split_parts(p->precision) && p->width == k.width && p->tile == (k.tangents == 2 ? 16 : 32) &&
+              p->dregs == 8 * k.dt && p->cregs == (p->cond_dim > 0 ? 8 : 0) && p->n_hidden == k.n_hidden &&
+              p->activation == FF_ACT_SILU && p->dim >= 1 && p->dim <= 16 * k.dt && p->cond_dim >= 0 && p->cond_dim <= 16))
+            return false;
+        d->family = kSplit; d->name = k.name; d->one_wave = k.launch; d->row_nets = 1; d->split = &k;
+        return true;
+    }
+    if (p->precision != FF_PREC_F32) return false;
+    if (p->kernel_id < ff::g_n_kernels) {
+        const ff::KernelEntry& k = ff::g_kernels[p->kernel_id];
+        if (!shape_ok(p, k.tile, k.H, k.dregs, k.cregs) || p->activation < 0 || p->activation >= FF_ACT_COUNT ||
+            !(p->activation == k.act || (k.act == 9 && p->activation != FF_ACT_SILU)))
+            return false;
+        d->family = kF32; d->name = k.name; d->one_wave = k.launch; d->coop = k.launch_coop;
+        twin_line(d, k.wps > 0 ? k.wps : 1);
+        d->tangents = k.tangents; d->nets = 1; d->row_nets = 1;
+        d->exchange = k.launch ? 2 : 1;
+        d->max_aux = FF_MAX_AUX; d->takes_k1 = true; d->empty_batch_first = true;
+        return true;
+    }
+    const bool select = p->kernel_id >= FF_PAIR_SELECT_KERNEL_BASE;
+    const int index = p->kernel_id - (select ? FF_PAIR_SELECT_KERNEL_BASE : FF_PAIR_KERNEL_BASE);
+    if (index < 0 || index >= ff::g_n_pair_kernels) return false;
+    const ff::PairKernelEntry& k = ff::g_pair_kernels[index];
+    const ff::Launchers& l = select ? k.select : k.pair;
+    if (!l.one_wave || !shape_ok(p, k.tile, k.H, k.dregs, k.cregs) || p->activation != FF_ACT_SILU || p->dim % 2 != 0) return false;
+    d->family = select ? kSelect : kPair; d->name = l.name; d->one_wave = l.one_wave; d->coop = l.coop;
+    twin_line(d, k.wps);
+    if (k.wps >= 3) { d->c0 = 0.03; d->per_round = 0.85; }      // the 128-wide pair and select twins' own line
+    d->state_only = true; d->nets = 2; d->exchange = 2;
+    d->row_nets = select ? 1 : 2;                                // a select row carries the c1 of the one network it runs
+    d->max_aux = select ? 0 : FF_MAX_AUX; d->takes_k1 = !select; // no first stage from the caller, no auxiliary outputs
+    d->checks_noise_stride = true;
+    return true;
 }
 
 static ff::Layout plan_layout(const ff_mlp_plan_t* p)
@@ -168,61 +245,33 @@ static ff::Layout plan_layout(const ff_mlp_plan_t* p)
     return ff::make_layout(p->tile, p->width, p->dregs, p->cregs, p->n_hidden);
 }
 
-// a pair plan (ff_mlp_pair_plan): kernel ids FF_PAIR_KERNEL_BASE + i, a range no other plan uses; a select plan
-// (ff_mlp_pair_select_plan): FF_PAIR_SELECT_KERNEL_BASE + i, the same index into the same table
-static bool plan_ok_pair_at(const ff_mlp_plan_t* p, int base)
-{
-    if (!p || p->precision != FF_PREC_F32 || p->kernel_id < base || p->kernel_id >= base + ff::g_n_pair_kernels)
-        return false;
-    const ff::PairKernelEntry& k = ff::g_pair_kernels[p->kernel_id - base];
-    const int per_reg = 64 / k.tile;
-    return k.H == p->width && k.dregs == p->dregs && k.cregs == p->cregs && k.tile == p->tile && p->n_hidden >= 1 &&
-           p->activation == FF_ACT_SILU && p->dim >= 2 && p->dim % 2 == 0 && p->dim <= per_reg * p->dregs &&
-           p->cond_dim >= 0 && p->cond_dim <= per_reg * p->cregs;
-}
-
-static bool plan_ok_pair(const ff_mlp_plan_t* p) { return plan_ok_pair_at(p, FF_PAIR_KERNEL_BASE); }
-
-static bool plan_ok_select(const ff_mlp_plan_t* p)
-{
-    return plan_ok_pair_at(p, FF_PAIR_SELECT_KERNEL_BASE) &&
-           ff::g_pair_kernels[p->kernel_id - FF_PAIR_SELECT_KERNEL_BASE].launch_select != nullptr;
-}
-
-// "mlp_pair_<shape>" -> "mlp_pairsel_<shape>": the select kernels are named after the pair kernel of their shape
-static const char* select_kernel_name(int index)
-{
-    static char names[8][64];
-    if (index < 0 || index >= 8) return NULL;
-    if (!names[index][0]) {
-        const char* pn = ff::g_pair_kernels[index].name;
-        char buf[64];
-        snprintf(buf, sizeof(buf), "mlp_pairsel_%s", strncmp(pn, "mlp_pair_", 9) == 0 ? pn + 9 : pn);
-        memcpy(names[index], buf, sizeof(buf));
-    }
-    return names[index];
-}
-
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
 {
-    if (plan_ok_split(plan)) return ff::g_split_kernels[plan->kernel_id].name;
-    if (plan_ok(plan)) return ff::g_kernels[plan->kernel_id].name;
-    if (plan_ok_pair(plan)) return ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE].name;
-    if (plan_ok_select(plan)) return select_kernel_name(plan->kernel_id - FF_PAIR_SELECT_KERNEL_BASE);
-    return NULL;
+    LaunchDesc d;
+    return describe(plan, &d) ? d.name : NULL;
+}
+
+// ff_adaptive.hip: plans ff_mlp_ode_adaptive takes -- every valid plan but the select plans (fixed tables only)
+namespace ff {
+bool plan_steps_adaptively(const ff_mlp_plan_t* plan)
+{
+    LaunchDesc d;
+    return describe(plan, &d) && d.family != kSelect;
+}
 }
 
 extern "C" int ff_pair_kernel_count(void) { return ff::g_n_pair_kernels; }
 
 extern "C" const char* ff_pair_kernel_name(int index)
 {
-    return index >= 0 && index < ff::g_n_pair_kernels ? ff::g_pair_kernels[index].name : NULL;
+    return index >= 0 && index < ff::g_n_pair_kernels ? ff::g_pair_kernels[index].pair.name : NULL;
 }
 
 extern "C" int ff_mlp_row_width(const ff_mlp_plan_t* plan)
 {
     if (!plan) return -1;
-    return plan_ok_pair(plan) ? 2 * plan->width : plan->width;      // (a select row carries one network's c1)
+    LaunchDesc d;
+    return describe(plan, &d) ? d.row_nets * plan->width : plan->width;
 }
 
 extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
@@ -230,7 +279,7 @@ extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, cons
     const int rc = ff_mlp_pair_plan(dim, cond_dim, n_hidden, hidden_widths, plan);      // one envelope, one preference
     if (rc != FF_OK) return rc;
     const int index = plan->kernel_id - FF_PAIR_KERNEL_BASE;
-    if (ff::g_pair_kernels[index].launch_select == nullptr) { memset(plan, 0, sizeof(*plan)); return FF_ERR_UNSUPPORTED; }
+    if (ff::g_pair_kernels[index].select.one_wave == nullptr) { memset(plan, 0, sizeof(*plan)); return FF_ERR_UNSUPPORTED; }
     plan->kernel_id = FF_PAIR_SELECT_KERNEL_BASE + index;
     return FF_OK;
 }
@@ -238,50 +287,26 @@ extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, cons
 extern "C" int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
 {
     if (!plan || !hidden_widths || dim < 2 || dim % 2 != 0 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
-    int wmax = 0;
-    for (int i = 0; i < n_hidden; ++i) {
-        if (hidden_widths[i] < 1) return FF_ERR_BADARG;
-        if (hidden_widths[i] > wmax) wmax = hidden_widths[i];
-    }
-    // the preference of ff_mlp_plan_prec: narrowest width, then the 16-column tile, then fewer first-layer k-steps
-    int best = -1;
-    for (int i = 0; i < ff::g_n_pair_kernels; ++i) {
-        const ff::PairKernelEntry& k = ff::g_pair_kernels[i];
-        const int need_d = ff::regs_for(k.tile, dim);
-        const int need_c = cond_dim > 0 ? ff::regs_for(k.tile, cond_dim) : 0;
-        if (k.H < wmax || k.dregs < need_d || k.cregs < need_c) continue;
-        if (best < 0) { best = i; continue; }
-        const ff::PairKernelEntry& b = ff::g_pair_kernels[best];
-        const int kc = (k.dregs + k.cregs) * (64 / k.tile), bc = (b.dregs + b.cregs) * (64 / b.tile);
-        if (k.H < b.H || (k.H == b.H && (k.tile < b.tile || (k.tile == b.tile && kc < bc)))) best = i;
-    }
+    const int wmax = widest(n_hidden, hidden_widths);
+    if (wmax < 0) return FF_ERR_BADARG;
+    const int best = best_entry(ff::g_pair_kernels, ff::g_n_pair_kernels, dim, cond_dim, wmax, [](const ff::PairKernelEntry&) { return true; });
     if (best < 0) return FF_ERR_UNSUPPORTED;
-    memset(plan, 0, sizeof(*plan));
-    plan->dim = dim;
-    plan->cond_dim = cond_dim;
-    plan->n_hidden = n_hidden;
-    plan->width = ff::g_pair_kernels[best].H;
-    plan->dregs = ff::g_pair_kernels[best].dregs;
-    plan->cregs = ff::g_pair_kernels[best].cregs;
-    plan->kernel_id = FF_PAIR_KERNEL_BASE + best;
-    plan->tile = ff::g_pair_kernels[best].tile;
-    plan->activation = FF_ACT_SILU;
-    return FF_OK;
+    const ff::PairKernelEntry& k = ff::g_pair_kernels[best];
+    return fill_plan(plan, dim, cond_dim, n_hidden, k.H, k.dregs, k.cregs, FF_PAIR_KERNEL_BASE + best, k.tile, FF_ACT_SILU);
 }
 
 extern "C" size_t ff_mlp_pair_wpack_floats(const ff_mlp_plan_t* plan)
 {
-    if (!plan_ok_pair(plan) && !plan_ok_select(plan)) return 0;
-    return 2 * plan_layout(plan).total_floats;
+    LaunchDesc d;
+    return describe(plan, &d) && d.nets == 2 ? 2 * plan_layout(plan).total_floats : 0;
 }
 
 extern "C" size_t ff_mlp_wpack_floats(const ff_mlp_plan_t* plan)
 {
-    if (plan_ok_split(plan)) {
-        return ff::split::total_words(plan->n_hidden, split_parts(plan->precision), plan->dregs / 8, plan->width);
-    }
-    if (!plan_ok(plan)) return 0;
-    return plan_layout(plan).total_floats;
+    LaunchDesc d;
+    if (!describe(plan, &d)) return 0;
+    if (d.family == kSplit) return ff::split::total_words(plan->n_hidden, split_parts(plan->precision), plan->dregs / 8, plan->width);
+    return d.nets == 1 ? plan_layout(plan).total_floats : 0;
 }
 
 // three-way bf16 split by truncation: v = hi + mid + lo exactly (8 + 8 + 8 significand bits)
@@ -383,7 +408,9 @@ static int wpack_f32(const ff::Layout& L, int D, int C, const float* const* W, c
 extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, const float* const* b,
                             const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out)
 {
-    if (plan_ok_split(plan)) {
+    LaunchDesc d;
+    if (!describe(plan, &d) || d.nets == 2) return FF_ERR_BADARG;
+    if (d.family == kSplit) {
         if (!W || !b || !hidden_widths || !out) return FF_ERR_BADARG;
         const int D = plan->dim, C = plan->cond_dim, NH = plan->n_hidden;
         if (x_col0 < 0 || x_col0 + D > in_features0) return FF_ERR_BADARG;
@@ -394,7 +421,7 @@ extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, co
             if (!W[i] || (i > 0 && !b[i])) return FF_ERR_BADARG;
         return wpack_split(plan, W, b, hidden_widths, in_features0, x_col0, c_col0, out);
     }
-    if (!plan_ok(plan) || !W || !b || !hidden_widths || !out) return FF_ERR_BADARG;
+    if (!W || !b || !hidden_widths || !out) return FF_ERR_BADARG;
     const int D = plan->dim, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
     if (x_col0 < 0 || x_col0 + D > in_features0) return FF_ERR_BADARG;
     if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
@@ -468,7 +495,8 @@ extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* 
                                  const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
                                  int x_col0, int c_col0, float* out)
 {
-    if ((!plan_ok_pair(plan) && !plan_ok_select(plan)) || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
+    LaunchDesc d;
+    if (!describe(plan, &d) || d.nets != 2 || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
     const int D2 = plan->dim, Dh = D2 / 2, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
     if (x_col0 < 0 || x_col0 + Dh > in_features0) return FF_ERR_BADARG;
     if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
@@ -512,28 +540,52 @@ extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* 
 
 extern "C" int ff_mlp_samples_per_workgroup(const ff_mlp_plan_t* plan, int mode)
 {
-    if (plan_ok_pair(plan) || plan_ok_select(plan)) return mode == FF_MODE_STATE ? 4 * plan->tile : FF_ERR_BADARG;
-    if (plan_ok_split(plan)) {
-        const int kt = ff::g_split_kernels[plan->kernel_id].tangents;
+    LaunchDesc d;
+    if (!describe(plan, &d)) return FF_ERR_BADARG;
+    if (d.family == kSplit) {
+        const int kt = d.split->tangents;
         if (mode == FF_MODE_STATE && kt == 0) return 128;
         if (mode == FF_MODE_HUTCH && kt == 1) return 64;
         if (mode == FF_MODE_EXACT && kt == 2) return 8 * (16 / (1 + (plan->dim < 15 ? plan->dim : 15)));
         return FF_ERR_BADARG;
     }
-    if (!plan_ok(plan)) return FF_ERR_BADARG;
+    if (d.state_only && mode != FF_MODE_STATE) return FF_ERR_BADARG;
     int nt, unit;
     int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
     if (rc) return rc;
-    const bool wide = ff::g_kernels[plan->kernel_id].launch == nullptr;      // a tile per workgroup
-    return (wide ? 1 : 4) * (plan->tile / (1 + nt));
+    return (d.one_wave ? 4 : 1) * (plan->tile / (1 + nt));      // (the wide catch-all: a tile per workgroup)
+}
+
+// The kernels' argument block from the caller's: the one place that knows the field list.  `lp`: the divergence-side
+// pointers go along (LaunchDesc::state_only families leave them out).  etab_stride and wpack_floats are the caller's.
+static ff::KernelArgs fill_args(const ff_mlp_plan_t* plan, const ff_ode_args* a, bool lp, int n_tangent, int unit_tangents,
+                                int tangent_first)
+{
+    ff::KernelArgs ka;
+    memset(&ka, 0, sizeof(ka));
+    ka.x_in = a->x_in; ka.x_out = a->x_out; ka.cond = a->cond; ka.noise = a->noise; ka.wpack = a->wpack; ka.etab = a->etab;
+    ka.in_shift = a->in_shift; ka.in_scale = a->in_scale; ka.out_scale = a->out_scale; ka.out_shift = a->out_shift;
+    ka.status = a->status; ka.gate = a->gate; ka.batch = a->batch; ka.noise_stride = a->noise_stride;
+    ka.n_evals = a->n_evals; ka.n_hidden = plan->n_hidden; ka.dim = plan->dim; ka.cond_dim = plan->cond_dim;
+    ka.n_tangent = n_tangent; ka.unit_tangents = unit_tangents; ka.tangent_first = tangent_first;
+    ka.k1_in = a->k1_in; ka.n_aux = a->n_aux;
+    for (int j = 0; j < FF_MAX_AUX; ++j) ka.aux_out[j] = a->aux_out[j];
+    if (lp) {
+        ka.probe = a->probe; ka.dlogp_out = a->dlogp_out; ka.dlogp_in = a->dlogp_in; ka.kl1_in = a->kl1_in;
+        for (int j = 0; j < FF_MAX_AUX; ++j) ka.aux_lp_out[j] = a->aux_lp_out[j];
+    }
+    ka.rng_seed = a->rng_seed; ka.rng_sample_offset = a->rng_sample_offset; ka.rng_noise_base = a->rng_noise_base;
+    ka.jac_out = a->jac_out;
+    ka.jac_all = a->jac_out && a->jac_all ? 1 : 0;
+    ka.act_kind = plan->activation; ka.act_p0 = plan->act_param[0]; ka.act_p1 = plan->act_param[1];
+    return ka;
 }
 
 // FF_PREC_BF16X3 / BF16X2 launch: state-only (Euler-Maruyama noise rows included) / Hutchinson integration of a table
-static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
+static int launch_split(const ff_mlp_plan_t* plan, const ff::SplitKernelEntry& k, const ff_ode_args* a, void* hip_stream)
 {
     if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
-    const ff::SplitKernelEntry& k = ff::g_split_kernels[plan->kernel_id];
     if (a->mode != FF_MODE_STATE && a->mode != FF_MODE_HUTCH && a->mode != FF_MODE_EXACT) return FF_ERR_BADARG;
     if (k.tangents != (a->mode == FF_MODE_STATE ? 0 : (a->mode == FF_MODE_HUTCH ? 1 : 2))) return FF_ERR_BADARG;
     if (a->mode == FF_MODE_HUTCH && !a->probe) return FF_ERR_BADARG;
@@ -555,19 +607,7 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->stage_slots > ff::split::slots_on_chip(k.dt)) return FF_ERR_UNSUPPORTED;
     if (a->batch == 0) return FF_OK;
-    ff::KernelArgs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.gate = a->gate;
-    ka.x_in = a->x_in; ka.x_out = a->x_out; ka.cond = a->cond; ka.probe = a->probe;
-    ka.dlogp_out = a->dlogp_out; ka.wpack = a->wpack; ka.etab = a->etab;
-    ka.in_shift = a->in_shift; ka.in_scale = a->in_scale; ka.out_scale = a->out_scale; ka.out_shift = a->out_shift;
-    ka.status = a->status; ka.batch = a->batch; ka.dlogp_in = a->dlogp_in;
-    ka.k1_in = a->k1_in; ka.kl1_in = a->kl1_in; ka.n_aux = a->n_aux;
-    ka.noise = a->noise; ka.noise_stride = a->noise_stride;
-    ka.rng_seed = a->rng_seed; ka.rng_sample_offset = a->rng_sample_offset; ka.rng_noise_base = a->rng_noise_base;
-    for (int j = 0; j < FF_MAX_AUX; ++j) { ka.aux_out[j] = a->aux_out[j]; ka.aux_lp_out[j] = a->aux_lp_out[j]; }
-    ka.n_evals = a->n_evals; ka.n_hidden = plan->n_hidden; ka.dim = plan->dim; ka.cond_dim = plan->cond_dim;
-    ka.n_tangent = nt; ka.unit_tangents = a->mode == FF_MODE_EXACT ? 1 : 0; ka.tangent_first = tfirst;
+    ff::KernelArgs ka = fill_args(plan, a, true, nt, a->mode == FF_MODE_EXACT ? 1 : 0, tfirst);
     ka.etab_stride = FF_ROW_HDR + plan->width;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)ff::split::total_words(k.n_hidden, k.parts, k.dt, k.width);
@@ -592,7 +632,9 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* h
 //   twin, n tiles:                  max(least, c0 + n / (0.95 chip)),  chip = 1024 wps tiles in flight,
 //                                   c0 = 0.10 (0.20 at one wavefront per SIMD), least = 0.22 / 0.30 / 0.35 for wps = 3 / 2 / 1
 // The twin serves whatever it is faster at.
-// Two-network kernels (`pair`; profiles/pair_twin.txt, the same units): at two wavefronts per SIMD (width 256) the constants
+// Two-network kernels (profiles/pair_twin.txt; the same rule in the same units -- an evaluation is two networks on the
+// one-wavefront kernel and on the twin alike -- with a line of their own where the measurement asked for one, which
+// describe() puts into their descriptions): at two wavefronts per SIMD (width 256) the constants
 // above pick the faster kernel at every measured tile count and stay.  At three (width 128) the twin's line is steeper and
 // starts lower -- c0 = 0.03, 0.85 of a chip's worth per round: with 0.10 / 0.95 the rule took the one-wavefront kernel at
 // 768 tiles (5 % slower there) and the twin at 2560 (7 % slower).
@@ -613,22 +655,19 @@ struct LaunchChoice {
     long long tail_tiles;      // tiles of a second launch on the twin (0 = none)
 };
 
-static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, bool jac_out, bool pair = false)
+static LaunchChoice choose_launch(const LaunchDesc& d, long long tiles, bool jac_out)
 {
-    const long long chip = 1024ll * (k.wps > 0 ? k.wps : 1);
+    const long long chip = 1024ll * d.wps;
     auto twin_wins = [&](long long n) {
-        const int wps = k.wps > 0 ? k.wps : 1;
-        const double one_wave = (double)((n + 1023) / 1024) / (double)wps;
-        const double least = wps >= 3 ? 0.22 : (wps == 2 ? 0.30 : 0.35);
-        const bool pair3 = pair && wps >= 3;
-        const double line = (wps == 1 ? 0.20 : (pair3 ? 0.03 : 0.10)) + n / ((pair3 ? 0.85 : 0.95) * (double)chip);
-        return (line > least ? line : least) < one_wave;
+        const double one_wave = (double)((n + 1023) / 1024) / (double)d.wps;
+        const double line = d.c0 + n / (d.per_round * (double)chip);
+        return (line > d.least ? line : d.least) < one_wave;
     };
-    bool coop = k.launch_coop != nullptr && tiles <= chip && twin_wins(tiles);
-    if (const char* pin = getenv("FF_COOP")) coop = k.launch_coop != nullptr && atoi(pin) != 0;
-    if (k.launch == nullptr) coop = true;                  // wide catch-all: cooperative at every batch size, one exchange buffer
+    bool coop = d.coop != nullptr && tiles <= chip && twin_wins(tiles);
+    if (const char* pin = getenv("FF_COOP")) coop = d.coop != nullptr && atoi(pin) != 0;
+    if (d.one_wave == nullptr) coop = true;                // wide catch-all: cooperative at every batch size, one exchange buffer
     long long tail_tiles = 0;
-    if (!coop && k.launch_coop != nullptr && k.wps > 0 && !jac_out) {
+    if (!coop && d.coop != nullptr && !jac_out) {
         const long long rem = tiles % chip;
         const char* pin = getenv("FF_TAIL_SPLIT");
         if (tiles > chip && rem > 0 && !(pin && atoi(pin) == 0) && twin_wins(rem)) tail_tiles = rem;
@@ -636,178 +675,45 @@ static LaunchChoice choose_launch(const ff::KernelEntry& k, long long tiles, boo
     return LaunchChoice{coop, tiles - tail_tiles, tail_tiles};
 }
 
-// A two-network kernel as choose_launch sees it: the same rule in the same units (an evaluation is two networks on the
-// one-wavefront kernel and on the twin alike), with constants of its own where the measurement asked for them.
-static ff::KernelEntry pair_as_entry(const ff::PairKernelEntry& p)
-{
-    ff::KernelEntry k = {};
-    k.tile = p.tile; k.H = p.H; k.dregs = p.dregs; k.cregs = p.cregs;
-    k.launch = p.launch; k.name = p.name; k.launch_coop = p.launch_coop; k.wps = p.wps;
-    return k;
-}
-
-// A select kernel as choose_launch sees it (its twin's line is the pair twin's: the comment above choose_launch).
-static ff::KernelEntry select_as_entry(const ff::PairKernelEntry& p)
-{
-    ff::KernelEntry k = pair_as_entry(p);
-    k.launch = p.launch_select; k.launch_coop = p.launch_select_coop;
-    return k;
-}
-
 // What ff_mlp_ode_launch would enqueue for `batch` samples in `mode`: FF_LAUNCH_* (see the header).
 extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int32_t mode, int32_t tangent_count, int32_t jac_out)
 {
-    if (plan_ok_split(plan)) return FF_LAUNCH_ONE_WAVE;
-    if (plan_ok_pair(plan)) {
-        if (batch < 0 || mode != FF_MODE_STATE || jac_out) return FF_ERR_BADARG;
-        const ff::PairKernelEntry& pk = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_KERNEL_BASE];
-        const LaunchChoice ch = choose_launch(pair_as_entry(pk), (batch + plan->tile - 1) / plan->tile, false, true);
-        return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
-    }
-    if (plan_ok_select(plan)) {
-        if (batch < 0 || mode != FF_MODE_STATE || jac_out) return FF_ERR_BADARG;
-        const ff::PairKernelEntry& pk = ff::g_pair_kernels[plan->kernel_id - FF_PAIR_SELECT_KERNEL_BASE];
-        const LaunchChoice ch = choose_launch(select_as_entry(pk), (batch + plan->tile - 1) / plan->tile, false, true);
-        return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
-    }
-    if (!plan_ok(plan) || batch < 0) return FF_ERR_BADARG;
+    LaunchDesc d;
+    if (!describe(plan, &d)) return FF_ERR_BADARG;
+    if (d.family == kSplit) return FF_LAUNCH_ONE_WAVE;
+    if (batch < 0 || (d.state_only && (mode != FF_MODE_STATE || jac_out))) return FF_ERR_BADARG;
     int nt, unit;
     const int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
     if (rc) return rc;
     if (mode == FF_MODE_EXACT && tangent_count > 0) nt = tangent_count;
     if (nt + 1 > plan->tile) return FF_ERR_BADARG;
     const long long spt = plan->tile / (1 + nt);
-    const LaunchChoice ch = choose_launch(ff::g_kernels[plan->kernel_id], (batch + spt - 1) / spt, jac_out != 0);
+    const LaunchChoice ch = choose_launch(d, (batch + spt - 1) / spt, jac_out != 0);
     return ch.coop ? FF_LAUNCH_TWIN : (ch.tail_tiles ? FF_LAUNCH_ONE_WAVE_AND_TWIN : FF_LAUNCH_ONE_WAVE);
 }
 
-// pair plans (ff_mlp_pair.hpp): state-only integration of a table whose rows carry c1 of both networks; select plans: of
-// a table whose rows carry c1 of the one network they run (no first stage from the caller, no auxiliary outputs)
-static int launch_pair(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream, bool select = false)
+// Geometry and enqueue of every fp32 family: `ka` filled for the whole batch, `spt` samples per tile.  One-wavefront
+// kernel, cooperative twin, or full rounds on the first and the leftover rows on the twin (choose_launch).
+static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArgs ka, long long spt, bool jac_out, hipStream_t stream)
 {
-    if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
-    if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
-    if (a->mode != FF_MODE_STATE || a->jac_out) return FF_ERR_BADARG;      // divergence-free by construction: no tangents
-    if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
-    if (a->n_aux < 0 || a->n_aux > FF_MAX_AUX) return FF_ERR_BADARG;
-    if (a->noise && a->noise_stride < a->batch * (int64_t)plan->dim) return FF_ERR_BADARG;
-    if (select && (a->k1_in || a->n_aux > 0)) return FF_ERR_BADARG;
-    if (a->batch == 0) return FF_OK;
-    const ff::PairKernelEntry& k = ff::g_pair_kernels[plan->kernel_id - (select ? FF_PAIR_SELECT_KERNEL_BASE : FF_PAIR_KERNEL_BASE)];
-    const ff::KernelEntry ke = select ? select_as_entry(k) : pair_as_entry(k);
-    ff::KernelArgs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.gate = a->gate;
-    ka.x_in = a->x_in; ka.x_out = a->x_out; ka.cond = a->cond;
-    ka.noise = a->noise; ka.wpack = a->wpack; ka.etab = a->etab;
-    ka.in_shift = a->in_shift; ka.in_scale = a->in_scale; ka.out_scale = a->out_scale; ka.out_shift = a->out_shift;
-    ka.status = a->status; ka.batch = a->batch; ka.noise_stride = a->noise_stride;
-    ka.n_evals = a->n_evals; ka.n_hidden = plan->n_hidden; ka.dim = plan->dim; ka.cond_dim = plan->cond_dim;
-    ka.k1_in = a->k1_in; ka.n_aux = a->n_aux;
-    for (int j = 0; j < FF_MAX_AUX; ++j) ka.aux_out[j] = a->aux_out[j];
-    ka.rng_seed = a->rng_seed; ka.rng_sample_offset = a->rng_sample_offset; ka.rng_noise_base = a->rng_noise_base;
-    ka.etab_stride = FF_ROW_HDR + (select ? 1 : 2) * plan->width;
-    const ff::Layout L = plan_layout(plan);
-    if (2 * L.total_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
-    if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
-    ka.wpack_floats = (int)(2 * L.total_floats);
-    // one-wavefront kernel, cooperative twin, or full rounds on the first and the leftover rows on the twin (choose_launch)
-    const long long spt = plan->tile;
-    const LaunchChoice ch = choose_launch(ke, (a->batch + spt - 1) / spt, false, true);
+    const long long batch = ka.batch;
+    const LaunchChoice ch = choose_launch(d, (batch + spt - 1) / spt, jac_out);
     const bool coop = ch.coop;
     const long long main_tiles = ch.main_tiles, tail_tiles = ch.tail_tiles;
     const unsigned slots = ff::kSlots * (plan->dregs / 4) * 64 * 16;
     const unsigned kh = (plan->width / 32) * ff::tile_rb(plan->tile);                 // operand registers of a hidden layer
-    const unsigned lds_coop = slots + 2u * (kh / 4) * 64 * 16, lds_wave = 4u * slots;
+    const unsigned lds_coop = slots + (unsigned)d.exchange * (kh / 4) * 64 * 16, lds_wave = 4u * slots;
     if ((coop || tail_tiles ? lds_coop : 0u) > 160u * 1024u || (!coop ? lds_wave : 0u) > 160u * 1024u) return FF_ERR_UNSUPPORTED;
     const long long grid = coop ? main_tiles : (main_tiles + 3) / 4;
     if (grid > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
-    if (tail_tiles) ka.batch = main_tiles * spt;                                       // (full tiles only: < a->batch)
-    int herr = (coop ? ke.launch_coop : ke.launch)(&ka, (unsigned)grid, coop ? lds_coop : lds_wave, (hipStream_t)hip_stream);
+    if (tail_tiles) ka.batch = main_tiles * spt;                                       // (full tiles only: < batch)
+    int herr = (coop ? d.coop : d.one_wave)(&ka, (unsigned)grid, coop ? lds_coop : lds_wave, stream);
     if (herr == 0 && tail_tiles) {
-        // the same launch over rows [row0, batch), as in ff_mlp_ode_launch
+        // the same launch over rows [row0, batch): every per-row array moves on by row0 rows, the counter-based noise by
+        // row0 samples (an array the family does not pass is NULL here and stays NULL)
         const long long row0 = main_tiles * spt, D = plan->dim, C = plan->cond_dim;
         ff::KernelArgs t = ka;
-        t.batch = a->batch - row0;
-        t.x_in += row0 * D; t.x_out += row0 * D;
-        if (t.cond) t.cond += row0 * C;
-        if (t.noise) t.noise += row0 * D;
-        if (t.k1_in) t.k1_in += row0 * D;
-        for (int j = 0; j < FF_MAX_AUX; ++j)
-            if (t.aux_out[j]) t.aux_out[j] += row0 * D;
-        t.rng_sample_offset += row0;
-        herr = ke.launch_coop(&t, (unsigned)tail_tiles, lds_coop, (hipStream_t)hip_stream);
-    }
-    if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
-    return FF_OK;
-}
-
-extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
-{
-    if (a && plan_ok_split(plan)) return launch_split(plan, a, hip_stream);
-    if (a && plan_ok_pair(plan)) return launch_pair(plan, a, hip_stream);
-    if (a && plan_ok_select(plan)) return launch_pair(plan, a, hip_stream, true);
-    if (!plan_ok(plan) || !a) return FF_ERR_BADARG;
-    if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
-    if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
-    const ff::KernelEntry& k = ff::g_kernels[plan->kernel_id];
-    int nt, unit;
-    int rc = tangents_of_mode(a->mode, plan->dim, plan->tile, &nt, &unit);
-    if (rc) return rc;
-    int tfirst = 0;
-    if (a->mode == FF_MODE_EXACT) {
-        tfirst = a->tangent_first;
-        if (a->tangent_count > 0) nt = a->tangent_count;
-        else if (plan->dim > nt) return FF_ERR_BADARG;      // must be split by the caller
-        if (tfirst < 0 || tfirst + nt > plan->dim || nt + 1 > plan->tile) return FF_ERR_BADARG;
-    }
-    if ((a->mode != FF_MODE_STATE) != (k.tangents != 0)) return FF_ERR_BADARG;
-    if (a->mode == FF_MODE_HUTCH && !a->probe) return FF_ERR_BADARG;
-    if (a->mode != FF_MODE_STATE && !a->dlogp_out) return FF_ERR_BADARG;
-    if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
-    if (a->batch == 0) return FF_OK;
-
-    ff::KernelArgs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.x_in = a->x_in; ka.x_out = a->x_out; ka.cond = a->cond; ka.probe = a->probe;
-    ka.dlogp_out = a->dlogp_out; ka.noise = a->noise; ka.wpack = a->wpack; ka.etab = a->etab;
-    ka.in_shift = a->in_shift; ka.in_scale = a->in_scale; ka.out_scale = a->out_scale; ka.out_shift = a->out_shift;
-    ka.status = a->status; ka.batch = a->batch; ka.noise_stride = a->noise_stride;
-    ka.n_evals = a->n_evals; ka.n_hidden = plan->n_hidden; ka.dim = plan->dim; ka.cond_dim = plan->cond_dim;
-    ka.n_tangent = nt; ka.unit_tangents = unit; ka.tangent_first = tfirst;
-    if (a->n_aux < 0 || a->n_aux > FF_MAX_AUX) return FF_ERR_BADARG;
-    ka.k1_in = a->k1_in; ka.kl1_in = a->kl1_in; ka.dlogp_in = a->dlogp_in; ka.n_aux = a->n_aux;
-    for (int j = 0; j < FF_MAX_AUX; ++j) { ka.aux_out[j] = a->aux_out[j]; ka.aux_lp_out[j] = a->aux_lp_out[j]; }
-    ka.rng_seed = a->rng_seed; ka.rng_sample_offset = a->rng_sample_offset; ka.rng_noise_base = a->rng_noise_base;
-    if (a->jac_out && a->mode != FF_MODE_EXACT) return FF_ERR_BADARG;
-    ka.jac_out = a->jac_out;
-    ka.jac_all = a->jac_out && a->jac_all ? 1 : 0;
-    ka.act_kind = plan->activation; ka.act_p0 = plan->act_param[0]; ka.act_p1 = plan->act_param[1];
-    ka.gate = a->gate;
-    ka.etab_stride = FF_ROW_HDR + plan->width;
-    const ff::Layout L = plan_layout(plan);
-    if (L.total_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
-    if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
-    ka.wpack_floats = (int)L.total_floats;
-
-    const long long spt = plan->tile / (1 + nt);           // samples per tile
-    const LaunchChoice ch = choose_launch(k, (a->batch + spt - 1) / spt, a->jac_out != nullptr);
-    const bool coop = ch.coop, wide = k.launch == nullptr;
-    const long long tiles = ch.main_tiles + ch.tail_tiles, tail_tiles = ch.tail_tiles;
-    const unsigned slots = ff::kSlots * (plan->dregs / 4) * 64 * 16;
-    const unsigned kh = (plan->width / 32) * ff::tile_rb(plan->tile);                 // operand registers of a hidden layer
-    const unsigned lds_coop = slots + (wide ? 1u : 2u) * (kh / 4) * 64 * 16, lds_wave = 4u * slots;
-    if ((coop || tail_tiles ? lds_coop : 0u) > 160u * 1024u || (!coop ? lds_wave : 0u) > 160u * 1024u) return FF_ERR_UNSUPPORTED;
-    const long long main_tiles = tiles - tail_tiles;
-    const long long grid = coop ? main_tiles : (main_tiles + 3) / 4;
-    if (grid > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
-    if (tail_tiles) ka.batch = main_tiles * spt;                                       // (full tiles only: < a->batch)
-    int herr = (coop ? k.launch_coop : k.launch)(&ka, (unsigned)grid, coop ? lds_coop : lds_wave, (hipStream_t)hip_stream);
-    if (herr == 0 && tail_tiles) {
-        // the same launch over rows [row0, batch): every per-row array moves on by row0 rows, the counter-based noise by row0 samples
-        const long long row0 = main_tiles * spt, D = plan->dim, C = plan->cond_dim;
-        ff::KernelArgs t = ka;
-        t.batch = a->batch - row0;
+        t.batch = batch - row0;
         t.x_in += row0 * D; t.x_out += row0 * D;
         if (t.cond) t.cond += row0 * C;
         if (t.probe) t.probe += row0 * D;
@@ -821,10 +727,47 @@ extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a
             if (t.aux_lp_out[j]) t.aux_lp_out[j] += row0;
         }
         t.rng_sample_offset += row0;
-        herr = k.launch_coop(&t, (unsigned)tail_tiles, lds_coop, (hipStream_t)hip_stream);
+        herr = d.coop(&t, (unsigned)tail_tiles, lds_coop, stream);
     }
     if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
     return FF_OK;
+}
+
+extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
+{
+    LaunchDesc d;
+    if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
+    if (d.family == kSplit) return launch_split(plan, *d.split, a, hip_stream);
+    if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
+    if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
+    int nt, unit;
+    int rc = tangents_of_mode(a->mode, plan->dim, plan->tile, &nt, &unit);
+    if (rc) return rc;
+    int tfirst = 0;
+    if (a->mode == FF_MODE_EXACT) {
+        tfirst = a->tangent_first;
+        if (a->tangent_count > 0) nt = a->tangent_count;
+        else if (plan->dim > nt) return FF_ERR_BADARG;      // must be split by the caller
+        if (tfirst < 0 || tfirst + nt > plan->dim || nt + 1 > plan->tile) return FF_ERR_BADARG;
+    }
+    // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
+    if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && !a->probe) return FF_ERR_BADARG;
+    if (a->mode != FF_MODE_STATE && !a->dlogp_out) return FF_ERR_BADARG;
+    if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
+    if (a->batch == 0 && d.empty_batch_first) return FF_OK;
+    if (a->n_aux < 0 || a->n_aux > d.max_aux || (a->k1_in && !d.takes_k1)) return FF_ERR_BADARG;
+    if (a->jac_out && a->mode != FF_MODE_EXACT) return FF_ERR_BADARG;
+    if (d.checks_noise_stride && a->noise && a->noise_stride < a->batch * (int64_t)plan->dim) return FF_ERR_BADARG;
+    if (a->batch == 0) return FF_OK;
+
+    ff::KernelArgs ka = fill_args(plan, a, !d.state_only, nt, unit, tfirst);
+    ka.etab_stride = FF_ROW_HDR + d.row_nets * plan->width;
+    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats;
+    if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
+    if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
+    ka.wpack_floats = (int)wpack_floats;
+    return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

@@ -40,6 +40,14 @@ struct SplitKernelEntry {
 extern const SplitKernelEntry g_split_kernels[];
 extern const int g_n_split_kernels;
 
+// the launchers of one kernel shape: the one-wavefront kernel and its cooperative twin for small batches (one tile per
+// workgroup), and the name the kernel goes by
+struct Launchers {
+    LaunchFn one_wave;      // NULL: the library carries no kernel of this kind
+    LaunchFn coop;          // NULL: no twin
+    const char* name;
+};
+
 // two-network family (ff_mlp_pair.hpp, ff_mlp_pair_plan): state-only, SiLU; a pair plan's kernel_id is
 // FF_PAIR_KERNEL_BASE + the index into this table
 struct PairKernelEntry {
@@ -48,13 +56,10 @@ struct PairKernelEntry {
     int dregs;      // state registers
     int cregs;      // conditional registers
     int wps;        // wavefronts per SIMD (launch bound)
-    LaunchFn launch;
-    const char* name;
-    LaunchFn launch_coop;   // cooperative twin for small batches (one tile per workgroup) or NULL
+    Launchers pair;
     // row-select variant of the same shape (ff_mlp_pair_select_plan: kernel_id FF_PAIR_SELECT_KERNEL_BASE + the index): a row
-    // runs one of the two networks.  Not entries of a table of their own; NULL where a library carries none.
-    LaunchFn launch_select;
-    LaunchFn launch_select_coop;
+    // runs one of the two networks.  Not entries of a table of their own; one_wave NULL where a library carries none.
+    Launchers select;
 };
 extern const PairKernelEntry g_pair_kernels[];
 extern const int g_n_pair_kernels;
