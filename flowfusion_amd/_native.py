@@ -425,7 +425,7 @@ def normal_fill(batch: int, dim: int, seed: int, sample_offset: int, device, noi
 
 def stage_combine(out: torch.Tensor, x: Optional[torch.Tensor], ks, coefs, x_coef: float = 1.0) -> torch.Tensor:
     """ff_stage_combine: out = x_coef * x + sum_s coefs[s] * ks[s] in one pass (flat fp32 device tensors of
-    equal numel; `out` may alias an input).  Terms with a zero coefficient are not read."""
+    equal numel; `out` may alias an input).  Terms with a zero coefficient are not read, `x` with a zero `x_coef` included."""
     if not out.is_cuda:
         raise RuntimeError("flowfusion_amd: ff_stage_combine works on device memory (there is no CPU path)")
     dev = out.device

@@ -142,8 +142,9 @@ extern "C" int ff_stage_combine(const ff_combine_args* a, void* hip_stream)
     if (!a || !a->out || a->n < 0) return FF_ERR_BADARG;
     if (a->n == 0) return FF_OK;
     ff::CombineArgs k;
-    k.x = a->x; k.x_coef = a->x_coef; k.out = a->out; k.n = a->n;
-    uintptr_t bits = (uintptr_t)a->out | (uintptr_t)a->x;
+    k.x = a->x_coef != 0.f ? a->x : nullptr;                  // like a zero coefficient: x is neither read nor aligned against
+    k.x_coef = a->x_coef; k.out = a->out; k.n = a->n;
+    uintptr_t bits = (uintptr_t)a->out | (uintptr_t)k.x;
     for (int s = 0; s < FF_MAX_SLOTS; ++s) {
         k.k[s] = a->coef[s] != 0.f ? a->k[s] : nullptr;       // a zero coefficient never reads its array
         k.coef[s] = a->coef[s];

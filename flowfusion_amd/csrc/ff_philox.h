@@ -22,7 +22,7 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
 }
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1)
 {
-    const float u1 = __builtin_fmaf((float)(a >> 8), 0x1p-24f, 0x1p-25f);        // (0, 1)
+    const float u1 = __builtin_fmaf((float)(a >> 8), 0x1p-24f, 0x1p-25f);        // (0, 1]: word 0xFFFFFF rounds to 1.0f, radius 0
     const float u2 = (float)(b >> 8) * 0x1p-24f;                                   // [0, 1): a turn
     const float rad = __builtin_amdgcn_sqrtf(-1.38629436111989061883f * __builtin_amdgcn_logf(u1));   // sqrt(-2 ln u1)
     z0 = rad * __builtin_amdgcn_cosf(u2);                                          // v_cos/v_sin take turns

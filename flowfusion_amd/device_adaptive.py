@@ -34,6 +34,10 @@ FIRST_CHUNK = 16          # attempted steps enqueued before the first look at th
 TRACE = None              # diagnostics: a list collects (attempts, accepted, t, dt, last error ratio) after every attempted step
                           # (one attempt per chunk while it is set; scratch/diag_adaptive_pair.py)
 TRACE_ROWS = False        # ... and a host copy of the evaluation table the controller wrote for the NEXT attempt (tests)
+TRACE_STATE = False       # ... and, last in the entry, a dict of host clones of the work views (y, f0, aux[, lp, fl0, aux_lp,
+                          # aux_lp_pass]), the state's t_prev / dt_prev / t_end / commit / done and, after the last chunk, out_y / out_lp
+                          # (tests)
+TRACE_STATE_FIRST = None  # ... with TRACE_STATE: clone for the first N attempts and the last only (None in between)
 MAX_CHUNK = 64
 POISON = None             # tests: a value the work buffers are filled with before the solve (uninitialised reads show)
 MAX_TIME_COLS = 64        # kMaxTimeCols of ff_adaptive.hip
@@ -275,7 +279,8 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
                 raise err
             if TRACE is not None:
                 TRACE.append((int(st.n_attempts), int(st.n_accepted), float(st.t), float(st.dt), float(st.last_ratio))
-                             + ((etab.view(8, 32 + width).cpu().clone(),) if TRACE_ROWS else ()))
+                             + ((etab.view(8, 32 + width).cpu().clone(),) if TRACE_ROWS else ())
+                             + ((_trace_state(st, v, has_lp, P, out_y, out_lp, len(TRACE)),) if TRACE_STATE else ()))
             if st.done:
                 break
             if not st.active:
@@ -286,6 +291,24 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
     del keep
     stats = {"attempts": int(st.n_attempts), "accepted": int(st.n_accepted), "chunks": chunks}
     return out_y, (out_lp if has_lp else None), stats
+
+
+def _trace_state(st, v, has_lp, P, out_y, out_lp, index):
+    """TRACE_STATE: what one attempted step left in the work buffers, as host clones (``v``: the views ``solve`` carved)."""
+    if TRACE_STATE_FIRST is not None and index >= TRACE_STATE_FIRST and not st.done:
+        return None
+    host = lambda t: t.detach().cpu().clone()
+    d = {"t_prev": float(st.t_prev), "dt_prev": float(st.dt_prev), "t_end": float(st.t_end), "commit": int(st.commit), "done": int(st.done),
+         "y": host(v[1]), "f0": host(v[2]), "aux": [host(t) for t in v[3:7]]}
+    if has_lp:
+        d.update(lp=host(v[9]), fl0=host(v[10]), aux_lp=[host(t) for t in v[11:15]])
+        if P > 1:
+            d["aux_lp_pass"] = host(v[16]).view(P, 4, -1)
+    if st.done:
+        d["out_y"] = host(out_y)
+        if has_lp:
+            d["out_lp"] = host(out_lp)
+    return d
 
 
 def _passes(net, plan):

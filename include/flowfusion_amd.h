@@ -352,7 +352,8 @@ int ff_normal_fill(float* out, int64_t batch, int32_t dim, uint64_t seed, int64_
 
 /*
  * out = x_coef * x + sum_s coef[s] * k[s]   over n contiguous fp32 elements (DEVICE pointers; x may be NULL,
- * k[s] is not read when coef[s] == 0; out may alias x or a k[s]).
+ * k[s] is not read when coef[s] == 0 and x is not read when x_coef == 0: such an array may hold anything, NaN included,
+ * and its alignment does not decide between the 16-byte and the scalar loop; out may alias x or a k[s]).
  * The stage-input, step-update, dense-output and error-estimate algebra of an explicit Runge-Kutta step for a
  * right-hand side evaluated OUTSIDE the library -- the reference accepts any `model=` module in ScoreModel
  * (diffusion.py:201,233-238) and hands the stepping to torchdiffeq (call sites diffusion.py:631-639, 744-752),

@@ -9,6 +9,16 @@ M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 MASK = np.uint64(0xFFFFFFFF)
 
+# rows of the counter-based stream at the extremes of the Box-Muller mapping: (global row, pair of the row's four normals,
+# what its words are); seed 2024, the prior's noise index, dim 4 -- tests/test_host_logic.py proves them without a GPU,
+# tests/test_gpu_stream_kernels.py feeds them to ff_normal_fill
+EXTREME_SEED = 2024
+EXTREME_ROWS = [
+    (4267672, 0, "radius_min_word"), (1510162, 1, "radius_min_word"),
+    (15768586, 1, "radius_max_word"), (39224954, 1, "radius_max_word"),
+    (378522, 0, "angle_zero_word"), (27042013, 0, "angle_zero_word"),
+]
+
 
 def philox4x32_10(counter, key):
     """counter: uint32 array [..., 4]; key: (k0, k1) python ints.  Returns uint32 [..., 4]."""

@@ -566,6 +566,33 @@ def test_philox_known_answers_and_normals():
     assert not np.array_equal(normals(2025, 0, 10, 6, [0]), z[:1, :10])
 
 
+def test_philox_rows_at_the_extremes_of_the_box_muller_mapping():
+    """The rows tests/test_gpu_stream_kernels.py feeds to ff_normal_fill as the extremes of the mapping (seed 2024, the
+    prior's noise index, dim 4; found by a search of the restatement over 39 M rows) really are what that test says they
+    are: a radius word of 0 (u1 = 2^-25, the largest radius of the stream), a radius word of 0xFFFFFF (u1 rounds to exactly
+    1.0f, radius 0) and an angle word of 0.  The mapping uses the upper 24 bits of a word."""
+    import numpy as np
+    from tests._philox import EXTREME_ROWS, EXTREME_SEED, box_muller, normals, philox4x32_10
+    rows = [r for r, _, _ in EXTREME_ROWS]
+    ctr = np.zeros((len(rows), 4), dtype=np.uint32)
+    ctr[:, 0], ctr[:, 2] = rows, 0xFFFFFFFF
+    words = philox4x32_10(ctr, (EXTREME_SEED & 0xFFFFFFFF, EXTREME_SEED >> 32)) >> np.uint32(8)
+    for (row, pair, kind), w in zip(EXTREME_ROWS, words):
+        radius, angle = int(w[2 * pair]), int(w[2 * pair + 1])
+        z = normals(EXTREME_SEED, row, 1, 4, [0xFFFFFFFF])[0, 0, 2 * pair:2 * pair + 2]
+        if kind == "radius_min_word":
+            assert radius == 0 and abs(float(np.hypot(*z.astype(np.float64))) - np.sqrt(50 * np.log(2.0))) < 1e-6      # 5.887
+        elif kind == "radius_max_word":
+            assert radius == 0xFFFFFF and np.all(z == 0.0)
+            u1 = np.float32(radius) * np.float32(2.0 ** -24) + np.float32(2.0 ** -25)
+            assert u1 == np.float32(1.0)                                 # 1 - 2^-25 is a tie: it rounds to even, 1.0f
+        else:
+            assert kind == "angle_zero_word" and angle == 0 and z[1] == 0.0 and z[0] > 0.0
+    assert {k for _, _, k in EXTREME_ROWS} == {"radius_min_word", "radius_max_word", "angle_zero_word"}
+    z0, z1 = box_muller(np.array([0], dtype=np.uint32), np.array([0], dtype=np.uint32))
+    assert abs(float(z0[0]) - 5.8870501) < 1e-6 and z1[0] == 0.0
+
+
 def test_emulated_euler_maruyama_with_philox_noise(built_library):
     """Host plumbing of noise="philox": the table of a whole Euler-Maruyama run (one launch) through the kernel
     semantics with the restated generator equals the oracle's loop fed with the same normals."""
