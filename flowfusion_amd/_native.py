@@ -322,8 +322,8 @@ def pack_weights(plan: PlanStruct, weights: List[torch.Tensor], biases: List[Opt
     L = lib()
     n = L.ff_mlp_wpack_floats(ctypes.byref(plan))
     out = torch.empty(n, dtype=torch.float32)
-    ws = [w.detach().to("cpu", torch.float32).contiguous() for w in weights]
-    bs = [None if b is None else b.detach().to("cpu", torch.float32).contiguous() for b in biases]
+    ws = [f32_on(w, "cpu") for w in weights]
+    bs = [f32_on(b, "cpu") for b in biases]
     wp = (ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
     bp = (ctypes.c_void_p * len(bs))(*[0 if b is None else b.data_ptr() for b in bs])
     hw = (ctypes.c_int * len(hidden))(*hidden)
@@ -373,11 +373,10 @@ def pack_pair_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[int], x
     L = lib()
     n = L.ff_mlp_pair_wpack_floats(ctypes.byref(plan))
     out = torch.empty(n, dtype=torch.float32)
-    host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
     keep, ptrs = [], []
     for layers in (q_layers, p_layers):
-        ws = [host(l.weight) for l in layers]
-        bs = [host(l.bias) for l in layers]
+        ws = [f32_on(l.weight, "cpu") for l in layers]
+        bs = [f32_on(l.bias, "cpu") for l in layers]
         keep += ws + bs
         ptrs.append((ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws]))
         ptrs.append((ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs]))
@@ -480,8 +479,7 @@ def trace_estimate(jac: torch.Tensor, kind: str, probes, host: bool = False) -> 
     dev = jac.device
     if host != (dev.type == "cpu"):
         raise RuntimeError("flowfusion_amd: ff_trace_estimate works on device memory (host=True: CPU tensors, tests only)")
-    f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    jac, p0, p1 = f32(jac), f32(p0), f32(p1)
+    jac, p0, p1 = f32_on(jac, dev), f32_on(p0, dev), f32_on(p1, dev)
     out = torch.empty(n_rows, B, dtype=torch.float32, device=dev)
     items = 1 if host else n_rows * B
     ws = torch.empty(max(1, int(lib().ff_trace_workspace_floats(code, D, r, items))), dtype=torch.float32, device=dev)
@@ -573,6 +571,42 @@ def _chk(t: Optional[torch.Tensor], name: str, dev) -> int:
     return t.data_ptr()
 
 
+def f32_on(t: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
+    """``t`` (or None) detached, on ``dev``, contiguous float32: the form in which every C call takes a tensor."""
+    return None if t is None else t.detach().to(dev, torch.float32).contiguous()
+
+
+# the caller's tensors among the ff_ode_args fields -> the name the ops' signatures (and so _chk's messages) give each
+_ARG_NAMES = {"x_in": "x", "cond": "cond", "probe": "probe", "noise": "noise", "wpack": "wpack", "etab": "etab",
+              "in_shift": "in_shift", "in_scale": "in_scale", "out_scale": "out_scale", "out_shift": "out_shift",
+              "k1_in": "k1", "kl1_in": "kl1", "dlogp_in": "dlogp0", "jac_out": "jac"}
+_AuxPtrs = ctypes.c_void_p * MAX_AUX
+
+
+def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
+    """ff_ode_args.aux_out / aux_lp_out: the addresses of t[0], t[1], .. of a contiguous fp32 tensor the op allocated
+    (NULL throughout for one without elements: the state-only modes' aux_lp)."""
+    if t.numel() == 0:
+        return _AuxPtrs()
+    step = t.numel() // t.shape[0] * 4
+    return _AuxPtrs(*range(t.data_ptr(), t.data_ptr() + t.shape[0] * step, step))
+
+
+def _launch_ode(p: PlanStruct, dev, tensors: dict, **fields) -> None:
+    """The one ff_mlp_ode_launch of the four ops below, on torch's current stream of ``dev``.  ``tensors``: the caller's
+    tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
+    of what the op allocated itself.  A field named in neither stays zero."""
+    a = OdeArgs(**fields)
+    for field, t in tensors.items():
+        if t is not None:
+            setattr(a, field, _chk(t, _ARG_NAMES[field], dev))
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_ode_launch")
+
+
 @torch.library.custom_op("flowfusion_amd::mlp_ode", mutates_args=())
 def mlp_ode(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[torch.Tensor],
             noise: Optional[torch.Tensor], wpack: torch.Tensor, etab: torch.Tensor,
@@ -596,41 +630,18 @@ def mlp_ode(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[torch
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     if B == 0:                      # nothing to integrate (zero-size tensors have no storage to point at)
         return x_out, dlogp, status
-    a = OdeArgs()
-    a.x_in = _chk(x, "x", dev)
-    a.x_out = x_out.data_ptr()
-    a.cond = _chk(cond, "cond", dev)
-    a.probe = _chk(probe, "probe", dev)
-    a.dlogp_out = dlogp.data_ptr() if mode != MODE_STATE else 0
-    a.noise = _chk(noise, "noise", dev)
-    a.wpack = _chk(wpack, "wpack", dev)
-    a.etab = _chk(etab, "etab", dev)
-    a.in_shift = _chk(in_shift, "in_shift", dev)
-    a.in_scale = _chk(in_scale, "in_scale", dev)
-    a.out_scale = _chk(out_scale, "out_scale", dev)
-    a.out_shift = _chk(out_shift, "out_shift", dev)
-    a.status = status.data_ptr()
-    a.batch = B
-    a.noise_stride = B * D
-    a.n_evals = etab.shape[0]
-    a.mode = mode
-    a.tangent_first = tangent_first
-    a.tangent_count = tangent_count
-    a.rng_seed = rng_seed & 0xFFFFFFFFFFFFFFFF
-    a.rng_sample_offset = rng_sample_offset
-    a.rng_noise_base = rng_noise_base
-    a.stage_slots = _slots_hint(plan)
     if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
         raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
     if probe is not None and tuple(probe.shape) != (B, D):
         raise RuntimeError(f"probe has shape {tuple(probe.shape)}, expected {(B, D)}")
     if etab.shape[1] != 32 + row_width(p):
         raise RuntimeError("evaluation table width does not match the plan")
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
-    if rc != FF_OK:
-        raise _err(rc, "ff_mlp_ode_launch")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": probe, "noise": noise, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                x_out=x_out.data_ptr(), dlogp_out=dlogp.data_ptr() if mode != MODE_STATE else 0, status=status.data_ptr(),
+                batch=B, noise_stride=B * D, n_evals=etab.shape[0], mode=mode,
+                tangent_first=tangent_first, tangent_count=tangent_count, rng_seed=rng_seed & 0xFFFFFFFFFFFFFFFF,
+                rng_sample_offset=rng_sample_offset, rng_noise_base=rng_noise_base, stage_slots=_slots_hint(plan))
     return x_out, dlogp, status
 
 
@@ -662,34 +673,14 @@ def mlp_ode_step(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[
         return aux, aux_lp
     scratch = torch.empty_like(x)
     dl = torch.empty(B if mode != MODE_STATE else 0, dtype=torch.float32, device=dev)
-    a = OdeArgs()
-    a.x_in = _chk(x, "x", dev)
-    a.x_out = scratch.data_ptr()
-    a.cond = _chk(cond, "cond", dev)
-    a.probe = _chk(probe, "probe", dev)
-    a.dlogp_out = dl.data_ptr() if mode != MODE_STATE else 0
-    a.wpack = _chk(wpack, "wpack", dev)
-    a.etab = _chk(etab, "etab", dev)
-    a.batch = B
-    a.n_evals = etab.shape[0] - 2
-    a.mode = mode
-    a.tangent_first = tangent_first
-    a.tangent_count = tangent_count
-    a.k1_in = _chk(k1, "k1", dev)
-    a.kl1_in = _chk(kl1, "kl1", dev)
-    a.dlogp_in = _chk(dlogp0, "dlogp0", dev)
-    for j in range(n_aux):
-        a.aux_out[j] = aux[j].data_ptr()
-        a.aux_lp_out[j] = aux_lp[j].data_ptr() if mode != MODE_STATE else 0
-    a.n_aux = n_aux
-    a.stage_slots = _slots_hint(plan)
-    if etab.shape[1] != 32 + row_width(p) or a.n_evals < 0:
+    n_evals = etab.shape[0] - 2
+    if etab.shape[1] != 32 + row_width(p) or n_evals < 0:
         raise RuntimeError("evaluation table does not match the plan")
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
-    if rc != FF_OK:
-        raise _err(rc, "ff_mlp_ode_launch")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": probe, "wpack": wpack, "etab": etab,
+                         "k1_in": k1, "kl1_in": kl1, "dlogp_in": dlogp0},
+                x_out=scratch.data_ptr(), dlogp_out=dl.data_ptr() if mode != MODE_STATE else 0,
+                batch=B, n_evals=n_evals, mode=mode, tangent_first=tangent_first, tangent_count=tangent_count,
+                aux_out=_row_ptrs(aux), aux_lp_out=_row_ptrs(aux_lp), n_aux=n_aux, stage_slots=_slots_hint(plan))
     return aux, aux_lp
 
 
@@ -713,30 +704,13 @@ def mlp_rhs_jac(x: torch.Tensor, cond: Optional[torch.Tensor], wpack: torch.Tens
     rhs = torch.empty_like(x)
     if B == 0:
         return rhs
-    if tuple(jac.shape) != (B, D, D) or etab.shape[0] != 3 or etab.shape[1] != 32 + p.width:
+    if tuple(jac.shape) != (B, D, D) or etab.shape[0] != 3 or etab.shape[1] != 32 + row_width(p):
         raise RuntimeError("mlp_rhs_jac: jac must be [B, D, D] and etab one evaluation row + two auxiliary rows")
     scratch = torch.empty_like(x)
     dl = torch.empty(B, dtype=torch.float32, device=dev)
-    a = OdeArgs()
-    a.x_in = _chk(x, "x", dev)
-    a.x_out = scratch.data_ptr()
-    a.cond = _chk(cond, "cond", dev)
-    a.dlogp_out = dl.data_ptr()
-    a.wpack = _chk(wpack, "wpack", dev)
-    a.etab = _chk(etab, "etab", dev)
-    a.batch = B
-    a.n_evals = 1
-    a.mode = MODE_EXACT
-    a.tangent_first = tangent_first
-    a.tangent_count = tangent_count
-    a.aux_out[0] = rhs.data_ptr()
-    a.n_aux = 1
-    a.jac_out = _chk(jac, "jac", dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
-    if rc != FF_OK:
-        raise _err(rc, "ff_mlp_ode_launch")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "wpack": wpack, "etab": etab, "jac_out": jac},
+                x_out=scratch.data_ptr(), dlogp_out=dl.data_ptr(), batch=B, n_evals=1, mode=MODE_EXACT,
+                tangent_first=tangent_first, tangent_count=tangent_count, aux_out=_AuxPtrs(rhs.data_ptr()), n_aux=1)
     return rhs
 
 
@@ -761,28 +735,12 @@ def mlp_ode_jacobians(x: torch.Tensor, cond: Optional[torch.Tensor], wpack: torc
     if B == 0:
         return x_out
     n_evals = etab.shape[0]
-    if tuple(jac.shape) != (n_evals, B, D, D) or etab.shape[1] != 32 + p.width:
+    if tuple(jac.shape) != (n_evals, B, D, D) or etab.shape[1] != 32 + row_width(p):
         raise RuntimeError("mlp_ode_jacobians: jac must be [n_evals, B, D, D] and etab must match the plan")
     dl = torch.empty(B, dtype=torch.float32, device=dev)
-    a = OdeArgs()
-    a.x_in = _chk(x, "x", dev)
-    a.x_out = x_out.data_ptr()
-    a.cond = _chk(cond, "cond", dev)
-    a.dlogp_out = dl.data_ptr()
-    a.wpack = _chk(wpack, "wpack", dev)
-    a.etab = _chk(etab, "etab", dev)
-    a.batch = B
-    a.n_evals = n_evals
-    a.mode = MODE_EXACT
-    a.tangent_first = tangent_first
-    a.tangent_count = tangent_count
-    a.jac_out = _chk(jac, "jac", dev)
-    a.jac_all = 1
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
-    if rc != FF_OK:
-        raise _err(rc, "ff_mlp_ode_launch")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "wpack": wpack, "etab": etab, "jac_out": jac},
+                x_out=x_out.data_ptr(), dlogp_out=dl.data_ptr(), batch=B, n_evals=n_evals, mode=MODE_EXACT,
+                tangent_first=tangent_first, tangent_count=tangent_count, jac_all=1)
     return x_out
 
 

@@ -164,9 +164,8 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
     P = len(passes)
     if P > _native.ADAPT_MAX_PASSES:
         raise NotImplementedError(f"{P} unit-tangent passes per attempted step exceed FF_ADAPT_MAX_PASSES")
-    f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
-    cond_d = f32(cond) if net.cond_dim > 0 else None
-    probe_d = f32(probe)
+    cond_d = _native.f32_on(cond, dev) if net.cond_dim > 0 else None
+    probe_d = _native.f32_on(probe, dev)
     wpack = net.wpack(dev, mode)
     width = net.width(mode)         # first-layer bias words per evaluation row (plan.width; twice that on a pair plan)
     nBD, nB = B * D, B
@@ -196,7 +195,7 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
             b.aux_lp[j] = aux_lp[j].data_ptr()
         if P > 1:
             b.aux_lp_pass = v[16].data_ptr()
-    extras = [f32(c).reshape(-1) for c in norm_only if c is not None and c.numel() > 0]
+    extras = [_native.f32_on(c, dev).reshape(-1) for c in norm_only if c is not None and c.numel() > 0]
     if len(extras) > 2:
         raise NotImplementedError("more than two norm-only state components")
     for j, c in enumerate(extras):
@@ -208,7 +207,7 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
         code, p0, p1, r, m = _native.trace_kind_and_probes(kind, probes)
         if tuple(p0.shape) != (r, B, D) or (p1 is not None and tuple(p1.shape) != (m, B, D)) or r > D:
             raise RuntimeError(f"{kind} probes of shape {tuple(p0.shape)} do not fit a [{B}, {D}] state")
-        p0, p1 = f32(p0), f32(p1)
+        p0, p1 = _native.f32_on(p0, dev), _native.f32_on(p1, dev)
         rows = cfg.n_stages - 1
         est_jac = torch.empty(rows * B * D * D, dtype=torch.float32, device=dev)
         est_div = torch.empty(rows * B, dtype=torch.float32, device=dev)

@@ -52,10 +52,11 @@ def _is_adaptive(method) -> bool:
     return method in solvers.ALL_ADAPTIVE
 
 
-def _step_control(n: int, world: int, group, global_control: bool, method):
+def _step_control(n: int, group, global_control: bool, method):
     """The context a sharded solve runs in.  Batch-global step control needs every rank in the exchange, and an empty
     shard has no launch to hang the exchange on: its peers would wait in the all-reduce for ever.  ``n`` and ``world``
     are known to every rank, so every rank raises here, before anyone enters a collective."""
+    world = _shard(n, group)[0]
     if not (global_control and world > 1 and _is_adaptive(method)):
         return contextlib.nullcontext()
     if n < world:
@@ -92,7 +93,49 @@ def shard_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
 
 
 def shard_sizes(n: int, world: int):
-    return [shard_bounds(n, world, r)[1] - shard_bounds(n, world, r)[0] for r in range(world)]
+    return [hi - lo for lo, hi in (shard_bounds(n, world, r) for r in range(world))]
+
+
+# ---- what every sharded entry point below does before and after its solve ---------------------------------------------------
+def _shard(n: int, group) -> Tuple[int, int, int, int]:
+    """(world, rank, lo, hi): the rows [lo, hi) of an n-row batch this rank owns (one rank without a process group)."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    return (world, rank) + shard_bounds(n, world, rank)
+
+
+def _local_rows(full, local, lo, hi, what):
+    if local is not None:
+        if full is not None or local.shape[0] != hi - lo:
+            raise ValueError(f"local_{what} must hold exactly this rank's rows [{lo}, {hi}) (and excludes `{what}`)")
+        return local.contiguous()
+    return None if full is None else full[lo:hi].contiguous()
+
+
+def _local_batch(x, local_x, n_total, conditional, local_conditional, group):
+    """(n, lo, hi, rows, cond) of a log-density entry point: ``x`` (and ``conditional``) are the full tensors, every rank
+    slicing its rows -- or ``local_x`` (and ``local_conditional``) this rank's rows already, with ``n_total`` the size of
+    the whole batch."""
+    if (x is None) == (local_x is None):
+        raise ValueError("pass either the full batch `x` or this rank's rows `local_x` (with n_total)")
+    if x is None and n_total is None:
+        raise ValueError("local_x needs n_total")
+    if x is not None and local_conditional is not None:
+        raise ValueError("local_conditional goes with local_x")
+    if x is None and conditional is not None:
+        raise ValueError("local_x goes with local_conditional, not the full `conditional`")
+    n = int(x.shape[0] if x is not None else n_total)
+    _, _, lo, hi = _shard(n, group)
+    return n, lo, hi, _local_rows(x, local_x, lo, hi, "x"), _local_rows(conditional, local_conditional, lo, hi, "conditional")
+
+
+def _finish(local: torch.Tensor, n: int, group, gather: bool):
+    """The one collective at the end: the gathered [n, ...] result, or with ``gather=False`` this rank's rows and their
+    bounds."""
+    world, _, lo, hi = _shard(n, group)
+    if not gather:
+        return local, (lo, hi)
+    return gather_rows(local, n, group) if world > 1 else local
 
 
 def gather_rows(local: torch.Tensor, n_total: int, group=None) -> torch.Tensor:
@@ -126,9 +169,7 @@ def run_sharded(fn: Callable[..., torch.Tensor], inputs: Sequence[Optional[torch
     with its bounds, for consumers that keep the data distributed.
     """
     n = next(t.shape[0] for t in inputs if t is not None)
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    lo, hi = shard_bounds(n, world, rank)
+    _, _, lo, hi = _shard(n, group)
     local = fn(*[None if t is None else t[lo:hi].contiguous() for t in inputs])
     if not gather:
         return local, (lo, hi)
@@ -149,23 +190,15 @@ def sample_sde_sharded(score_model, shape, conditional: Optional[torch.Tensor] =
     batch, *dims = shape
     if len(dims) != 1:
         raise NotImplementedError("sample_sde_sharded: only [batch, dim] states are supported")
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    lo, hi = shard_bounds(batch, world, rank)
+    _, _, lo, hi = _shard(batch, group)
     dev = next(score_model.model.parameters()).device
     # the prior is Normal(0, scale) (diffusion.py:1003, 1093)
     sde = score_model.sde
     scale = float(sde.sigma_max) if hasattr(sde, "sigma_max") else 1.0
     x = _native.normal_fill(hi - lo, dims[0], int(seed), lo, dev, scale=scale)
-    cond = None if conditional is None else conditional[lo:hi].contiguous()
-    if local_conditional is not None:
-        if conditional is not None or local_conditional.shape[0] != hi - lo:
-            raise ValueError("local_conditional must hold exactly this rank's rows (and excludes `conditional`)")
-        cond = local_conditional.contiguous()
+    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
     local = score_model._sample_sde_from(x, None, cond, steps, rng=(int(seed), lo))
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, batch, group) if world > 1 else local
+    return _finish(local, batch, group, gather)
 
 
 def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,
@@ -183,33 +216,12 @@ def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional:
     torchdiffeq takes it (``global_step_control``: one small all-reduce per norm; every rank needs at least one row);
     results then agree across world sizes to the rounding of those norms.  ``global_control=False``: every rank
     controls its steps from its own rows (agreement to the solver tolerances only)."""
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    if (x is None) == (local_x is None):
-        raise ValueError("pass either the full batch `x` or this rank's rows `local_x` (with n_total)")
-    if x is not None:
-        n = x.shape[0]
-        lo, hi = shard_bounds(n, world, rank)
-        rows = x[lo:hi].contiguous()
-        if local_conditional is not None:
-            raise ValueError("local_conditional goes with local_x")
-        cond = None if conditional is None else conditional[lo:hi].contiguous()
-    else:
-        if n_total is None or conditional is not None:
-            raise ValueError("local_x needs n_total (and local_conditional instead of conditional)")
-        n = int(n_total)
-        lo, hi = shard_bounds(n, world, rank)
-        if local_x.shape[0] != hi - lo or (local_conditional is not None and local_conditional.shape[0] != hi - lo):
-            raise ValueError(f"rank {rank} of {world} owns rows [{lo}, {hi}) of {n}: local tensors must hold exactly those")
-        rows = local_x.contiguous()
-        cond = None if local_conditional is None else local_conditional.contiguous()
+    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     randomised = any(getattr(score_model, k, False) for k in ("hutch", "hutchpp", "xtrace"))
     extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if randomised else {}
-    with _step_control(n, world, group, global_control, solver.get("method", "dopri5")):
+    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
         local = score_model.log_prob(rows, conditional=cond, **solver, **extra)
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, n, group) if world > 1 else local
+    return _finish(local, n, group, gather)
 
 
 def sample_ode_sharded(score_model, n_total: int, dim: int, seed: int = 0, conditional: Optional[torch.Tensor] = None,
@@ -221,32 +233,17 @@ def sample_ode_sharded(score_model, n_total: int, dim: int, seed: int = 0, condi
     rtol, method, options) goes to ``sample_ode_from_base`` unchanged; with an adaptive method (the reference's default)
     and ``global_control`` the step size comes from the error norm of the whole batch (``global_step_control``)."""
     from . import _native
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    lo, hi = shard_bounds(int(n_total), world, rank)
+    n = int(n_total)
+    _, _, lo, hi = _shard(n, group)
     dev = next(score_model.model.parameters()).device
     z = _native.normal_fill(hi - lo, int(dim), int(seed), lo, dev)
-    cond = None if conditional is None else conditional[lo:hi].contiguous()
-    if local_conditional is not None:
-        if conditional is not None or local_conditional.shape[0] != hi - lo:
-            raise ValueError("local_conditional must hold exactly this rank's rows (and excludes `conditional`)")
-        cond = local_conditional.contiguous()
-    with _step_control(int(n_total), world, group, global_control, solver.get("method", "dopri5")):
+    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
+    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
         local, _ = score_model.sample_ode_from_base(z, conditional=cond, **solver)
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, int(n_total), group) if world > 1 else local
+    return _finish(local, n, group, gather)
 
 
 # ---- the flows (flowfusion/flow.py:259-306, 386-438; 750-799, 885-941) -- BASELINE configs[3] is worded "sharded over 8xMI355X"
-def _local_rows(full, local, lo, hi, what):
-    if local is not None:
-        if full is not None or local.shape[0] != hi - lo:
-            raise ValueError(f"local_{what} must hold exactly this rank's rows [{lo}, {hi}) (and excludes `{what}`)")
-        return local.contiguous()
-    return None if full is None else full[lo:hi].contiguous()
-
-
 def flow_sample_sharded(flow, n_total: int, seed: int = 0, conditional: Optional[torch.Tensor] = None, group=None,
                         gather: bool = True, local_conditional: Optional[torch.Tensor] = None, global_control: bool = True,
                         **solver):
@@ -260,19 +257,15 @@ def flow_sample_sharded(flow, n_total: int, seed: int = 0, conditional: Optional
     (``global_step_control``), ``global_control=False``: from the rank's own rows."""
     from . import _native
     from .flow import _DEFAULT_SAMPLE_METHOD
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
     n = int(n_total)
-    lo, hi = shard_bounds(n, world, rank)
+    _, _, lo, hi = _shard(n, group)
     dev = next(flow.parameters()).device
     xT = _native.normal_fill(hi - lo, int(flow.target_dimension), int(seed), lo, dev)
     cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
     method = solver.get("method") or _DEFAULT_SAMPLE_METHOD
-    with _step_control(n, world, group, global_control, method):
+    with _step_control(n, group, global_control, method):
         local = flow.sample(xT, **solver) if cond is None else flow.sample(xT, cond, **solver)
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, n, group) if world > 1 else local
+    return _finish(local, n, group, gather)
 
 
 def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None, seed: int = 0,
@@ -285,26 +278,11 @@ def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: O
     ``hutchinson=True`` the probe comes from the library's counter-based stream keyed by ``seed`` and the GLOBAL row
     (``probe="philox"``), so a row's result does not depend on the number of ranks; the exact trace (the reference's
     default, flow.py:158-161) needs no random numbers.  Step control as in ``flow_sample_sharded``."""
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    if (x is None) == (local_x is None):
-        raise ValueError("pass either the full batch `x` or this rank's rows `local_x` (with n_total)")
-    if x is None and n_total is None:
-        raise ValueError("local_x needs n_total")
-    n = int(x.shape[0] if x is not None else n_total)
-    lo, hi = shard_bounds(n, world, rank)
-    rows = _local_rows(x, local_x, lo, hi, "x")
-    if x is not None and local_conditional is not None:
-        raise ValueError("local_conditional goes with local_x")
-    if x is None and conditional is not None:
-        raise ValueError("local_x goes with local_conditional, not the full `conditional`")
-    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
+    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if solver.get("hutchinson") else {}
-    with _step_control(n, world, group, global_control, solver.get("method", "dopri5")):
+    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
         local = flow.log_prob(rows, **solver, **extra) if cond is None else flow.log_prob(rows, cond, **solver, **extra)
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, n, group) if world > 1 else local
+    return _finish(local, n, group, gather)
 
 
 # ---- the symplectic flows (flowfusion/symplectic.py:166-253) ------------------------------------------------------------------
@@ -322,19 +300,15 @@ def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: O
     fine.  ``conditional`` is the raw [n_total, C] tensor (every rank slices its rows) or ``local_conditional`` this
     rank's rows.  More than one rank over RCCL has not been run on hardware, like everything else multi-rank here."""
     from . import _native
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
     n = int(n_total)
-    lo, hi = shard_bounds(n, world, rank)
+    _, _, lo, hi = _shard(n, group)
     dev = next(model.model.parameters()).device
     # the joint state is [q | p]: 2 D columns (a model built without `shift` is asked for its networks' state width)
     dim = 2 * int(model.shift.numel()) if model.shift is not None else int(model._net().dim)
     x = _native.normal_fill(hi - lo, dim, int(seed), lo, dev)
     cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
     local = model._sample_from(x, cond, int(num_steps), **({} if method == "euler" else {"method": method}))
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, n, group) if world > 1 else local
+    return _finish(local, n, group, gather)
 
 
 def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,
@@ -357,24 +331,9 @@ def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditi
     the world size.  More than one rank over RCCL has
     not been run on hardware, like everything else multi-rank here."""
     from . import _native
-    world = dist.get_world_size(group) if dist.is_initialized() else 1
-    rank = dist.get_rank(group) if dist.is_initialized() else 0
-    if (x is None) == (local_x is None):
-        raise ValueError("pass either the full batch `x` or this rank's rows `local_x` (with n_total)")
-    if x is None and n_total is None:
-        raise ValueError("local_x needs n_total")
-    n = int(x.shape[0] if x is not None else n_total)
-    lo, hi = shard_bounds(n, world, rank)
-    rows = _local_rows(x, local_x, lo, hi, "x")
-    if x is not None and local_conditional is not None:
-        raise ValueError("local_conditional goes with local_x")
-    if x is None and conditional is not None:
-        raise ValueError("local_x goes with local_conditional, not the full `conditional`")
-    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
+    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     p0 = _native.normal_fill(hi - lo, int(rows.shape[1]), int(seed), lo, rows.device)
-    with _step_control(n, world, group, global_control, method):
+    with _step_control(n, group, global_control, method):
         local = model._log_prob_from(rows, p0, cond, atol, rtol, method=method,
                                      **({} if num_steps is None else {"num_steps": num_steps}))
-    if not gather:
-        return local, (lo, hi)
-    return gather_rows(local, n, group) if world > 1 else local
+    return _finish(local, n, group, gather)

@@ -14,7 +14,8 @@ import torch
 from torch import nn
 
 from . import _native
-from ._native import MODE_EXACT, MODE_HUTCH, MODE_STATE  # noqa: F401  (re-exported)
+from ._native import MODE_EXACT, MODE_HUTCH, MODE_STATE, f32_on  # noqa: F401  (modes re-exported)
+from .solvers import ROW_A, ROW_AUX_COEF, ROW_B, ROW_CIN, ROW_HDR, ROW_SLOT, ROW_USE_Y
 
 
 def activation_spec(act) -> Tuple[int, float, float]:
@@ -147,15 +148,16 @@ class FusedNet:
         vers = tuple((p.data_ptr(), p._version) for l in self.linears for p in (l.weight, l.bias))
         return (str(device), plan.precision, plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden), vers
 
+    def _pack(self, plan) -> torch.Tensor:
+        return _native.pack_weights(plan, [l.weight for l in self.linears], [l.bias for l in self.linears],
+                                    self.hidden, self.x_col0, self.c_col0)
+
     def wpack(self, device, mode: int) -> torch.Tensor:
         plan = self.plan(mode)
         layout, vers = self._param_key(device, plan)
         hit = self._wpack.get(layout)
         if hit is None or hit[0] != vers:
-            packed = _native.pack_weights(
-                plan, [l.weight for l in self.linears], [l.bias for l in self.linears],
-                self.hidden, self.x_col0, self.c_col0)
-            hit = (vers, packed.to(device))
+            hit = (vers, self._pack(plan).to(device))
             self._wpack[layout] = hit
         return hit[1]
 
@@ -177,17 +179,17 @@ class FusedNet:
             raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(x.shape)}")
         dev = x.device
         plan = self.plan(mode) if plan is None else plan
-        f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
         if self.cond_dim > 0:
             if cond is None:
                 raise ValueError("this network has conditional inputs; `conditional` is required")
-            cond = f32(cond)
+            cond = f32_on(cond, dev)
             if cond.dim() != 2 or cond.shape != (x.shape[0], self.cond_dim):
                 raise ValueError(f"conditional must be [batch, {self.cond_dim}], got {tuple(cond.shape)}")
         else:
             cond = None
-        args = (f32(x), cond, f32(probe), f32(noise), self.wpack(dev, mode), f32(etab),
-                f32(in_shift), f32(in_scale), f32(out_scale), f32(out_shift), _native.plan_words(plan, stage_slots), mode)
+        args = (f32_on(x, dev), cond, f32_on(probe, dev), f32_on(noise, dev), self.wpack(dev, mode), f32_on(etab, dev),
+                f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+                _native.plan_words(plan, stage_slots), mode)
         if rng is not None:
             if mode != MODE_STATE or noise is not None:
                 raise ValueError("in-kernel noise applies to state-only integration without a noise buffer")
@@ -224,9 +226,8 @@ class FusedNet:
         the CPU tests (kernel-semantics emulator)."""
         plan = self.plan(mode)
         width = self.width(mode)        # first-layer bias words per row (two networks' worth on a pair plan)
-        f32 = lambda t: None if t is None else t.detach().to(device, torch.float32).contiguous()
-        cond_d = f32(cond) if self.cond_dim > 0 else None
-        probe_d = f32(probe)
+        cond_d = f32_on(cond, device) if self.cond_dim > 0 else None
+        probe_d = f32_on(probe, device)
         own = launcher is None
         if own:
             wpack = self.wpack(device, mode)
@@ -240,16 +241,16 @@ class FusedNet:
             self.require_slots(used, mode, "this adaptive method")
             hint = {"used": used} if own else {}
             a, b, c1 = schedule(sign * t_rows)
-            rows = torch.zeros(n + 2, 32 + width, dtype=torch.float32)
-            rows[:n, 0] = sign * a
-            rows[:n, 1] = sign * b
+            rows = torch.zeros(n + 2, ROW_HDR + width, dtype=torch.float32)
+            rows[:n, ROW_A] = sign * a
+            rows[:n, ROW_B] = sign * b
             ints = rows.view(torch.int32)
-            ints[:n, 4] = slots
-            rows[:n, 8:16] = cin
-            rows[:n, 32:32 + c1.shape[1]] = c1
-            rows[n, 8:16], rows[n, 16:24] = tail[0], tail[1]
-            rows[n + 1, 8:16], rows[n + 1, 16:24] = tail[2], tail[3]
-            ints[n, 3] = use_y
+            ints[:n, ROW_SLOT] = slots
+            rows[:n, ROW_CIN] = cin
+            rows[:n, ROW_HDR:ROW_HDR + c1.shape[1]] = c1
+            rows[n, ROW_CIN], rows[n, ROW_AUX_COEF] = tail[0], tail[1]
+            rows[n + 1, ROW_CIN], rows[n + 1, ROW_AUX_COEF] = tail[2], tail[3]
+            ints[n, ROW_USE_Y] = use_y
             aux = aux_lp = None
             for i, (first, count) in enumerate(passes):
                 o, olp = launcher(y, k1, kl1 if i == 0 else None, lp0 if i == 0 else None, rows, n_aux, first, count, **hint)
@@ -339,15 +340,8 @@ class FusedPair(FusedNet):
         vers = tuple((p.data_ptr(), p._version) for l in self.linears + self.p_linears for p in (l.weight, l.bias))
         return (str(device), plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden), vers
 
-    def wpack(self, device, mode: int) -> torch.Tensor:
-        plan = self.plan(mode)
-        layout, vers = self._param_key(device, plan)
-        hit = self._wpack.get(layout)
-        if hit is None or hit[0] != vers:
-            packed = _native.pack_pair_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
-            hit = (vers, packed.to(device))
-            self._wpack[layout] = hit
-        return hit[1]
+    def _pack(self, plan) -> torch.Tensor:
+        return _native.pack_pair_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
 
     def cached_table(self, key, device, build):
         q0, p0 = self.linears[0], self.p_linears[0]

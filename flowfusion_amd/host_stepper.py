@@ -17,9 +17,9 @@ from typing import Callable, Optional
 import torch
 
 from . import _native
-from ._native import MODE_EXACT
+from ._native import MODE_EXACT, f32_on
 from .fused import FusedNet, exact_trace_passes
-from .solvers import FLAG_STEP_END, MAX_SLOTS, ROW_HDR
+from .solvers import FLAG_STEP_END, MAX_SLOTS, ROW_A, ROW_B, ROW_CIN, ROW_COUT, ROW_FLAGS, ROW_HDR, ROW_SLOT
 
 
 class RowStepper:
@@ -33,8 +33,7 @@ class RowStepper:
         plan = net.plan(MODE_EXACT)
         self.width = int(plan.width)
         self.passes = exact_trace_passes(net.dim, plan.tile)
-        f32 = lambda t: None if t is None else t.detach().to(device, torch.float32).contiguous()
-        cond_d = f32(cond) if net.cond_dim > 0 else None
+        cond_d = f32_on(cond, device) if net.cond_dim > 0 else None
         if launcher is None:
             words = _native.plan_words(plan)
             wpack = net.wpack(device, MODE_EXACT)
@@ -46,9 +45,9 @@ class RowStepper:
     def rhs_div(self, y: torch.Tensor, a: float, b: float, c1: torch.Tensor):
         """(rhs [B, D], divergence estimate [B]) of  a*y + b*NET(y; c1)."""
         rows = torch.zeros(3, ROW_HDR + self.width, dtype=torch.float32)
-        rows[0, 0], rows[0, 1] = a, b
+        rows[0, ROW_A], rows[0, ROW_B] = a, b
         rows[0, ROW_HDR:ROW_HDR + c1.numel()] = c1
-        rows[1, 8] = 1.0                               # auxiliary output 0 = stage slot 0 = the right-hand side
+        rows[1, ROW_CIN.start] = 1.0                       # auxiliary output 0 = stage slot 0 = the right-hand side
         y = y.contiguous()
         jac = torch.empty(y.shape[0], self.net.dim, self.net.dim, dtype=torch.float32, device=y.device)
         rhs = None
@@ -64,14 +63,14 @@ class RowStepper:
         kl = [torch.zeros(x.shape[0], device=x.device) for _ in range(MAX_SLOTS)]
         lp = torch.zeros(x.shape[0], device=x.device)
         for e in range(table.shape[0]):
-            cin, cout = table[e, 8:8 + MAX_SLOTS], table[e, 16:16 + MAX_SLOTS]
+            cin, cout = table[e, ROW_CIN], table[e, ROW_COUT]
             y = x.clone()
             for s in range(MAX_SLOTS):
                 if float(cin[s]) != 0.0:
                     y = y + float(cin[s]) * ks[s]
-            slot = int(ints[e, 4])
-            ks[slot], kl[slot] = self.rhs_div(y, float(table[e, 0]), float(table[e, 1]), table[e, ROW_HDR:])
-            if int(ints[e, 3]) & FLAG_STEP_END:
+            slot = int(ints[e, ROW_SLOT])
+            ks[slot], kl[slot] = self.rhs_div(y, float(table[e, ROW_A]), float(table[e, ROW_B]), table[e, ROW_HDR:])
+            if int(ints[e, ROW_FLAGS]) & FLAG_STEP_END:
                 for s in range(MAX_SLOTS):
                     if float(cout[s]) != 0.0:
                         x = x + float(cout[s]) * ks[s]
@@ -90,10 +89,10 @@ class RowStepper:
         w = torch.zeros(n, dtype=torch.float64)
         owner = {}
         for e in range(n):
-            owner[int(ints[e, 4])] = e
-            if int(ints[e, 3]) & FLAG_STEP_END:
+            owner[int(ints[e, ROW_SLOT])] = e
+            if int(ints[e, ROW_FLAGS]) & FLAG_STEP_END:
                 for s in range(MAX_SLOTS):
-                    c = float(table[e, 16 + s])
+                    c = float(table[e, ROW_COUT][s])
                     if c != 0.0 and s in owner:
                         w[owner[s]] += c
         w = w.to(torch.float32).to(x.device)
@@ -102,8 +101,7 @@ class RowStepper:
         words = _native.plan_words(plan)
         wpack = self.net.wpack(dev, MODE_EXACT)
         tab = table.to(dev)
-        f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()
-        cond_d = f32(cond) if self.net.cond_dim > 0 else None
+        cond_d = f32_on(cond, dev) if self.net.cond_dim > 0 else None
         chunk = max(1, min(B, max_bytes // max(1, n * D * D * 4)))
         outs, lps = [], []
         for lo in range(0, B, chunk):

@@ -48,6 +48,12 @@ MAX_SLOTS = 7         # stage slots on chip (FF_MAX_SLOTS)
 FLAG_STEP_END = 1
 FLAG_NOISE = 2
 FLAG_NET_B = 4        # select plans: the row runs net B (FF_ROW_NET_B)
+# word of each field in the row header: ff::RowHdr in csrc/ff_layout.h (what csrc/ff_kernel_args.h's `etab` points at)
+ROW_A, ROW_B, ROW_GN, ROW_FLAGS, ROW_SLOT, ROW_NOISE_IDX = 0, 1, 2, 3, 4, 5
+ROW_CIN, ROW_COUT = slice(8, 16), slice(16, 24)
+# the two auxiliary rows behind an attempt's evaluation rows (ff_ode_args in include/flowfusion_amd.h): coef_0 / coef_2 in
+# their cin words, coef_1 / coef_3 in their cout words, the use_y bits in the flags word of the first
+ROW_AUX_COEF, ROW_USE_Y = ROW_COUT, ROW_FLAGS
 
 _one_third = 1.0 / 3.0
 _two_thirds = 2.0 / 3.0
@@ -261,17 +267,17 @@ def build_table(plan: EvalPlan, a: torch.Tensor, b: torch.Tensor, c1: torch.Tens
     """
     n = plan.t_eval.numel()
     rows = torch.zeros(n, ROW_HDR + width, dtype=torch.float32)
-    rows[:, 0] = plan.sign * a.to(torch.float32)
-    rows[:, 1] = plan.sign * b.to(torch.float32)
+    rows[:, ROW_A] = plan.sign * a.to(torch.float32)
+    rows[:, ROW_B] = plan.sign * b.to(torch.float32)
     if gn is not None:
-        rows[:, 2] = gn
+        rows[:, ROW_GN] = gn
     iview = rows.view(torch.int32)
-    iview[:, 3] = plan.flags
-    iview[:, 4] = plan.slot
+    iview[:, ROW_FLAGS] = plan.flags
+    iview[:, ROW_SLOT] = plan.slot
     if noise_idx is not None:
-        iview[:, 5] = noise_idx.to(torch.int32)
-    rows[:, 8:16] = plan.cin
-    rows[:, 16:24] = plan.cout
+        iview[:, ROW_NOISE_IDX] = noise_idx.to(torch.int32)
+    rows[:, ROW_CIN] = plan.cin
+    rows[:, ROW_COUT] = plan.cout
     rows[:, ROW_HDR:ROW_HDR + c1.shape[1]] = c1.to(torch.float32)
     return rows
 
