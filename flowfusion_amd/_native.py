@@ -178,6 +178,8 @@ NORM_TERMS = 3                      # FF_NORM_TERMS
 PRIOR_NOISE_INDEX = 0xFFFFFFFF     # FF_PRIOR_NOISE_INDEX
 PROBE_NOISE_INDEX = 0xFFFFFFFE     # FF_PROBE_NOISE_INDEX
 TRACE_PROBE_NOISE_BASE = 0xFFFE0000  # FF_TRACE_PROBE_NOISE_BASE (second probe set: + 0x8000)
+MOMENTUM_NOISE_BASE = 0xFFFD0000   # FF_MOMENTUM_NOISE_BASE (+ k: momentum k of a data point, ff_marginal_expand / _reduce)
+MAX_MOMENTA = 4096                 # 1 <= K <= 4096
 
 _lib = None
 
@@ -249,6 +251,14 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
                                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.ff_stage_combine.restype = ctypes.c_int
     L.ff_stage_combine.argtypes = [ctypes.POINTER(CombineArgs), ctypes.c_void_p]
+    expand = [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    reduce = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64,
+              ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_marginal_expand.restype = L.ff_marginal_expand_host.restype = ctypes.c_int
+    L.ff_marginal_reduce.restype = L.ff_marginal_reduce_host.restype = ctypes.c_int
+    L.ff_marginal_expand.argtypes, L.ff_marginal_expand_host.argtypes = expand + [ctypes.c_void_p], expand
+    L.ff_marginal_reduce.argtypes, L.ff_marginal_reduce_host.argtypes = reduce + [ctypes.c_void_p], reduce
     L.ff_mlp_ode_adaptive.restype = ctypes.c_int
     L.ff_mlp_ode_adaptive.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.POINTER(AdaptConfig),
                                       ctypes.POINTER(AdaptBuffers), ctypes.c_double, ctypes.c_double, ctypes.c_int32,
@@ -453,6 +463,74 @@ def stage_combine(out: torch.Tensor, x: Optional[torch.Tensor], ks, coefs, x_coe
         rc = lib().ff_stage_combine(ctypes.byref(a), ctypes.c_void_p(stream))
     if rc != FF_OK:
         raise _err(rc, "ff_stage_combine")
+    return out
+
+
+def _on_stream(dev, device_fn, host_fn, args):
+    """One call of a kernel entry point on torch's current stream of ``dev``, or of its host twin for CPU tensors."""
+    if dev.type != "cuda":
+        return host_fn(*args)
+    with torch.cuda.device(dev):
+        return device_fn(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
+
+def marginal_expand(x: torch.Tensor, num_momenta: int, seed: int, sample_offset: int = 0,
+                    shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                    cond: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """ff_marginal_expand: (z0 [B K, 2 D], cond_out [B K, C] or None) from ``x`` [B, D]: row r K + k is
+    [(x[r] - shift) / scale | momentum k of global row sample_offset + r] and the (already normalised) ``cond[r]``.
+    Device tensors on the current stream; CPU tensors go to ff_marginal_expand_host."""
+    dev = x.device
+    B, D = x.shape
+    K = int(num_momenta)
+    if not 1 <= K <= MAX_MOMENTA:
+        raise ValueError(f"num_momenta={num_momenta}: 1 .. {MAX_MOMENTA} momentum draws per data point")
+    for t, name in ((shift, "shift"), (scale, "scale")):
+        if t is not None and t.numel() != D:
+            raise RuntimeError(f"marginal_expand: {name} has {t.numel()} elements, x has {D} columns")
+    if cond is not None and (cond.dim() != 2 or cond.shape[0] != B or cond.shape[1] < 1):
+        raise RuntimeError(f"marginal_expand: cond has shape {tuple(cond.shape)}, expected [{B}, C >= 1]")
+    C = 0 if cond is None else int(cond.shape[1])
+    z0 = torch.empty(B * K, 2 * D, dtype=torch.float32, device=dev)
+    cond_out = None if cond is None else torch.empty(B * K, C, dtype=torch.float32, device=dev)
+    if B == 0:
+        return z0, cond_out
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_expand, L.ff_marginal_expand_host,
+                    (_chk(x, "x", dev), _chk(shift, "shift", dev), _chk(scale, "scale", dev), _chk(cond, "cond", dev), B, D, C, K,
+                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), z0.data_ptr(), 0 if cond is None else cond_out.data_ptr()))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_expand")
+    return z0, cond_out
+
+
+def marginal_reduce(z1: torch.Tensor, num_momenta: int, seed: int, sample_offset: int = 0, log_det: float = 0.0,
+                    out: Optional[torch.Tensor] = None, ess: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ff_marginal_reduce: ``out`` [B] = logsumexp over the K rows of a data point of log N(z1) - log N(p0), - log K -
+    log_det, from ``z1`` [B K, 2 D] (the solution from ``marginal_expand``'s z0; p0 regenerated from ``seed`` and
+    ``sample_offset``); ``ess`` [B], if given, takes the effective sample size.  ``out`` is allocated if None.  Device
+    tensors on the current stream; CPU tensors go to ff_marginal_reduce_host."""
+    dev = z1.device
+    K = int(num_momenta)
+    if not 1 <= K <= MAX_MOMENTA:
+        raise ValueError(f"num_momenta={num_momenta}: 1 .. {MAX_MOMENTA} momentum draws per data point")
+    rows, D2 = z1.shape
+    if rows % K or D2 % 2 or D2 < 2:
+        raise RuntimeError(f"marginal_reduce: z1 has shape {tuple(z1.shape)}, expected [B * {K}, 2 D]")
+    B = rows // K
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    for t, name in ((out, "out"), (ess, "ess")):
+        if t is not None and t.numel() != B:
+            raise RuntimeError(f"marginal_reduce: {name} has {t.numel()} elements for {B} data points")
+    if B == 0:
+        return out
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_reduce, L.ff_marginal_reduce_host,
+                    (_chk(z1, "z1", dev), B, D2 // 2, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), float(log_det),
+                     _chk(out, "out", dev), _chk(ess, "ess", dev)))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_reduce")
     return out
 
 

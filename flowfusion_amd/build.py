@@ -295,6 +295,7 @@ const int g_n_pair_kernels = {len(PAIR_INSTANCES)};
     files.append(CSRC / "ff_aux.hip")
     files.append(CSRC / "ff_adaptive.hip")
     files.append(CSRC / "ff_trace.hip")
+    files.append(CSRC / "ff_marginal.hip")
     return files
 
 

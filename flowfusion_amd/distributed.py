@@ -315,7 +315,8 @@ def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditi
                                 seed: int = 0, group=None, gather: bool = True, local_x: Optional[torch.Tensor] = None,
                                 n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None,
                                 global_control: bool = True, atol: float = 1e-5, rtol: float = 1e-5,
-                                method: str = "dopri5", num_steps: Optional[int] = None):
+                                method: str = "dopri5", num_steps: Optional[int] = None,
+                                num_momenta: Optional[int] = None, return_ess: bool = False):
     """``SymplecticFlowModel.log_prob`` of a [B, D] batch over all ranks; one all-gather of the [B] result at the end.
     ``x`` (and ``conditional``) are the full tensors, every rank slicing its rows -- or ``local_x`` (and
     ``local_conditional``) this rank's rows already, with ``n_total`` the size of the whole batch.  The momentum draw
@@ -328,10 +329,24 @@ def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditi
     ``global_control=False``: every rank steps from its own rows and enters no exchange.  ``method="leapfrog"`` with
     ``num_steps``: the fixed flipped grid of ``sample(.., method="leapfrog")`` in one launch per rank -- no collective but the
     final gather, ``global_control`` is ignored, ranks without rows are fine and a row's result is bitwise independent of
-    the world size.  More than one rank over RCCL has
+    the world size.  ``num_momenta=K`` (an integer): the marginal over K momentum draws per data point instead
+    (``SymplecticFlowModel.log_prob_marginal`` with this ``seed`` and ``sample_offset`` = the rank's first row; the momenta
+    are keyed by the global row under noise indices of their own), with ``return_ess=True`` the gathered
+    ``(log_p, ess)``; step control and the leapfrog invariance as above.  More than one rank over RCCL has
     not been run on hardware, like everything else multi-rank here."""
     from . import _native
     n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
+    if num_momenta is not None:
+        with _step_control(n, group, global_control, method):
+            local = model.log_prob_marginal(rows, cond, int(num_momenta), atol, rtol, method=method, num_steps=num_steps,
+                                            seed=int(seed), sample_offset=lo, return_ess=return_ess)
+        if not return_ess:
+            return _finish(local, n, group, gather)
+        if not gather:
+            return tuple(local), (lo, hi)
+        return tuple(_finish(t, n, group, True) for t in local)
+    if return_ess:
+        raise ValueError("return_ess goes with num_momenta (the one-draw estimate has no weights to count)")
     p0 = _native.normal_fill(hi - lo, int(rows.shape[1]), int(seed), lo, rows.device)
     with _step_control(n, group, global_control, method):
         local = model._log_prob_from(rows, p0, cond, atol, rtol, method=method,

@@ -13,7 +13,10 @@ grid (one fused launch); ``log_prob`` is adaptive dopri5 on the device controlle
 ``method="leapfrog"`` of ``_sample_from`` / ``_log_prob_from`` / ``_integrate``) integrate the same grid with
 kick-drift-kick leapfrog on the row-select kernel: every sub-step moves one half of the state under the network that reads
 the other half, so the discrete map preserves volume and ``log_prob_leapfrog(x, num_steps=n)`` -- the flipped grid, one
-launch, no step controller -- is the exact density of what ``sample_leapfrog(shape, num_steps=n)`` applies.  Networks outside the compiled pair
+launch, no step controller -- is the exact density of what ``sample_leapfrog(shape, num_steps=n)`` applies.
+``log_prob_marginal`` (extension) averages the importance weights of K momentum draws per data point -- the marginal over
+the momentum that ``log_prob`` estimates from one draw -- with a streaming kernel at each end of the solve
+(csrc/ff_marginal.hip).  Networks outside the compiled pair
 shapes, non-SiLU activations and any other ``model`` with the same ``forward(t, state, conditional)`` are evaluated by
 torch with the stepping in the library (generic.py; ``FusedEnvelopeWarning`` for the first two).  GPU only: CPU tensors
 raise.  The reference draws a tqdm progress bar in ``sample``; this module does not.
@@ -156,12 +159,7 @@ class SymplecticFlowModel(nn.Module):
         q, _ = torch.chunk(x, 2, dim=-1)
         return q * self.scale + self.shift
 
-    @torch.no_grad()
-    def _log_prob_from(self, x, p0, conditional=None, atol=1e-5, rtol=1e-5, method="dopri5", options=None, *,
-                       num_steps=None):
-        """``log_prob`` with the momentum draw ``p0`` supplied; ``method`` / ``options`` as torchdiffeq takes them (the
-        reference always runs its default, dopri5), or ``method="leapfrog"`` with ``num_steps``: the flipped grid of
-        ``sample``, no tolerances."""
+    def _check_log_prob_method(self, method, num_steps):
         if method == "leapfrog":
             if num_steps is None or int(num_steps) < 1:
                 raise ValueError("method='leapfrog' needs num_steps >= 1 (the steps of the sample it inverts)")
@@ -170,19 +168,92 @@ class SymplecticFlowModel(nn.Module):
         elif method not in solvers.FIXED_METHODS and method not in solvers.ADAPTIVE_METHODS:
             raise ValueError(f"method={method!r}: log_prob takes 'dopri5' (the default), 'leapfrog' with num_steps, or another "
                              f"torchdiffeq method ({sorted(solvers.FIXED_METHODS)}, {solvers.ALL_ADAPTIVE})")
+
+    def _solve_forward(self, z0, conditional_normalised, atol, rtol, method, options, num_steps):
+        """z1 [B, 2D]: the solve of ``log_prob`` over t: 0 -> 1 from ``z0`` (``method`` already checked): the flipped grid
+        of ``sample`` under leapfrog, ``odeint.solve`` on t_span = [0, 1] otherwise."""
+        if method == "leapfrog":
+            grid = torch.linspace(1.0, 0.0, int(num_steps) + 1).flip(0)
+            return self._integrate(z0, grid, conditional_normalised, "leapfrog")
+        t_span = torch.tensor([0.0, 1.0])
+        z1, _ = odeint.solve(self, z0, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional_normalised)
+        return z1
+
+    @torch.no_grad()
+    def _log_prob_from(self, x, p0, conditional=None, atol=1e-5, rtol=1e-5, method="dopri5", options=None, *,
+                       num_steps=None):
+        """``log_prob`` with the momentum draw ``p0`` supplied; ``method`` / ``options`` as torchdiffeq takes them (the
+        reference always runs its default, dopri5), or ``method="leapfrog"`` with ``num_steps``: the flipped grid of
+        ``sample``, no tolerances."""
+        self._check_log_prob_method(method, num_steps)
         q0 = (x - self.shift) / self.scale
         conditional = self._norm_cond(conditional)
         z0 = torch.cat([q0, p0], dim=-1)
-        if method == "leapfrog":
-            grid = torch.linspace(1.0, 0.0, int(num_steps) + 1).flip(0)
-            z1 = self._integrate(z0, grid, conditional, "leapfrog")
-        else:
-            t_span = torch.tensor([0.0, 1.0])
-            z1, _ = odeint.solve(self, z0, t_span, method, options, MODE_STATE, atol, rtol, cond=conditional)
+        z1 = self._solve_forward(z0, conditional, atol, rtol, method, options, num_steps)
         normal = torch.distributions.Normal(0, 1)
         log_p_z1 = normal.log_prob(z1).sum(dim=-1)
         log_p_p0 = normal.log_prob(p0).sum(dim=-1)
         return log_p_z1 - log_p_p0 - torch.sum(torch.log(self.scale))
+
+    # -- extension: the marginal over K momentum draws ------------------------------------------------------------------
+    MARGINAL_CHUNK_ROWS = 1 << 22        # rows (data points x momenta) in flight by default on a fixed grid
+
+    @torch.no_grad()
+    def log_prob_marginal(self, x, conditional=None, num_momenta=16, atol=1e-5, rtol=1e-5, *, method="dopri5",
+                          num_steps=None, options=None, seed=None, sample_offset=0, chunk_points=None, return_ess=False):
+        """The data log-density as the marginal over the momentum, from ``num_momenta`` = K draws per point.
+
+        The flow preserves volume in [q | p], so p(q0) = E_{p0 ~ N}[N(z1(q0, p0)) / N(p0)]; ``log_prob`` returns the
+        one-draw estimate of it in log space (a different value on every call), this returns
+        ``logsumexp_k(log N(z1_k) - log N(p0_k)) - log K - sum log scale`` [B]: ff_marginal_expand writes the K starting
+        states of every point, the solve of ``log_prob`` (``method`` / ``num_steps`` / ``options`` / ``atol`` / ``rtol`` as
+        in ``_log_prob_from``; compiled shapes and the module route alike) runs on the B K rows, ff_marginal_reduce
+        combines them in double.  The momenta come from the library's counter-based stream keyed by ``seed`` and the global
+        row ``sample_offset + r`` (noise indices FF_MOMENTUM_NOISE_BASE + k): an explicit ``seed`` makes the call
+        reproducible, ``seed=None`` draws a 63-bit one from torch's default generator (``torch.manual_seed`` governs it).
+        ``return_ess=True`` returns ``(log_p, ess)``, ess [B] the effective sample size of the K weights, in (0, K].
+
+        Memory: on a fixed grid (``method="leapfrog"`` or a fixed-grid torchdiffeq method) the points are processed in
+        chunks of ``chunk_points`` (default: ``chunk_points * K <= 2**22`` rows), each expand -> solve -> reduce into the
+        one output; rows do not depend on the batch they sit in, so the result is bitwise independent of ``chunk_points``
+        (and of a sharding that passes ``sample_offset`` = its first row).  An adaptive method controls its step from the
+        whole batch it is handed: all B K rows are one solve, and ``chunk_points`` raises."""
+        K = int(num_momenta)
+        if not 1 <= K <= _native.MAX_MOMENTA:
+            raise ValueError(f"num_momenta={num_momenta}: 1 .. {_native.MAX_MOMENTA} momentum draws per data point")
+        self._check_log_prob_method(method, num_steps)
+        B = int(x.shape[0])
+        if method != "leapfrog" and method not in solvers.FIXED_METHODS:
+            if chunk_points is not None:
+                raise ValueError(f"chunk_points with method={method!r}: an adaptive solve takes its step size from the error "
+                                 "norm of the whole batch, so chunks would change every row's steps; all B * num_momenta rows "
+                                 "are one solve.  method='leapfrog' with num_steps (a fixed grid) processes chunks with "
+                                 "bitwise the same result")
+            chunk = max(B, 1)
+        elif chunk_points is None:
+            chunk = max(1, self.MARGINAL_CHUNK_ROWS // K)
+        else:
+            chunk = int(chunk_points)
+            if chunk < 1:
+                raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed, first = int(seed), int(sample_offset)
+        x = x.contiguous()
+        cond = self._norm_cond(conditional)
+        cond = None if cond is None else cond.contiguous()
+        log_det = 0.0 if self.scale is None else float(torch.log(self.scale.double()).sum())
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+        ess = torch.empty(B, dtype=torch.float32, device=x.device) if return_ess else None
+        for lo in range(0, B, chunk):
+            hi = min(B, lo + chunk)
+            z0, ck = _native.marginal_expand(x[lo:hi], K, seed, first + lo, self.shift, self.scale,
+                                             None if cond is None else cond[lo:hi])
+            z1 = self._solve_forward(z0, ck, atol, rtol, method, options, num_steps)
+            del z0
+            _native.marginal_reduce(z1, K, seed, first + lo, log_det, out[lo:hi], None if ess is None else ess[lo:hi])
+            del z1
+        return (out, ess) if return_ess else out
 
     # -- what odeint.solve asks of a front end -------------------------------------------------------
     def _layers(self):

@@ -338,6 +338,11 @@ int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidd
  * FF_TRACE_PROBE_NOISE_BASE + c, d), probe c of the SECOND set (G) that of index FF_TRACE_PROBE_NOISE_BASE + 0x8000 + c
  * (host side: probe="philox" on a model with hutchpp=True / xtrace=True) -- the same probes whatever the sharding. */
 #define FF_TRACE_PROBE_NOISE_BASE 0xFFFE0000u
+/* Noise indices reserved for the K momentum draws of a data point in the marginal log-density of the symplectic flows
+ * (ff_marginal_expand / ff_marginal_reduce below): momentum k of global row g is z(seed, g, FF_MOMENTUM_NOISE_BASE + k, d),
+ * k < 4096 -- a range of its own below the trace probes', so a seed shared with the prior draw or a probe set gives
+ * unrelated momenta. */
+#define FF_MOMENTUM_NOISE_BASE 0xFFFD0000u
 
 /*
  * out[r][d] = scale * z(seed, global row sample_offset + r, noise_index, d)  for r < batch, d < dim, with z the
@@ -392,6 +397,44 @@ typedef struct ff_norm_term {
 size_t ff_scaled_rms_workspace_bytes(void);
 int ff_scaled_rms(const ff_norm_term* terms, int32_t n_terms, float atol, float rtol, const float* check,
                   int64_t n_check, float* out, void* workspace, void* hip_stream);
+
+/* ---- marginal log-density of a symplectic flow over K momentum draws (csrc/ff_marginal.hip, csrc/ff_marginal.h) ----
+ *
+ * SymplecticFlowModel.log_prob (flowfusion/symplectic.py:204-253) draws ONE momentum p0 per data point and returns
+ * log N(z1) - log N(p0) - sum log scale, z1 the solution from [q0 | p0].  The flow preserves volume in the joint space,
+ * so the data density is the marginal p(q0) = E_{p0 ~ N}[N(Phi(q0, p0)) / N(p0)] and the reference's value a one-draw
+ * estimate of it.  These two kernels are the ends of the K-draw estimate, around any state-only solve of the B K rows:
+ * data point r, momentum k is row r K + k (the K rows of a point are contiguous), 1 <= K <= 4096.
+ *
+ * ff_marginal_expand:   z0[r K + k][0 : D]   = (x[r] - shift) / scale      fp32 subtraction, correctly rounded division
+ *                       z0[r K + k][D : 2 D] = z(seed, sample_offset + r, FF_MOMENTUM_NOISE_BASE + k, d)
+ *                       cond_out[r K + k]    = cond[r]
+ *   x [B][D]; shift, scale [D] or NULL (0 and 1); cond [B][C], already normalised, or NULL (C and cond_out are then
+ *   ignored); z0 [B K][2 D]; cond_out [B K][C].  The momenta are bit for bit what ff_normal_fill writes for that noise
+ *   index and global row.
+ * ff_marginal_reduce:   lw_k       = -1/2 (sum_{2D} z1[r K + k]^2 - sum_D p0(r, k)^2) - (D / 2) log 2 pi
+ *                       out_logp[r] = logsumexp_k lw_k - log K - log_det
+ *                       out_ess[r]  = (sum_k w_k)^2 / sum_k w_k^2,   w_k = exp(lw_k - max_k lw_k)
+ *   z1 [B K][2 D]; out_logp [B]; out_ess [B] or NULL; log_det = sum log scale.  p0 is regenerated from the stream (pass
+ *   the seed and sample_offset of the expand), neither stored nor read back.  The sums and the log-sum-exp run in double
+ *   and are rounded to fp32 once.  Non-finite input follows torch.logsumexp in float64: a NaN in any lw_k gives NaN,
+ *   all -inf gives -inf (and an effective sample size of NaN: no draw has weight).
+ * A data point's results do not depend on B, on its position in the batch or on the launch geometry, so a batch may be
+ * processed in chunks (sample_offset + first point of the chunk) or sharded over ranks with bitwise the same results.
+ * All pointers are DEVICE pointers; both enqueue on hip_stream; B == 0 is FF_OK without a launch.  The _host twins run
+ * the same arithmetic (csrc/ff_marginal.h) on HOST pointers for tests without a GPU: their normals come through libm
+ * and agree with the device's to rounding, not bit for bit; the two host functions are consistent with each other.
+ */
+int ff_marginal_expand(const float* x, const float* shift, const float* scale, const float* cond, int64_t B, int32_t D,
+                       int32_t C, int32_t K, uint64_t seed, int64_t sample_offset, float* z0, float* cond_out,
+                       void* hip_stream);
+int ff_marginal_reduce(const float* z1, int64_t B, int32_t D, int32_t K, uint64_t seed, int64_t sample_offset,
+                       double log_det, float* out_logp, float* out_ess, void* hip_stream);
+int ff_marginal_expand_host(const float* x, const float* shift, const float* scale, const float* cond, int64_t B,
+                            int32_t D, int32_t C, int32_t K, uint64_t seed, int64_t sample_offset, float* z0,
+                            float* cond_out);
+int ff_marginal_reduce_host(const float* z1, int64_t B, int32_t D, int32_t K, uint64_t seed, int64_t sample_offset,
+                            double log_det, float* out_logp, float* out_ess);
 
 /* ---- Hutch++ / XTrace divergence estimates from recorded Jacobians (csrc/ff_trace.hip, csrc/ff_trace_est.h) ----
  *
