@@ -418,6 +418,12 @@ FF_HD constexpr int act_group_at(const LayerGeom& L, int phys, int gpb, int M, i
     return blk <= L.NOB - 2 ? blk * gpb + gi : -1;
 }
 
+} // namespace ff
+
+#include "ff_ode_frame.hpp"      // the pieces this kernel shares with mlp_pair_kernel
+
+namespace ff {
+
 // COOP (small batches): the four wavefronts of a workgroup share ONE tile of TILE columns and split every hidden layer's
 // output rows between them (NB / 4 logical blocks each), exchanging the activations through LDS after each layer --
 // one evaluation then takes about a third of a lone wavefront's time, which is what counts when the batch is too small
@@ -445,7 +451,6 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     constexpr int K1 = DREGS + CREGS;
     constexpr int KH = NB * RB;                      // operand registers of a hidden layer
     constexpr int R4 = DREGS / 4;
-    typedef const __attribute__((address_space(4))) RowHdr* HdrPtr;   // scalar (SMEM) loads
 
     // launches enqueued ahead of a device-side decision (the adaptive driver, ff_adaptive.hip): a cleared gate word makes
     // this launch a no-op -- uniform over the grid, read before any barrier
@@ -460,7 +465,6 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     const long long wave = COOP ? (long long)blockIdx.x : (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wavefront of the workgroup
     const int D = args.dim;
-    const int C = args.cond_dim;
     const ActSpec aspec = {args.act_p0, args.act_p1, (ACT == 6 || ACT == kActAny) ? 1.0f / args.act_p0 : 0.f, args.act_kind};
 
     // ---- column roles -----------------------------------------------------------------
@@ -487,29 +491,11 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     // ---- load state (value columns) / tangent vectors -----------------------------------
     float x[DREGS];
 #pragma unroll
-    for (int r = 0; r < DREGS; ++r) {
-        const int d = feat_of_reg(TILE, r, qd);
-        float v = 0.f;
-        if (d < D) {
-            if (!is_tangent) {
-                v = args.x_in[sample * D + d];
-                if (args.in_shift) v = v - args.in_shift[d];
-                if (args.in_scale) v = v / args.in_scale[d];
-            } else if (args.unit_tangents) {
-                v = (d == args.tangent_first + role - 1) ? 1.0f : 0.0f;
-            } else {
-                v = args.probe[sample * D + d];
-            }
-        }
-        x[r] = v;
-    }
+    for (int r = 0; r < DREGS; ++r) x[r] = state_reg<TILE>(args, sample, qd, is_tangent, role, r);
     float cnd[CREGS > 0 ? CREGS : 1];
     if constexpr (CREGS > 0) {
 #pragma unroll
-        for (int r = 0; r < CREGS; ++r) {
-            const int d = feat_of_reg(TILE, r, qd);
-            cnd[r] = (d < C && !is_tangent) ? args.cond[sample * C + d] : 0.f;
-        }
+        for (int r = 0; r < CREGS; ++r) cnd[r] = cond_reg<TILE>(args, sample, qd, is_tangent, r);
     }
 
     // tangent lanes: e.e restricted to this lane's features
@@ -525,35 +511,18 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     // (cooperative twin: one copy -- the four wavefronts hold the same tile and write the same values)
     f32x4* const ks = lds_slots + (size_t)(COOP ? 0 : (threadIdx.x >> 6)) * kSlots * R4 * 64 + lane;
     f32x4* const exch = lds_slots + (size_t)kSlots * R4 * 64 + lane;         // COOP: 2 (WIDE: 1) x (KH / 4) x 64 exchange slots
-    FF_SKEW_HOLD(COOP && wv == kSkewWave, 1);          // (test builds: this wavefront starts late ...)
-#pragma unroll
-    for (int s = 0; s < kSlots; ++s)
-#pragma unroll
-        for (int j = 0; j < R4; ++j) ks[(s * R4 + j) * 64] = f32x4{0.f, 0.f, 0.f, 0.f};
-    FF_SKEW_HOLD(COOP && wv == kSkewWave, 2);          // (... and lingers between its zero fill and its first store)
+    // zero fill, then the caller's first stage.  The twin's barrier between the two is round 3's first fix; the skew test's
+    // un-fixed build drops it again.
+#if defined(FF_DEBUG_UNFIX)
+    constexpr bool FILL_BARRIER = false;
+#else
+    constexpr bool FILL_BARRIER = COOP;
+#endif
     float kl[kSlots];
 #pragma unroll
     for (int s = 0; s < kSlots; ++s) kl[s] = 0.f;
     float lp = 0.f;
-    // Cooperative twin: the four wavefronts share the slots.  Everything they store there later is the same value from
-    // each of them, so late or repeated stores are harmless -- except this zero fill: a wavefront that starts late would
-    // wipe the caller's first stage (below) between another wavefront's store and its first read.  All fills first.
-#if !defined(FF_DEBUG_UNFIX)
-    if constexpr (COOP) __syncthreads();
-#endif
-    if (args.k1_in) {            // first stage supplied by the caller (FSAL of the previous step)
-#pragma unroll
-        for (int j = 0; j < R4; ++j) {
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int d = feat_of_reg(TILE, 4 * j + i, qd);
-                if (d < D && !is_tangent) v[i] = args.k1_in[sample * D + d];
-            }
-            ks[j * 64] = v;
-        }
-    }
-    FF_SKEW_HOLD(COOP && wv != kSkewWave, 2);          // (test builds: the others wait between that store and their first read)
+    init_stage_slots<TILE, DREGS, COOP, FILL_BARRIER>(args, ks, sample, qd, is_tangent, wv == kSkewWave);
     if constexpr (TANGENTS) {
         // the per-sample divergence of stage 0 is carried by ONE lane of the sample (first tangent
         // column, lane group 0); all other lanes integrate their own partial sums from zero
@@ -568,25 +537,17 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     const int out_bias_byte = (int)(L.bias_off_out() * 4);
 
     // ---- cooperative twin: this wavefront's share of a layer --------------------------------------------------------
-    // Wavefront wv owns logical blocks [wv * NBW, (wv + 1) * NBW) of every hidden layer and visits its chunks of a layer
-    // group-major: visit i = (group i / NM, own block i % NM) -> chunk_index() of ff_layout.h in the SAME packed stream.
-    // Every layer's visiting list is padded to a multiple of RING, so a layer always starts at ring slot 0.
+    // Wavefront wv owns logical blocks [wv * NBW, (wv + 1) * NBW) of every hidden layer (coop_byte / coop_layer, ff_ode_frame.hpp).
     constexpr int NBW = COOP ? NB / 4 : NB;
     const int ob0 = wv * NBW;
     constexpr LayerGeom CG1 = layer_geom(K1, NB, RB / 4), CGH = layer_geom(KH, NB, RB / 4), CGO = layer_geom(KH, NOB_OUT, RB / 4);
-    constexpr int CN1 = (CG1.G * NBW + RING - 1) / RING * RING;          // padded visits of layer 1
-    auto coop_byte = [&](const LayerGeom& G, int sbyte, int i, int nm, int b0) __attribute__((always_inline)) {
-        const int g = i / nm, j = i % nm;
-        return sbyte + chunk_index(G, g < G.G ? g : 0, b0 + j) * CB;      // (padding visits re-read a real chunk)
-    };
-
     // prefetch ring: the first RING chunks of layer 1 (of this wavefront's visiting list in the cooperative twin)
     f32x4 ring[RING][T::PHYS];
 #pragma unroll
     for (int i = 0; i < RING; ++i)
 #pragma unroll
         for (int p = 0; p < T::PHYS; ++p)
-            ring[i][p] = sload(ws, lane16, (COOP ? coop_byte(CG1, 0, i, NBW, ob0) : i * CB) + p * 1024);
+            ring[i][p] = sload(ws, lane16, (COOP ? coop_byte<TILE>(CG1, 0, i, NBW, ob0) : i * CB) + p * 1024);
 
     float P[WIDE ? 4 : KH];          // operand registers of a hidden layer (WIDE: they stay in LDS)
     // Accumulators of the hidden layers.  They always hold the bias of the layer about to run: a block is
@@ -643,94 +604,20 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
         float net[NOB_OUT * RB];
         if constexpr (COOP) {
             // ---- cooperative evaluation: NB / 4 blocks of every layer per wavefront, activations exchanged through LDS --
-            constexpr int RBQ = RB / 4;
-            const int c1_byte = row_byte + 128, c1_next = row_byte + args.etab_stride * 4 + 128;
-            // one layer of this wavefront's share: acc[j] += W[block b0 + j, :] . Bop over the layer's groups, in
-            // ascending group order (the order of the one-wavefront kernel: same FMA chain per output row).
-            // next(k, slot): request visit k of the NEXT layer into ring slot `slot`.
-            auto coop_layer = [&](auto tag, const auto& Bop, auto& acc, int sbyte, int b0, auto&& next) __attribute__((always_inline)) {
-                constexpr int KIND = decltype(tag)::value;          // 0 = layer 1, 1 = hidden, 2 = output
-                constexpr LayerGeom G = KIND == 0 ? CG1 : (KIND == 1 ? CGH : CGO);
-                constexpr int NM = KIND == 2 ? NOB_OUT : NBW;
-                constexpr int NV = KIND == 0 ? CN1 : G.G * NM;
-                static_assert(NV % RING == 0, "visiting lists are multiples of the ring length");
-                constexpr int OUT_LAST = (DREGS * T::NQ - (NOB_OUT - 1) * 32 + TILE - 1) / TILE;
-                constexpr int LAST_PHYS = KIND == 2 ? (OUT_LAST < T::PHYS ? OUT_LAST : T::PHYS) : T::PHYS;
-                // WIDE: the operands of group g come from the exchange buffer, requested one group ahead
-                constexpr bool LDS_B = WIDE && KIND != 0;
-                f32x4 bq = f32x4{0.f, 0.f, 0.f, 0.f}, bq_next = f32x4{0.f, 0.f, 0.f, 0.f};
-                if constexpr (LDS_B) bq_next = exch[0];
-                static_for<NV>([&](auto ii) {
-                    constexpr int i = decltype(ii)::value;
-                    constexpr int slot = i % RING, g = i / NM, j = i % NM;
-                    if constexpr (g < G.G) {
-                        if constexpr (LDS_B && j == 0) {
-                            bq = bq_next;
-                            if constexpr (g + 1 < G.G) bq_next = exch[(g + 1) * 64];
-                        }
-                        static_for<4>([&](auto qq) {
-                            constexpr int q = decltype(qq)::value;
-                            float bop;
-                            if constexpr (LDS_B) bop = bq[q];
-                            else bop = Bop[4 * g + q];
-                            static_for<T::PHYS>([&](auto pp) {
-                                constexpr int p = decltype(pp)::value;
-                                if constexpr (KIND == 2 && j == NM - 1 && p >= LAST_PHYS) {
-                                    if constexpr (g == 0 && q == 0) acc[j].v[p] = T::zero();
-                                } else if constexpr (KIND == 2 && g == 0 && q == 0)
-                                    acc[j].v[p] = T::mfma(ring[slot][p][q], bop, T::zero());
-                                else
-                                    acc[j].v[p] = T::mfma(ring[slot][p][q], bop, acc[j].v[p]);
-                            });
-                        });
-                    }
-                    constexpr int nxt = i + RING;
-                    if constexpr (nxt < NV) {
-                        static_for<T::PHYS>([&](auto pp) {
-                            constexpr int p = decltype(pp)::value;
-                            ring[slot][p] = sload(ws, lane16, coop_byte(G, sbyte, nxt, NM, b0) + p * 1024);
-                        });
-                    } else {
-                        next(std::integral_constant<int, nxt - NV>{}, std::integral_constant<int, slot>{});
-                    }
-                    __builtin_amdgcn_sched_barrier(0x2 | 0x4 | 0x400 | 0x80);
-                });
+            const int c1_byte = row_byte + 128;
+            // the layer and the activation exchange of the twin: coop_layer / coop_exchange, ff_ode_frame.hpp
+            auto layer = [&](auto tag, const auto& Bop, auto& acc, int sbyte, int b0, auto&& next) __attribute__((always_inline)) {
+                coop_layer<TILE, H, DREGS, CREGS, RING, WIDE, decltype(tag)::value>(ring, ws, lane16, exch, Bop, acc, sbyte, b0, next);
             };
-            // activate this wavefront's blocks and trade them for everybody else's: P <- all KH operand registers
-            auto coop_exchange = [&](const BlockAcc<TILE> (&acc)[NBW], int buf) __attribute__((always_inline)) {
-                f32x4* const xb = exch + (size_t)(WIDE ? 0 : buf) * (KH / 4) * 64;
-                if constexpr (WIDE) __syncthreads();         // one buffer: the layer that read it has finished everywhere
-                static_for<NBW>([&](auto jj) {
-                    constexpr int j = decltype(jj)::value;
-                    static_for<RBQ>([&](auto rr) {
-                        constexpr int r4 = decltype(rr)::value;
-                        ActGroup ag;
-                        float out[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) ag.pre[i] = acc[j].reg(4 * r4 + i);
-                        static_for<kActStages>([&](auto kk) {
-                            act_stage<TANGENTS, ACT, decltype(kk)::value>(ag, out, is_tangent, value_lane_bytes, aspec);
-                        });
-                        xb[((ob0 + j) * RBQ + r4) * 64] = f32x4{out[0], out[1], out[2], out[3]};
-                    });
-                });
-                __syncthreads();
-                FF_SKEW_HOLD(wv == kSkewWave, 2);       // (test builds: late to read what the others are about to overwrite)
-                if constexpr (!WIDE) {
-#pragma unroll
-                    for (int k4 = 0; k4 < KH / 4; ++k4) {
-                        const f32x4 v = xb[k4 * 64];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) P[4 * k4 + i] = v[i];
-                    }
-                }
+            auto exchange = [&](const BlockAcc<TILE> (&acc)[NBW], int buf) __attribute__((always_inline)) {
+                coop_exchange<TILE, H, TANGENTS, ACT, WIDE>(acc, exch, buf, ob0, P, wv == kSkewWave, is_tangent, value_lane_bytes, aspec);
             };
             auto next_hidden_or_out = [&](int l_next, auto kk, auto sl) __attribute__((always_inline)) {
                 // visit k of the layer after a hidden-side layer: hidden layer l_next, or the output layer
                 constexpr int k = decltype(kk)::value, slot = decltype(sl)::value;
                 const bool is_hid = l_next < args.n_hidden - 1;
-                const int byte = is_hid ? coop_byte(CGH, L.chunk_off_hid(l_next) * CB, k, NBW, ob0)
-                                        : coop_byte(CGO, out_sbyte, k, NOB_OUT, 0);
+                const int byte = is_hid ? coop_byte<TILE>(CGH, L.chunk_off_hid(l_next) * CB, k, NBW, ob0)
+                                        : coop_byte<TILE>(CGO, out_sbyte, k, NOB_OUT, 0);
                 static_for<T::PHYS>([&](auto pp) {
                     constexpr int p = decltype(pp)::value;
                     ring[slot][p] = sload(ws, lane16, byte + p * 1024);
@@ -740,40 +627,39 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
             // layer 1
 #pragma unroll
             for (int j = 0; j < NBW; ++j) cacc[j] = load_bias_acc<TILE>(ts, q16b, c1_byte + (ob0 + j) * 128);
-            coop_layer(std::integral_constant<int, 0>{}, y, cacc, 0, ob0,
-                       [&](auto kk, auto sl) { next_hidden_or_out(0, kk, sl); });
+            layer(std::integral_constant<int, 0>{}, y, cacc, 0, ob0,
+                  [&](auto kk, auto sl) { next_hidden_or_out(0, kk, sl); });
             for (int l = 0; l < args.n_hidden - 1; ++l) {
                 BlockAcc<TILE> nacc[NBW];                            // this layer's bias: requested before the exchange
                 const int bbyte = (int)(L.bias_off_hid(l) * 4);
 #pragma unroll
                 for (int j = 0; j < NBW; ++j) nacc[j] = load_bias_acc<TILE>(ws, q16b, bbyte + (ob0 + j) * 128);
-                coop_exchange(cacc, xbuf);
+                exchange(cacc, xbuf);
                 xbuf ^= 1;
 #pragma unroll
                 for (int j = 0; j < NBW; ++j) cacc[j] = nacc[j];
-                coop_layer(std::integral_constant<int, 1>{}, P, cacc, L.chunk_off_hid(l) * CB, ob0,
-                           [&](auto kk, auto sl) { next_hidden_or_out(l + 1, kk, sl); });
+                layer(std::integral_constant<int, 1>{}, P, cacc, L.chunk_off_hid(l) * CB, ob0,
+                      [&](auto kk, auto sl) { next_hidden_or_out(l + 1, kk, sl); });
             }
             BiasBlk<TILE> obias[NOB_OUT];
 #pragma unroll
             for (int o = 0; o < NOB_OUT; ++o) obias[o] = load_bias<TILE>(ws, q16b, out_bias_byte + o * 128);
-            coop_exchange(cacc, xbuf);
+            exchange(cacc, xbuf);
             xbuf ^= 1;
             // output layer: every wavefront computes all of it (a handful of rows; no exchange, and the same chain as the
             // one-wavefront kernel); the ring moves on to layer 1 of the next evaluation
             BlockAcc<TILE> oacc[NOB_OUT];
-            coop_layer(std::integral_constant<int, 2>{}, P, oacc, out_sbyte, 0, [&](auto kk, auto sl) {
+            layer(std::integral_constant<int, 2>{}, P, oacc, out_sbyte, 0, [&](auto kk, auto sl) {
                 constexpr int k = decltype(kk)::value, slot = decltype(sl)::value;
                 static_for<T::PHYS>([&](auto pp) {
                     constexpr int p = decltype(pp)::value;
-                    ring[slot][p] = sload(ws, lane16, coop_byte(CG1, 0, k, NBW, ob0) + p * 1024);
+                    ring[slot][p] = sload(ws, lane16, coop_byte<TILE>(CG1, 0, k, NBW, ob0) + p * 1024);
                 });
             });
 #pragma unroll
             for (int o = 0; o < NOB_OUT; ++o)
 #pragma unroll
                 for (int r = 0; r < RB; ++r) net[o * RB + r] = oacc[o].reg(r) + obias[o].reg(r);
-            (void)c1_next;
         } else {
         // `pend` = pre-activations of the previous layer's last block; they
         // are activated into P[(NB-1)*RB ..] behind the first MFMAs of the next layer, whose
@@ -941,15 +827,12 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
         }
         if (flags & 2u) {
             if constexpr (!TANGENTS) {
-                if (!args.noise) {      // in-kernel noise: registers 4j..4j+3 of a lane are dimensions 4*blk..4*blk+3
-                    const unsigned long long gs = (unsigned long long)(sample + args.rng_sample_offset);
+                if (!args.noise) {
 #pragma unroll
                     for (int j = 0; j < R4; ++j) {
-                        uint32_t c[4] = {(uint32_t)gs, (uint32_t)(gs >> 32), (uint32_t)(hdr->noise_idx + args.rng_noise_base),
-                                         (uint32_t)(feat_of_reg(TILE, 4 * j, qd) >> 2)};
-                        philox4x32_10(c, (uint32_t)args.rng_seed, (uint32_t)(args.rng_seed >> 32));
-                        box_muller(c[0], c[1], nz[4 * j], nz[4 * j + 1]);
-                        box_muller(c[2], c[3], nz[4 * j + 2], nz[4 * j + 3]);
+                        const f32x4 z = noise_draw4<TILE>(args, hdr, sample, qd, j);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) nz[4 * j + i] = z[i];
                     }
                 }
             }

@@ -19,7 +19,7 @@
 // two alternating LDS buffers with one barrier per layer; both output layers are computed by every wavefront; wavefront 0
 // writes the outputs.  Same packed weights, same table, the same fp32 FMA chain per output row: bitwise the one-wavefront
 // kernel's results.  The stage slots are ONE copy shared by the four wavefronts, which brings three hazards:
-//   * the zero fill of the slots needs a barrier before k1_in is stored (a late wavefront would wipe it);
+//   * the zero fill of the slots needs a barrier before k1_in is stored (a late wavefront would wipe it: init_stage_slots);
 //   * the exchange-buffer index alternates over the whole launch, not per evaluation or per network;
 //   * net A's output is NOT parked in the row's stage slot while net B runs (no barrier lies between a fast wavefront's store
 //     of the finished right-hand side into that slot and a slow wavefront's read of the parked value): it stays in registers.
@@ -56,7 +56,6 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     constexpr int KH = NB * RB;                      // operand registers of a hidden layer
     constexpr int R4 = DREGS / 4;
     constexpr int NSUB = SELECT ? 1 : 2;             // networks per evaluation row
-    typedef const __attribute__((address_space(4))) RowHdr* HdrPtr;   // scalar (SMEM) loads
 
     if (args.gate && *(const volatile int*)args.gate == 0) return;
 
@@ -69,7 +68,6 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     const long long wave = COOP ? (long long)blockIdx.x : (((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     [[maybe_unused]] const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wavefront of the workgroup
     const int D = args.dim;
-    const int C = args.cond_dim;
     const ActSpec aspec = {0.f, 0.f, 0.f, 0};
 
     long long sample = wave * TILE + col;
@@ -78,23 +76,11 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
 
     float x[DREGS];
 #pragma unroll
-    for (int r = 0; r < DREGS; ++r) {
-        const int d = feat_of_reg(TILE, r, qd);
-        float v = 0.f;
-        if (d < D) {
-            v = args.x_in[sample * D + d];
-            if (args.in_shift) v = v - args.in_shift[d];
-            if (args.in_scale) v = v / args.in_scale[d];
-        }
-        x[r] = v;
-    }
+    for (int r = 0; r < DREGS; ++r) x[r] = state_reg<TILE>(args, sample, qd, false, 0, r);
     float cnd[CREGS > 0 ? CREGS : 1];
     if constexpr (CREGS > 0) {
 #pragma unroll
-        for (int r = 0; r < CREGS; ++r) {
-            const int d = feat_of_reg(TILE, r, qd);
-            cnd[r] = d < C ? args.cond[sample * C + d] : 0.f;
-        }
+        for (int r = 0; r < CREGS; ++r) cnd[r] = cond_reg<TILE>(args, sample, qd, false, r);
     }
 
     // Runge-Kutta stage slots in LDS, one set per wavefront (each lane touches only its own words); the cooperative twin
@@ -102,27 +88,8 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     extern __shared__ __attribute__((aligned(16))) f32x4 lds_slots[];
     f32x4* const ks = lds_slots + (size_t)(COOP ? 0 : (threadIdx.x >> 6)) * kSlots * R4 * 64 + lane;
     [[maybe_unused]] f32x4* const exch = lds_slots + (size_t)kSlots * R4 * 64 + lane;      // COOP: 2 x (KH / 4) x 64 words of 16 bytes
-    FF_SKEW_HOLD(COOP && wv == kSkewWave, 1);          // (test builds: this wavefront starts late ...)
-#pragma unroll
-    for (int s = 0; s < kSlots; ++s)
-#pragma unroll
-        for (int j = 0; j < R4; ++j) ks[(s * R4 + j) * 64] = f32x4{0.f, 0.f, 0.f, 0.f};
-    FF_SKEW_HOLD(COOP && wv == kSkewWave, 2);          // (... and lingers between its zero fill and its first store)
-    // all zero fills before anybody stores the caller's first stage (mlp_ode_kernel has the story)
-    if constexpr (COOP) __syncthreads();
-    if (args.k1_in) {            // first stage supplied by the caller (FSAL of the previous step)
-#pragma unroll
-        for (int j = 0; j < R4; ++j) {
-            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int d = feat_of_reg(TILE, 4 * j + i, qd);
-                if (d < D) v[i] = args.k1_in[sample * D + d];
-            }
-            ks[j * 64] = v;
-        }
-    }
-    FF_SKEW_HOLD(COOP && wv != kSkewWave, 2);          // (test builds: the others wait between that store and their first read)
+    // zero fill; all of the twin's fills before anybody stores the caller's first stage (init_stage_slots, ff_ode_frame.hpp)
+    init_stage_slots<TILE, DREGS, COOP, COOP>(args, ks, sample, qd, false, wv == kSkewWave);
 
     const Layout L = make_layout(TILE, H, DREGS, CREGS, args.n_hidden);
     constexpr int CB = 1024 * T::PHYS;               // bytes per chunk
@@ -142,12 +109,13 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     const int out_bias_byte = (int)(L.bias_off_out() * 4);
 
     // cooperative twin: wavefront wv owns logical blocks [wv * NBW, (wv + 1) * NBW) of every hidden layer and visits its
-    // chunks of a layer group-major, every visiting list padded to a multiple of RING (mlp_ode_kernel's scheme)
+    // chunks of a layer group-major, every visiting list padded to a multiple of RING (coop_layer, ff_ode_frame.hpp).
+    // visit_byte is the frame's coop_byte kept as a lambda of this kernel: with the function, the 256-wide twins allocate
+    // 157 / 140 VGPRs for 143 / 130 (profiles/frame_refactor.txt).
     constexpr int NBW = COOP ? NB / 4 : NB;
     [[maybe_unused]] const int ob0 = wv * NBW;
     constexpr LayerGeom CG1 = layer_geom(K1, NB, RB / 4), CGH = layer_geom(KH, NB, RB / 4), CGO = layer_geom(KH, NOB_OUT, RB / 4);
-    constexpr int CN1 = (CG1.G * NBW + RING - 1) / RING * RING;          // padded visits of layer 1
-    auto coop_byte = [&](const LayerGeom& G, int sbyte, int i, int nm, int b0) __attribute__((always_inline)) {
+    auto visit_byte = [&](const LayerGeom& G, int sbyte, int i, int nm, int b0) __attribute__((always_inline)) {
         const int g = i / nm, j = i % nm;
         return sbyte + chunk_index(G, g < G.G ? g : 0, b0 + j) * CB;      // (padding visits re-read a real chunk)
     };
@@ -159,7 +127,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
     for (int i = 0; i < RING; ++i)
 #pragma unroll
         for (int p = 0; p < T::PHYS; ++p)
-            ring[i][p] = sload(ws, lane16, (COOP ? coop_byte(CG1, sb_row, i, NBW, ob0) : sb_row + i * CB) + p * 1024);
+            ring[i][p] = sload(ws, lane16, (COOP ? visit_byte(CG1, sb_row, i, NBW, ob0) : sb_row + i * CB) + p * 1024);
 
     float P[KH];                 // operand registers of a hidden layer
     // hidden accumulators: they hold the bias of the layer about to run (row 0's c1 of net A to start with)
@@ -201,72 +169,12 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
         float net[NOB_OUT * RB];
         if constexpr (COOP) {
             // ---- cooperative evaluation: NB / 4 blocks of every layer per wavefront, activations exchanged through LDS --
-            constexpr int RBQ = RB / 4;
-            // one layer of this wavefront's share: acc[j] += W[block b0 + j, :] . Bop over the layer's groups in ascending
-            // group order (the one-wavefront kernel's order: the same FMA chain per output row).
-            // next(k, slot): request visit k of the NEXT layer into ring slot `slot`.
-            auto coop_layer = [&](auto tag, const auto& Bop, auto& acc, int sbyte, int b0, auto&& next) __attribute__((always_inline)) {
-                constexpr int KIND = decltype(tag)::value;          // 0 = layer 1, 1 = hidden, 2 = output
-                constexpr LayerGeom G = KIND == 0 ? CG1 : (KIND == 1 ? CGH : CGO);
-                constexpr int NM = KIND == 2 ? NOB_OUT : NBW;
-                constexpr int NV = KIND == 0 ? CN1 : G.G * NM;
-                static_assert(NV % RING == 0, "visiting lists are multiples of the ring length");
-                constexpr int OUT_LAST = (DREGS * T::NQ - (NOB_OUT - 1) * 32 + TILE - 1) / TILE;
-                constexpr int LAST_PHYS = KIND == 2 ? (OUT_LAST < T::PHYS ? OUT_LAST : T::PHYS) : T::PHYS;
-                static_for<NV>([&](auto ii) {
-                    constexpr int i = decltype(ii)::value;
-                    constexpr int rs = i % RING, g = i / NM, j = i % NM;
-                    if constexpr (g < G.G) {
-                        static_for<4>([&](auto qq) {
-                            constexpr int q = decltype(qq)::value;
-                            static_for<T::PHYS>([&](auto pp) {
-                                constexpr int p = decltype(pp)::value;
-                                if constexpr (KIND == 2 && j == NM - 1 && p >= LAST_PHYS) {
-                                    if constexpr (g == 0 && q == 0) acc[j].v[p] = T::zero();
-                                } else if constexpr (KIND == 2 && g == 0 && q == 0)
-                                    acc[j].v[p] = T::mfma(ring[rs][p][q], Bop[4 * g + q], T::zero());
-                                else
-                                    acc[j].v[p] = T::mfma(ring[rs][p][q], Bop[4 * g + q], acc[j].v[p]);
-                            });
-                        });
-                    }
-                    constexpr int nxt = i + RING;
-                    if constexpr (nxt < NV) {
-                        static_for<T::PHYS>([&](auto pp) {
-                            constexpr int p = decltype(pp)::value;
-                            ring[rs][p] = sload(ws, lane16, coop_byte(G, sbyte, nxt, NM, b0) + p * 1024);
-                        });
-                    } else {
-                        next(std::integral_constant<int, nxt - NV>{}, std::integral_constant<int, rs>{});
-                    }
-                    __builtin_amdgcn_sched_barrier(0x2 | 0x4 | 0x400 | 0x80);
-                });
+            // the layer and the activation exchange of the twin: coop_layer / coop_exchange, ff_ode_frame.hpp
+            auto layer = [&](auto tag, const auto& Bop, auto& acc, int sbyte, int b0, auto&& next) __attribute__((always_inline)) {
+                coop_layer<TILE, H, DREGS, CREGS, RING, false, decltype(tag)::value>(ring, ws, lane16, exch, Bop, acc, sbyte, b0, next);
             };
-            // activate this wavefront's blocks and trade them for everybody else's: P <- all KH operand registers
-            auto coop_exchange = [&](const BlockAcc<TILE> (&acc)[NBW], int buf) __attribute__((always_inline)) {
-                f32x4* const xb = exch + (size_t)buf * (KH / 4) * 64;
-                static_for<NBW>([&](auto jj) {
-                    constexpr int j = decltype(jj)::value;
-                    static_for<RBQ>([&](auto rr) {
-                        constexpr int r4 = decltype(rr)::value;
-                        ActGroup g4;
-                        float out[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) g4.pre[i] = acc[j].reg(4 * r4 + i);
-                        static_for<kActStages>([&](auto kk) {
-                            act_stage<false, 0, decltype(kk)::value>(g4, out, false, 0, aspec);
-                        });
-                        xb[((ob0 + j) * RBQ + r4) * 64] = f32x4{out[0], out[1], out[2], out[3]};
-                    });
-                });
-                __syncthreads();
-                FF_SKEW_HOLD(wv == kSkewWave, 2);       // (test builds: late to read what the others are about to overwrite)
-#pragma unroll
-                for (int k4 = 0; k4 < KH / 4; ++k4) {
-                    const f32x4 v = xb[k4 * 64];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) P[4 * k4 + i] = v[i];
-                }
+            auto exchange = [&](const BlockAcc<TILE> (&acc)[NBW], int buf) __attribute__((always_inline)) {
+                coop_exchange<TILE, H, false, 0, false>(acc, exch, buf, ob0, P, wv == kSkewWave, false, 0, aspec);
             };
             // Net A's output while net B runs.  In registers: the stage slots are shared, and a fast wavefront stores the
             // row's finished right-hand side into the slot before a slow one would have read a value parked there.
@@ -278,8 +186,8 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                     // visit k of the layer after a hidden-side layer: hidden layer l_next, or the output layer
                     constexpr int k = decltype(kk)::value, rs = decltype(sl)::value;
                     const bool is_hid = l_next < args.n_hidden - 1;
-                    const int byte = is_hid ? coop_byte(CGH, sb + L.chunk_off_hid(l_next) * CB, k, NBW, ob0)
-                                            : coop_byte(CGO, sb + out_sbyte, k, NOB_OUT, 0);
+                    const int byte = is_hid ? visit_byte(CGH, sb + L.chunk_off_hid(l_next) * CB, k, NBW, ob0)
+                                            : visit_byte(CGO, sb + out_sbyte, k, NOB_OUT, 0);
                     static_for<T::PHYS>([&](auto pp) {
                         constexpr int p = decltype(pp)::value;
                         ring[rs][p] = sload(ws, lane16, byte + p * 1024);
@@ -290,33 +198,33 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                 const int c1_byte = row_byte + 128 + sub * H * 4;
 #pragma unroll
                 for (int j = 0; j < NBW; ++j) cacc[j] = load_bias_acc<TILE>(ts, q16, c1_byte + (ob0 + j) * 128);
-                coop_layer(std::integral_constant<int, 0>{}, y, cacc, sb, ob0,
-                           [&](auto kk, auto sl) { next_hidden_or_out(0, kk, sl); });
+                layer(std::integral_constant<int, 0>{}, y, cacc, sb, ob0,
+                      [&](auto kk, auto sl) { next_hidden_or_out(0, kk, sl); });
                 for (int l = 0; l < args.n_hidden - 1; ++l) {
                     BlockAcc<TILE> nacc[NBW];                            // this layer's bias: requested before the exchange
                     const int bbyte = sb + (int)(L.bias_off_hid(l) * 4);
 #pragma unroll
                     for (int j = 0; j < NBW; ++j) nacc[j] = load_bias_acc<TILE>(ws, q16, bbyte + (ob0 + j) * 128);
-                    coop_exchange(cacc, xbuf);
+                    exchange(cacc, xbuf);
                     xbuf ^= 1;
 #pragma unroll
                     for (int j = 0; j < NBW; ++j) cacc[j] = nacc[j];
-                    coop_layer(std::integral_constant<int, 1>{}, P, cacc, sb + L.chunk_off_hid(l) * CB, ob0,
-                               [&](auto kk, auto sl) { next_hidden_or_out(l + 1, kk, sl); });
+                    layer(std::integral_constant<int, 1>{}, P, cacc, sb + L.chunk_off_hid(l) * CB, ob0,
+                          [&](auto kk, auto sl) { next_hidden_or_out(l + 1, kk, sl); });
                 }
                 BiasBlk<TILE> obias[NOB_OUT];
 #pragma unroll
                 for (int o = 0; o < NOB_OUT; ++o) obias[o] = load_bias<TILE>(ws, q16, sb + out_bias_byte + o * 128);
-                coop_exchange(cacc, xbuf);
+                exchange(cacc, xbuf);
                 xbuf ^= 1;
                 // output layer: every wavefront computes all of it; the ring moves on to net B's layer 1 (after net A) or
                 // to net A's layer 1 of the next evaluation
                 BlockAcc<TILE> oacc[NOB_OUT];
-                coop_layer(std::integral_constant<int, 2>{}, P, oacc, sb + out_sbyte, 0, [&](auto kk, auto sl) {
+                layer(std::integral_constant<int, 2>{}, P, oacc, sb + out_sbyte, 0, [&](auto kk, auto sl) {
                     constexpr int k = decltype(kk)::value, rs = decltype(sl)::value;
                     static_for<T::PHYS>([&](auto pp) {
                         constexpr int p = decltype(pp)::value;
-                        ring[rs][p] = sload(ws, lane16, coop_byte(CG1, SELECT ? sb_next : (sub == 0 ? sub_bytes : 0), k, NBW, ob0) + p * 1024);
+                        ring[rs][p] = sload(ws, lane16, visit_byte(CG1, SELECT ? sb_next : (sub == 0 ? sub_bytes : 0), k, NBW, ob0) + p * 1024);
                     });
                 });
 #pragma unroll
@@ -512,15 +420,12 @@ __global__ __launch_bounds__(256, WPS) void mlp_pair_kernel(const KernelArgs arg
                     const int d = feat_of_reg(TILE, r, qd);
                     nz[r] = (d < D) ? np[d] : 0.f;
                 }
-            } else {                // in-kernel noise, drawn as mlp_ode_kernel draws it (ff_ode_args)
-                const unsigned long long gs = (unsigned long long)(sample + args.rng_sample_offset);
+            } else {
 #pragma unroll
                 for (int j = 0; j < R4; ++j) {
-                    uint32_t c[4] = {(uint32_t)gs, (uint32_t)(gs >> 32), (uint32_t)(hdr->noise_idx + args.rng_noise_base),
-                                     (uint32_t)(feat_of_reg(TILE, 4 * j, qd) >> 2)};
-                    philox4x32_10(c, (uint32_t)args.rng_seed, (uint32_t)(args.rng_seed >> 32));
-                    box_muller(c[0], c[1], nz[4 * j], nz[4 * j + 1]);
-                    box_muller(c[2], c[3], nz[4 * j + 2], nz[4 * j + 3]);
+                    const f32x4 z = noise_draw4<TILE>(args, hdr, sample, qd, j);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) nz[4 * j + i] = z[i];
                 }
             }
             const float gn = hdr->gn;
