@@ -180,6 +180,8 @@ PROBE_NOISE_INDEX = 0xFFFFFFFE     # FF_PROBE_NOISE_INDEX
 TRACE_PROBE_NOISE_BASE = 0xFFFE0000  # FF_TRACE_PROBE_NOISE_BASE (second probe set: + 0x8000)
 MOMENTUM_NOISE_BASE = 0xFFFD0000   # FF_MOMENTUM_NOISE_BASE (+ k: momentum k of a data point, ff_marginal_expand / _reduce)
 MAX_MOMENTA = 4096                 # 1 <= K <= 4096
+HUTCH_PROBE_NOISE_BASE = 0xFFFC0000  # FF_HUTCH_PROBE_NOISE_BASE (+ k: probe k >= 1 of a K-probe Hutchinson launch, ff_probe_fill)
+MAX_HUTCH_PROBES = 65535           # FF_MAX_HUTCH_PROBES
 
 _lib = None
 
@@ -245,6 +247,9 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_normal_fill.restype = ctypes.c_int
     L.ff_normal_fill.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64,
                                  ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p]
+    probe_fill = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_float]
+    L.ff_probe_fill.restype = L.ff_probe_fill_host.restype = ctypes.c_int
+    L.ff_probe_fill.argtypes, L.ff_probe_fill_host.argtypes = probe_fill + [ctypes.c_void_p], probe_fill
     L.ff_scaled_rms_workspace_bytes.restype = ctypes.c_size_t
     L.ff_scaled_rms.restype = ctypes.c_int
     L.ff_scaled_rms.argtypes = [ctypes.POINTER(NormTerm), ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p,
@@ -429,6 +434,27 @@ def normal_fill(batch: int, dim: int, seed: int, sample_offset: int, device, noi
                                   noise_index & 0xFFFFFFFF, float(scale), ctypes.c_void_p(stream))
     if rc != FF_OK:
         raise _err(rc, "ff_normal_fill")
+    return out
+
+
+def probe_fill(batch: int, num_probes: int, dim: int, seed: int, sample_offset: int, device, scale: float = 1.0) -> torch.Tensor:
+    """ff_probe_fill: the [batch, K, dim] probes (+-``scale``) of a K-probe Hutchinson launch for global rows
+    sample_offset .. sample_offset + batch - 1 -- probe 0 under the single-probe stream's index, probe k >= 1 under
+    HUTCH_PROBE_NOISE_BASE + k.  On a CUDA device on the current stream; ``device="cpu"`` goes to ff_probe_fill_host."""
+    device = torch.device(device)
+    K = int(num_probes)
+    if not 1 <= K <= MAX_HUTCH_PROBES:
+        raise ValueError(f"num_probes={num_probes}: 1 .. {MAX_HUTCH_PROBES} probes per sample")
+    if batch < 0 or dim < 1:
+        raise ValueError(f"probe_fill: batch={batch}, dim={dim}")
+    out = torch.empty(batch, K, dim, dtype=torch.float32, device=device)
+    if batch == 0:
+        return out
+    L = lib()
+    rc = _on_stream(device, L.ff_probe_fill, L.ff_probe_fill_host,
+                    (out.data_ptr(), batch, K, dim, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), float(scale)))
+    if rc != FF_OK:
+        raise _err(rc, "ff_probe_fill")
     return out
 
 
@@ -649,6 +675,22 @@ def _chk(t: Optional[torch.Tensor], name: str, dev) -> int:
     return t.data_ptr()
 
 
+def probe_count(probe: Optional[torch.Tensor]) -> int:
+    """ff_ode_args.tangent_count of a Hutchinson launch with this probe: K for [B, K, D], 0 (one probe) for [B, D] / None."""
+    return int(probe.shape[1]) if probe is not None and probe.dim() == 3 else 0
+
+
+def _chk_probe(probe: Optional[torch.Tensor], B: int, D: int, mode: int, tangent_count: int) -> None:
+    """The probe's shape: [B, D], or [B, K, D] in MODE_HUTCH with tangent_count = K (ff_ode_args.tangent_count)."""
+    if probe is None:
+        return
+    K = max(int(tangent_count), 1) if mode == MODE_HUTCH else 1
+    want = (B, K, D) if (probe.dim() == 3 or K > 1) else (B, D)
+    if tuple(probe.shape) != want:
+        raise RuntimeError(f"probe has shape {tuple(probe.shape)}, expected {want}" +
+                           (f" (tangent_count={tangent_count})" if len(want) == 3 else ""))
+
+
 def f32_on(t: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
     """``t`` (or None) detached, on ``dev``, contiguous float32: the form in which every C call takes a tensor."""
     return None if t is None else t.detach().to(dev, torch.float32).contiguous()
@@ -710,8 +752,7 @@ def mlp_ode(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[torch
         return x_out, dlogp, status
     if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
         raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
-    if probe is not None and tuple(probe.shape) != (B, D):
-        raise RuntimeError(f"probe has shape {tuple(probe.shape)}, expected {(B, D)}")
+    _chk_probe(probe, B, D, mode, tangent_count)
     if etab.shape[1] != 32 + row_width(p):
         raise RuntimeError("evaluation table width does not match the plan")
     _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": probe, "noise": noise, "wpack": wpack, "etab": etab,
@@ -754,6 +795,7 @@ def mlp_ode_step(x: torch.Tensor, cond: Optional[torch.Tensor], probe: Optional[
     n_evals = etab.shape[0] - 2
     if etab.shape[1] != 32 + row_width(p) or n_evals < 0:
         raise RuntimeError("evaluation table does not match the plan")
+    _chk_probe(probe, B, D, mode, tangent_count)
     _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": probe, "wpack": wpack, "etab": etab,
                          "k1_in": k1, "kl1_in": kl1, "dlogp_in": dlogp0},
                 x_out=scratch.data_ptr(), dlogp_out=dl.data_ptr() if mode != MODE_STATE else 0,

@@ -296,6 +296,7 @@ const int g_n_pair_kernels = {len(PAIR_INSTANCES)};
     files.append(CSRC / "ff_adaptive.hip")
     files.append(CSRC / "ff_trace.hip")
     files.append(CSRC / "ff_marginal.hip")
+    files.append(CSRC / "ff_probe.hip")
     return files
 
 

@@ -398,6 +398,7 @@ struct Driver {
             a.gate = gated ? &b->state->active : nullptr;
             a.tangent_first = b->n_passes >= 1 && base->mode == FF_MODE_EXACT ? b->pass_first[p] : 0;
             a.tangent_count = b->n_passes >= 1 && base->mode == FF_MODE_EXACT ? b->pass_count[p] : 0;
+            if (base->mode == FF_MODE_HUTCH) a.tangent_count = base->tangent_count;      // K probes per sample ([batch, K, dim])
             for (int j = 0; j < FF_MAX_AUX; ++j) {
                 a.aux_out[j] = (j < n_aux && p == 0) ? out[j] : nullptr;
                 a.aux_lp_out[j] = nullptr;

@@ -589,6 +589,7 @@ static int launch_split(const ff_mlp_plan_t* plan, const ff::SplitKernelEntry& k
     if (a->mode != FF_MODE_STATE && a->mode != FF_MODE_HUTCH && a->mode != FF_MODE_EXACT) return FF_ERR_BADARG;
     if (k.tangents != (a->mode == FF_MODE_STATE ? 0 : (a->mode == FF_MODE_HUTCH ? 1 : 2))) return FF_ERR_BADARG;
     if (a->mode == FF_MODE_HUTCH && !a->probe) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && a->tangent_count > 1) return FF_ERR_UNSUPPORTED;      // one probe per sample in this family
     if (a->mode != FF_MODE_STATE && !a->dlogp_out) return FF_ERR_BADARG;
     int nt = k.tangents == 1 ? 1 : 0, tfirst = 0;
     if (a->mode == FF_MODE_EXACT) {                     // unit tangents of dimensions [tfirst, tfirst + nt): at most 15 per launch
@@ -685,7 +686,7 @@ extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int3
     int nt, unit;
     const int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
     if (rc) return rc;
-    if (mode == FF_MODE_EXACT && tangent_count > 0) nt = tangent_count;
+    if ((mode == FF_MODE_EXACT || mode == FF_MODE_HUTCH) && tangent_count > 0) nt = tangent_count;   // (Hutchinson: K probes)
     if (nt + 1 > plan->tile) return FF_ERR_BADARG;
     const long long spt = plan->tile / (1 + nt);
     const LaunchChoice ch = choose_launch(d, (batch + spt - 1) / spt, jac_out != 0);
@@ -716,7 +717,7 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
         t.batch = batch - row0;
         t.x_in += row0 * D; t.x_out += row0 * D;
         if (t.cond) t.cond += row0 * C;
-        if (t.probe) t.probe += row0 * D;
+        if (t.probe) t.probe += row0 * D * (t.unit_tangents ? 1 : t.n_tangent);       // Hutchinson probes: [batch, n_tangent, dim]
         if (t.dlogp_out) t.dlogp_out += row0;
         if (t.dlogp_in) t.dlogp_in += row0;
         if (t.noise) t.noise += row0 * D;
@@ -749,6 +750,10 @@ extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a
         if (a->tangent_count > 0) nt = a->tangent_count;
         else if (plan->dim > nt) return FF_ERR_BADARG;      // must be split by the caller
         if (tfirst < 0 || tfirst + nt > plan->dim || nt + 1 > plan->tile) return FF_ERR_BADARG;
+    }
+    if (a->mode == FF_MODE_HUTCH && a->tangent_count > 1) {      // K probes per sample: probe is [batch, K, dim]
+        nt = a->tangent_count;
+        if (nt + 1 > plan->tile) return FF_ERR_BADARG;
     }
     // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
     if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;

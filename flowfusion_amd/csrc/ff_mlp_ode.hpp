@@ -498,6 +498,13 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
         for (int r = 0; r < CREGS; ++r) cnd[r] = cond_reg<TILE>(args, sample, qd, is_tangent, r);
     }
 
+    // Hutchinson: a tangent column's vector is its probe (state_reg left it zero)
+    if constexpr (TANGENTS) {
+        if (is_tangent && !args.unit_tangents) {
+#pragma unroll
+            for (int r = 0; r < DREGS; ++r) x[r] = probe_reg<TILE>(args, sample, qd, role, r);
+        }
+    }
     // tangent lanes: e.e restricted to this lane's features
     float ee = 0.f;
     if constexpr (TANGENTS) {

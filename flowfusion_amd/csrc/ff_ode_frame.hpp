@@ -16,7 +16,9 @@ typedef const __attribute__((address_space(4))) RowHdr* HdrPtr;   // scalar (SME
 // arrays stay their own (a register array handed to a helper by reference is split into registers only after inlining,
 // and mlp_ode_m16_h256_d16_c4_t0 then allocates 347 VGPRs for 336).
 // Value columns: x = (x_in - in_shift) / in_scale, cnd = cond.  Tangent columns (is_tangent; role j >= 1 = tangent j-1):
-// x = the unit vector of dimension tangent_first + role - 1, or the sample's probe; cnd = 0.
+// x = the unit vector of dimension tangent_first + role - 1, cnd = 0; a Hutchinson column (unit_tangents == 0) gets 0 here
+// and its probe from probe_reg, in a pass of the kernel's own behind the conditional inputs.  (The probe's address in this
+// function's branch, in any spelling, moved scratch on the 256-wide tangent units: profiles/hutch_multi_resources.txt.)
 template <int TILE>
 __device__ __forceinline__ float state_reg(const KernelArgs& args, long long sample, int qd, bool is_tangent, int role, int r)
 {
@@ -30,11 +32,17 @@ __device__ __forceinline__ float state_reg(const KernelArgs& args, long long sam
             if (args.in_scale) v = v / args.in_scale[d];
         } else if (args.unit_tangents) {
             v = (d == args.tangent_first + role - 1) ? 1.0f : 0.0f;
-        } else {
-            v = args.probe[sample * D + d];
         }
     }
     return v;
+}
+// One register of a Hutchinson tangent column: probe role - 1 of the sample's n_tangent probes, probe [batch, n_tangent, dim]
+// (n_tangent == 1: the sample's one probe).
+template <int TILE>
+__device__ __forceinline__ float probe_reg(const KernelArgs& args, long long sample, int qd, int role, int r)
+{
+    const int d = feat_of_reg(TILE, r, qd);
+    return d < args.dim ? args.probe[(sample * args.n_tangent + (role - 1)) * args.dim + d] : 0.f;
 }
 template <int TILE>
 __device__ __forceinline__ float cond_reg(const KernelArgs& args, long long sample, int qd, bool is_tangent, int r)

@@ -226,10 +226,11 @@ def solve(net, spec: ScheduleSpec, sign: float, mode: int, x: torch.Tensor, t0: 
     base.probe = 0 if probe_d is None else probe_d.data_ptr()
     base.wpack = wpack.data_ptr()
     base.batch, base.mode = B, mode
+    K = _native.probe_count(probe_d) if mode == _native.MODE_HUTCH else 0      # [B, K, D]: K probes per sample
+    base.tangent_count = K
     if cond_d is not None and tuple(cond_d.shape) != (B, plan.cond_dim):
         raise RuntimeError(f"cond has shape {tuple(cond_d.shape)}, expected {(B, plan.cond_dim)}")
-    if probe_d is not None and tuple(probe_d.shape) != (B, D):
-        raise RuntimeError(f"probe has shape {tuple(probe_d.shape)}, expected {(B, D)}")
+    _native._chk_probe(probe_d, B, D, mode, K)
     hook_error: list = []
     if exchange:
         # the sums of squares behind every norm meet the other ranks' between the reduction and the controller launch:

@@ -226,7 +226,10 @@ class ScoreModel(nn.Module):
         with torch.set_grad_enabled(True):
             x.requires_grad_(True)
             xdot = self.ode_drift(t, x, conditional=self.conditional)
-            if self.hutch:
+            if self.hutch and self.e.dim() == 3:      # num_probes = K > 1 (extension): the mean over the K probes [B, K, D]
+                div = sum((torch.autograd.grad(xdot, x, self.e[:, k], create_graph=True, retain_graph=True)[0] * self.e[:, k]).sum(dim=1)
+                          for k in range(self.e.shape[1])) / self.e.shape[1]
+            elif self.hutch:
                 vjp = torch.autograd.grad(xdot, x, self.e, create_graph=True, retain_graph=True)[0]
                 div = (vjp * self.e).sum(dim=1)
             elif self.hutchpp or self.xtrace:
@@ -567,7 +570,7 @@ class ScoreModel(nn.Module):
 
     @torch.no_grad()
     def solve_odes_forward(self, x0_samples, conditional=None, atol=1e-5, rtol=1e-5,
-                           method="dopri5", options=None, *, probe="torch", seed=None, sample_offset=0):
+                           method="dopri5", options=None, *, probe="torch", seed=None, sample_offset=0, num_probes=1):
         """Probability-flow ODE from epsilon up to t=1 with the divergence integrated alongside;
         returns ``(xT, delta_logp[B,1])`` (reference: diffusion.py:642-754).
 
@@ -575,17 +578,27 @@ class ScoreModel(nn.Module):
         moves it, exactly as the reference does (:701), so ``torch.manual_seed`` reproduces its stream;
         ``probe="philox"`` takes the signs of the library's counter-based normals keyed by ``seed`` and the GLOBAL row
         ``sample_offset + r`` (``ff_normal_fill`` with the reserved probe index): drawn on the device (no host draw, no
-        upload) and independent of how a batch is cut into shards (``distributed.log_prob_sharded``)."""
+        upload) and independent of how a batch is cut into shards (``distributed.log_prob_sharded``).
+        ``num_probes=K`` (Hutchinson models): the divergence is the mean over K independent +-1 probes per sample, all
+        carried by ONE launch -- a sample and its K probes share the columns of a kernel tile, so K <= tile - 1 (15, or 31 on
+        the 32-column kernels); a tile holds tile // (1 + K) samples, and the cost follows that occupancy (measured, profiles/hutch_multi.txt:
+        1.99x / 3.97x / 7.93x a single-probe solve at K = 3 / 7 / 15 on 16 columns); the variance falls as 1 / K.  ``self.e`` then holds the
+        probes as [B, K, D]; probe 0 of ``probe="philox"`` is the single-probe stream's, probe k >= 1 lives under the noise
+        index FF_HUTCH_PROBE_NOISE_BASE + k.  On fixed grids the rows are cut so that a probe buffer on the device stays
+        under 1 GiB (``odeint.solve_hutchinson``; ``probe="torch"`` still draws the whole [B, K, D] set on the host, and
+        ``self.e`` holds it whole).  f32 kernels only."""
         philox_ok = self.hutch or self.hutchpp or self.xtrace
         return self._solve_forward(x0_samples, conditional, atol, rtol, method, options, probe_rng=trace_estimators.probe_rng(
             probe, seed, sample_offset, philox_ok, "probe='philox' draws the probes of a Hutchinson / Hutch++ / XTrace model: "
-            "construct it with hutchinson=True, hutchpp=True or xtrace=True"))
+            "construct it with hutchinson=True, hutchpp=True or xtrace=True"), num_probes=num_probes)
 
     @torch.no_grad()
     def _solve_forward(self, x0_samples, conditional, atol, rtol, method, options, in_shift=None, in_scale=None,
-                       probe_rng=None):
+                       probe_rng=None, num_probes=1):
         """solve_odes_forward proper; ``(x - in_shift) / in_scale`` (PopulationModel*.log_prob,
         diffusion.py:1633, 1837) is applied by the kernel's prologue."""
+        K = trace_estimators.check_num_probes(num_probes, bool(self.hutch), "construct the model with hutchinson=True",
+                                              estimator=bool((self.hutchpp or self.xtrace) and not self.hutch))
         fused = self._fusable()
         if fused:
             self._net()
@@ -600,6 +613,12 @@ class ScoreModel(nn.Module):
         if self.hutch:
             if probe_rng is not None and x0_samples.dim() != 2:
                 raise NotImplementedError("probe='philox': only [batch, dim] states")
+            if K > 1:
+                t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
+                xT, dlogp = odeint.solve_hutchinson(self, x0_samples, t_span, method, options, atol, rtol, K, probe_rng,
+                                                    keep=lambda e: setattr(self, "e", e), cond=conditional,
+                                                    in_shift=in_shift, in_scale=in_scale)
+                return xT, dlogp.view(-1, 1)
             self.e = probe = trace_estimators.hutchinson_probe(x0_samples, probe_rng)
             mode = MODE_HUTCH
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
@@ -641,12 +660,12 @@ class ScoreModel(nn.Module):
 
     @torch.no_grad()
     def log_prob(self, x0_samples, conditional=None, atol=1e-4, rtol=1e-4, method="dopri5",
-                 options={"min_step": 1e-6}, *, probe="torch", seed=None, sample_offset=0):
+                 options={"min_step": 1e-6}, *, probe="torch", seed=None, sample_offset=0, num_probes=1):
         """log p(x0) = delta_logp + log prior(xT), shape [B,1] (reference: diffusion.py:756-815).  ``probe`` / ``seed`` /
-        ``sample_offset``: see ``solve_odes_forward``."""
+        ``sample_offset`` / ``num_probes``: see ``solve_odes_forward``."""
         xT, lp = self.solve_odes_forward(x0_samples, conditional=conditional, atol=atol, rtol=rtol,
                                          method=method, options=options, probe=probe, seed=seed,
-                                         sample_offset=sample_offset)
+                                         sample_offset=sample_offset, num_probes=num_probes)
         return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
 
 
@@ -679,10 +698,11 @@ class PopulationModelDiffusion(nn.Module):
         # the reference ignores `steps` here and always takes 100 (diffusion.py:1608)
         return self.score_model.sample_sde(shape, steps=100) * self.scale + self.shift
 
-    def log_prob(self, x, atol=1e-5, rtol=1e-5):
+    def log_prob(self, x, atol=1e-5, rtol=1e-5, *, num_probes=1):
         # the reference does not forward self.method here: the solver default applies (diffusion.py:1633-1635)
+        # (num_probes, extension: see ScoreModel.solve_odes_forward; a model built with hutchinson=True)
         xT, lp = self.score_model._solve_forward(x, None, atol, rtol, "dopri5", self.options,
-                                                 in_shift=self.shift, in_scale=self.scale)
+                                                 in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)
         return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), 1, keepdim=True)
 
 
@@ -716,7 +736,8 @@ class PopulationModelDiffusionConditional(nn.Module):
     def sample_sde(self, shape, conditional=None, steps=100):
         return self.score_model.sample_sde(shape, conditional=self._cond(conditional), steps=100) * self.scale + self.shift
 
-    def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5):
+    def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5, *, num_probes=1):
+        # (num_probes, extension: this wrapper's score model takes the exact trace, so more than one probe is refused there)
         xT, lp = self.score_model._solve_forward(x, self._cond(conditional), atol, rtol, "dopri5", self.options,
-                                                 in_shift=self.shift, in_scale=self.scale)
+                                                 in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)
         return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), 1, keepdim=True)

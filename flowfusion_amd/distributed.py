@@ -211,7 +211,8 @@ def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional:
     ``local_conditional``) are this rank's rows already, with ``n_total`` the size of the whole batch.  A Hutchinson,
     Hutch++ or XTrace model takes its probes from the library's counter-based stream keyed by ``seed`` and the GLOBAL row
     (``probe="philox"``), so with a fixed-grid ``method`` a row's result does not depend on the number of ranks; the
-    exact trace needs no random numbers.  ``**solver`` (atol, rtol, method, options) goes to ``log_prob`` unchanged.
+    exact trace needs no random numbers.  ``**solver`` (atol, rtol, method, options, num_probes) goes to ``log_prob``
+    unchanged: ``num_probes=K`` averages K counter-based probes per global row (``ff_probe_fill``), whatever the sharding.
     Under an adaptive ``method`` (the reference's default) the step size comes from the error norm of the WHOLE batch, as
     torchdiffeq takes it (``global_step_control``: one small all-reduce per norm; every rank needs at least one row);
     results then agree across world sizes to the rounding of those norms.  ``global_control=False``: every rank
@@ -277,7 +278,8 @@ def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: O
     (and ``local_conditional``) this rank's rows already, with ``n_total`` the size of the whole batch.  With
     ``hutchinson=True`` the probe comes from the library's counter-based stream keyed by ``seed`` and the GLOBAL row
     (``probe="philox"``), so a row's result does not depend on the number of ranks; the exact trace (the reference's
-    default, flow.py:158-161) needs no random numbers.  Step control as in ``flow_sample_sharded``."""
+    default, flow.py:158-161) needs no random numbers; ``num_probes=K`` (with ``hutchinson=True``) goes to ``log_prob``
+    with the rest of ``**solver``: K counter-based probes per global row.  Step control as in ``flow_sample_sharded``."""
     n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if solver.get("hutchinson") else {}
     with _step_control(n, group, global_control, solver.get("method", "dopri5")):

@@ -84,7 +84,10 @@ class _FlowBase(nn.Module):
             with torch.enable_grad():
                 y = y.detach().requires_grad_(True)
                 v = velocity(t, y)
-                if mode == MODE_HUTCH:
+                if mode == MODE_HUTCH and probe.dim() == 3:      # K probes (already times 1/sqrt(K)): the sum is their mean
+                    div = sum((torch.autograd.grad(v, y, probe[:, k], retain_graph=True)[0] * probe[:, k]).sum(dim=1)
+                              for k in range(probe.shape[1]))
+                elif mode == MODE_HUTCH:
                     div = (torch.autograd.grad(v, y, probe)[0] * probe).sum(dim=1)
                 else:
                     div = sum(torch.autograd.grad(v[:, i].sum(), y, retain_graph=True)[0][:, i] for i in range(D))
@@ -150,9 +153,18 @@ class _FlowBase(nn.Module):
         return trace_estimators.probe_rng(probe, seed, sample_offset, hutchinson,
                                           "probe='philox' is the Hutchinson probe: pass hutchinson=True")
 
-    def _fused_forward(self, x, conditional, method, options, hutchinson, atol, rtol, norm_only=(), probe_rng=None):
-        """``norm_only``: the raw conditional, which the reference keeps in the solver state (flow.py:779-796, 855-881)."""
+    def _fused_forward(self, x, conditional, method, options, hutchinson, atol, rtol, norm_only=(), probe_rng=None,
+                       num_probes=1):
+        """``norm_only``: the raw conditional, which the reference keeps in the solver state (flow.py:779-796, 855-881).
+        ``num_probes`` (keyword-only extension of ``solve_ode_forward`` / ``log_prob``, with ``hutchinson=True``): the
+        divergence is the mean over that many independent +-1 probes per sample, carried by one launch
+        (``odeint.solve_hutchinson``); 1 = the reference's single probe."""
         t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
+        K = trace_estimators.check_num_probes(num_probes, hutchinson, "pass hutchinson=True")
+        if hutchinson and K > 1:
+            xT, logj = odeint.solve_hutchinson(self, x, t_span, method, options, atol, rtol, K, probe_rng, cond=conditional,
+                                               norm_only=norm_only)
+            return xT, logj.view(-1, 1)
         probe = trace_estimators.hutchinson_probe(x, probe_rng) if hutchinson else None
         xT, logj = self._solve(x, t_span, method, options, MODE_HUTCH if hutchinson else MODE_EXACT, atol, rtol,
                                cond=conditional, probe=probe, norm_only=norm_only)
@@ -206,21 +218,21 @@ class ODEFlow(_FlowBase):
 
     def solve_ode_forward(self, x, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                           options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
-                          probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0):
+                          probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1):
         """Integrate t: 0 -> 1 with the divergence; returns ``(xT, log_jacobian[B,1])`` (flow.py:308-384).
-        ``probe`` / ``seed`` / ``sample_offset``: see ``_probe_rng``."""
+        ``probe`` / ``seed`` / ``sample_offset``: see ``_probe_rng``; ``num_probes``: see ``_fused_forward``."""
         if adjoint:
             raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
         return self._fused_forward(x, None, method, options, hutchinson, atol, rtol,
-                                   probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson))
+                                   probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson), num_probes=num_probes)
 
     def log_prob(self, x, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
-                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0):
+                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1):
         """Log-density of target-space points, shape [B] (flow.py:386-438)."""
         x = (x - self.target_shift) / self.target_scale
         xT, logj = self.solve_ode_forward(x, atol, rtol, method, options, adjoint, hutchinson=hutchinson,
-                                          probe=probe, seed=seed, sample_offset=sample_offset)
+                                          probe=probe, seed=seed, sample_offset=sample_offset, num_probes=num_probes)
         base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
         return base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
 
@@ -282,17 +294,19 @@ class ConditionalODEFlow(_FlowBase):
     def solve_ode_forward(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5,
                           method: str = "dopri5", options: Optional[dict] = None, adjoint: bool = False,
                           hutchinson: bool = False, *, probe: str = "torch", seed: Optional[int] = None,
-                          sample_offset: int = 0):
+                          sample_offset: int = 0, num_probes: int = 1):
         if adjoint:
             raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
         return self._fused_forward(x, self._norm_cond(conditional), method, options, hutchinson, atol, rtol,
-                                   norm_only=(conditional,), probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson))
+                                   norm_only=(conditional,), probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson),
+                                   num_probes=num_probes)
 
     def log_prob(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
-                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0):
+                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1):
         x = (x - self.target_shift) / self.target_scale
         xT, logj = self.solve_ode_forward(x, conditional, atol, rtol, method, options, adjoint,
-                                          hutchinson=hutchinson, probe=probe, seed=seed, sample_offset=sample_offset)
+                                          hutchinson=hutchinson, probe=probe, seed=seed, sample_offset=sample_offset,
+                                          num_probes=num_probes)
         base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
         return base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))

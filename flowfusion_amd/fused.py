@@ -194,6 +194,8 @@ class FusedNet:
             if mode != MODE_STATE or noise is not None:
                 raise ValueError("in-kernel noise applies to state-only integration without a noise buffer")
             return torch.ops.flowfusion_amd.mlp_ode(*args, 0, 0, int(rng[0]), int(rng[1]), int(rng[2]))
+        if mode == MODE_HUTCH and _native.probe_count(args[2]):      # K probes per sample: probe [B, K, D]
+            return torch.ops.flowfusion_amd.mlp_ode(*args, 0, _native.probe_count(args[2]))
         if mode != MODE_EXACT:
             return torch.ops.flowfusion_amd.mlp_ode(*args)
         # exact trace = sum over dimensions of unit-tangent contributions: integrate it in the
@@ -233,7 +235,9 @@ class FusedNet:
             wpack = self.wpack(device, mode)
             launcher = lambda y, k1, kl1, lp0, etab, n_aux, first, count, used=0: torch.ops.flowfusion_amd.mlp_ode_step(
                 y, cond_d, probe_d, k1, kl1, lp0, wpack, etab.to(device), _native.plan_words(plan, used), mode, n_aux, first, count)
-        passes = [(0, 0)] if mode != MODE_EXACT else exact_trace_passes(self.dim, plan.tile)
+        # (Hutchinson with a [B, K, D] probe: the count of the launch is K)
+        passes = [(0, _native.probe_count(probe_d) if mode == MODE_HUTCH else 0)] if mode != MODE_EXACT else \
+            exact_trace_passes(self.dim, plan.tile)
 
         def step(y, k1, lp0, kl1, t_rows, cin, slots, tail, use_y, n_aux):
             n = int(t_rows.numel())

@@ -90,6 +90,77 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
     return y, lp
 
 
+PROBE_BUFFER_FLOATS = 1 << 28      # a K-probe device buffer [rows, K, D] holds FEWER floats than this (under 1 GiB): fixed-grid solves cut their rows to fit
+
+
+def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, probe_rng=None, keep=None, **kw):
+    """``solve`` in MODE_HUTCH with ``num_probes`` = K > 1 independent +-1 probes per sample, averaged (extension; the
+    reference has the single probe, which the front ends keep solving as before -- they come here for K > 1 only).
+    ``probe_rng``: None = torch's generator, or (seed, global row of row 0) = the counter-based stream
+    (trace_estimators.hutchinson_probe).  ``keep(e)`` receives the +-1 probes [B, K, D] -- before the solve where it is one
+    launch sequence (ScoreModel.forward reads them on the generic route), after it where the rows were cut.
+
+    The fused kernel carries the K probes of a sample in K tangent columns of its tile (ff_ode_args.tangent_count) and
+    returns the SUM of their p^T J p, so it gets the probes times 1/sqrt(K).  On fixed grids the rows are cut so that a
+    probe buffer on the device stays under ``PROBE_BUFFER_FLOATS`` floats (1 GiB); rows are independent, so the result
+    does not depend on the cut.  Adaptive solves control the step over the whole batch and take it whole; so does a fixed
+    grid from ``options["grid_constructor"]``, which may depend on the batch it is given.  The rule
+    bounds device buffers only: torch's probes are drawn as ONE ``sign(randn(B, K, D))`` on the host (a row cut must
+    not change which numbers a seed gives), and ``keep`` is handed the whole [B, K, D] set."""
+    from . import trace_estimators
+    from ._native import MODE_HUTCH
+    K = int(num_probes)
+    if K < 2:
+        raise ValueError("solve_hutchinson is the K > 1 route; a single probe is solve(..., MODE_HUTCH, probe=e)")
+    if x.dim() != 2:
+        raise NotImplementedError("num_probes > 1: only [batch, dim] states")
+    fused = front._fusable()
+    if fused:
+        net = front._net()
+        if net.precision != "f32":
+            raise ValueError(f"num_probes={K} with precision={net.precision!r}: the split-precision kernels carry one probe per "
+                             "sample; use precision='f32'")
+        tile = int(net.plan(MODE_HUTCH).tile)
+        if K > tile - 1:
+            raise ValueError(f"num_probes={K}: the kernel of this network holds a sample and its probes in the {tile} columns of "
+                             f"one tile, so at most {tile - 1} probes; use num_probes <= {tile - 1} (or the exact trace)")
+    B, D = x.shape
+    scale = K ** -0.5
+    rows = B
+    # (a grid_constructor may build the grid from y0 -- the batch it is handed: such a solve is not cut either)
+    if fused and method not in solvers.ALL_ADAPTIVE and (options or {}).get("grid_constructor") is None:
+        rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D))
+
+    def draw(r0, r1, whole_cpu):
+        """(+-1 probes or None, the kernel's probes) of rows [r0, r1)."""
+        if probe_rng is None:
+            e = whole_cpu[r0:r1].to(x.device)
+        elif keep is None:      # nobody asks for the +-1 form: fill the scaled probes directly
+            return None, _native.probe_fill(r1 - r0, K, D, probe_rng[0], probe_rng[1] + r0, x.device, scale=scale)
+        else:
+            e = trace_estimators.hutchinson_probe(x[r0:r1], (probe_rng[0], probe_rng[1] + r0), K)
+        return e, e * scale
+
+    whole_cpu = torch.sign(torch.randn(B, K, D)) if probe_rng is None else None      # (the reference's draw, with a K axis)
+    if rows >= B:
+        e, p = draw(0, B, whole_cpu)
+        if keep is not None:
+            keep(e)
+        return solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kw)
+    ys, lps, es = [], [], []
+    for r0 in range(0, B, rows):
+        r1 = min(B, r0 + rows)
+        e, p = draw(r0, r1, whole_cpu)
+        kc = dict(kw)
+        if kc.get("cond") is not None:
+            kc["cond"] = kc["cond"][r0:r1]
+        y, lp = solve(front, x[r0:r1], t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kc)
+        ys.append(y), lps.append(lp), es.append(e)
+    if keep is not None:
+        keep(torch.cat(es))
+    return torch.cat(ys), torch.cat(lps)
+
+
 def solve_leapfrog(front, x, grid, cond=None):
     """Kick-drift-kick leapfrog of a separable front end (symplectic.py) over the nodes ``grid``; returns the state
     [B, 2D] and sets ``front.last_solver_stats``.  Compiled shapes: ONE fused launch of the row-select kernel on the table

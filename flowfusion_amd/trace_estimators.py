@@ -128,15 +128,41 @@ def draw_probes_philox(n: int, like: torch.Tensor, seed: int, sample_offset: int
     return torch.where(torch.stack(zs) >= 0, 1.0, -1.0).to(torch.float32)
 
 
-def hutchinson_probe(like: torch.Tensor, rng=None) -> torch.Tensor:
+def hutchinson_probe(like: torch.Tensor, rng=None, num_probes: int = 1) -> torch.Tensor:
     """The +-1 Hutchinson probe [B, D] of a log-density solve: drawn on the CPU and moved, as the reference does
     (diffusion.py:701), or with ``rng = (seed, global index of row 0)`` the signs of the library's counter-based normals
-    (``ff_normal_fill`` with the reserved probe index), drawn on the device."""
+    (``ff_normal_fill`` with the reserved probe index), drawn on the device.  ``num_probes = K > 1`` (extension): K
+    independent probes per sample, [B, K, D] -- ``sign(randn(B, K, D))`` on the CPU, or one ``ff_probe_fill`` launch (probe 0
+    is the single-probe stream's, probe k >= 1 lives under FF_HUTCH_PROBE_NOISE_BASE + k)."""
+    K = int(num_probes)
+    if K < 1:
+        raise ValueError(f"num_probes={num_probes}: at least one probe per sample")
+    if K > 1:
+        B, D = like.shape
+        if rng is None:
+            return torch.sign(torch.randn(B, K, D)).to(like.device)
+        from . import _native
+        return _native.probe_fill(B, K, D, rng[0], rng[1], like.device)
     if rng is None:
         return torch.sign(torch.randn(like.shape)).to(like.device)
     from . import _native
     z = _native.normal_fill(like.shape[0], like.shape[1], rng[0], rng[1], like.device, noise_index=_native.PROBE_NOISE_INDEX)
     return torch.where(z >= 0, 1.0, -1.0).to(torch.float32)
+
+
+def check_num_probes(num_probes, hutchinson: bool, what: str, estimator: bool = False) -> int:
+    """``num_probes`` of a log-density method as an int >= 1; more than one needs a Hutchinson model (``what`` says how to
+    get one) and is not an option of the Hutch++ / XTrace estimators (``estimator``), which draw their own probe sets."""
+    K = int(num_probes)
+    if K < 1:
+        raise ValueError(f"num_probes={num_probes}: at least one probe per sample")
+    if K > 1 and estimator:
+        raise ValueError(f"num_probes={K} is an option of the plain Hutchinson estimator: Hutch++ / XTrace take their probe "
+                         "counts from hpp_rank / hpp_vecs / xt_vecs; construct the model with hutchinson=True or leave num_probes=1")
+    if K > 1 and not hutchinson:
+        raise ValueError(f"num_probes={K} averages Hutchinson probes and this solve takes the exact trace: {what}, or leave "
+                         "num_probes=1")
+    return K
 
 
 def probe_rng(probe: str, seed, sample_offset: int, philox_ok: bool, refusal: str):

@@ -130,7 +130,8 @@ typedef struct ff_ode_args {
     const float* x_in;       /* [batch, dim]  initial state                                */
     float*       x_out;      /* [batch, dim]  final state                                  */
     const float* cond;       /* [batch, cond_dim] or NULL                                  */
-    const float* probe;      /* [batch, dim]  Hutchinson probe e (FF_MODE_HUTCH) or NULL   */
+    const float* probe;      /* [batch, dim]  Hutchinson probe e (FF_MODE_HUTCH) or NULL;
+                                [batch, K, dim] with tangent_count = K > 1 (see there)     */
     float*       dlogp_out;  /* [batch]       integrated divergence (modes 1,2) or NULL    */
     const float* noise;      /* [n_noise, batch, dim] standard normals (EM); NULL = in-kernel
                                 noise (rng_* below) if the table has FF_ROW_NOISE rows      */
@@ -149,7 +150,15 @@ typedef struct ff_ode_args {
     int32_t      tangent_count;  /* dimensions [first, first+count); count 0 = all `dim`.  A
                                     trace over more dimensions than fit one wavefront
                                     (count + 1 <= plan.tile) is the sum of dlogp_out over
-                                    several launches, each of which also returns x_out.     */
+                                    several launches, each of which also returns x_out.
+                                    FF_MODE_HUTCH: 0 or 1 = one probe per sample; K > 1 = K
+                                    probes per sample, `probe` is [batch, K, dim] and
+                                    dlogp_out the integral of sum_k p_k^T J p_k (scale the
+                                    probes by 1/sqrt(K) for the mean): tile / (1 + K)
+                                    samples per tile, K + 1 <= plan.tile (FF_ERR_BADARG
+                                    beyond).  FF_PREC_F32 plans only: a split-precision plan
+                                    answers FF_ERR_UNSUPPORTED for every K > 1, whether or
+                                    not K + 1 would fit a tile.                              */
     /* --- adaptive stepping support (all optional; zero / NULL when unused) ---------------------
      * One attempt of an embedded Runge-Kutta step is one launch: the first stage k[0] is supplied
      * by the caller (FSAL), the evaluation rows fill the other slots WITHOUT a STEP_END flag, and
@@ -343,6 +352,12 @@ int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidd
  * k < 4096 -- a range of its own below the trace probes', so a seed shared with the prior draw or a probe set gives
  * unrelated momenta. */
 #define FF_MOMENTUM_NOISE_BASE 0xFFFD0000u
+/* Noise indices reserved for probes 1 .. K-1 of a sample in a K-probe Hutchinson launch (ff_ode_args.tangent_count = K in
+ * FF_MODE_HUTCH; ff_probe_fill below): probe k >= 1 of global row g is the sign of z(seed, g, FF_HUTCH_PROBE_NOISE_BASE + k,
+ * d), k < 65536; probe 0 keeps FF_PROBE_NOISE_INDEX, so K = 1 is the single-probe stream.  A range of its own below the
+ * momenta's. */
+#define FF_HUTCH_PROBE_NOISE_BASE 0xFFFC0000u
+#define FF_MAX_HUTCH_PROBES 65535
 
 /*
  * out[r][d] = scale * z(seed, global row sample_offset + r, noise_index, d)  for r < batch, d < dim, with z the
@@ -354,6 +369,20 @@ int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidd
  */
 int ff_normal_fill(float* out, int64_t batch, int32_t dim, uint64_t seed, int64_t sample_offset,
                    uint32_t noise_index, float scale, void* hip_stream);
+
+/*
+ * The K Rademacher probes of a K-probe Hutchinson launch, in the layout ff_ode_args.probe takes ([batch, K, dim]):
+ *   out[r][k][d] = z(seed, sample_offset + r, index_k, d) >= 0 ? scale : -scale,
+ *   index_0 = FF_PROBE_NOISE_INDEX,  index_k = FF_HUTCH_PROBE_NOISE_BASE + k  (1 <= k < K <= FF_MAX_HUTCH_PROBES)
+ * -- bit for bit `where(ff_normal_fill(.., index_k, 1.0f) >= 0, 1, -1) * scale` of the K fills, stacked: one write-only
+ * pass instead of K fills, a stack, a comparison and a product.  Rows are keyed by the global row, so a shard's rows are
+ * the rows of the whole.  scale = 1/sqrt(K) makes the launch's sum over probes their mean.  `out` is a DEVICE pointer;
+ * enqueues on hip_stream.  ff_probe_fill_host: the same on host memory (libm's transcendentals: a sign may differ from
+ * the device's only where |z| is within their 2e-6 of zero).  FF_ERR_BADARG: out NULL, batch < 0, K or dim out of range.
+ */
+int ff_probe_fill(float* out, int64_t batch, int32_t K, int32_t dim, uint64_t seed, int64_t sample_offset, float scale,
+                  void* hip_stream);
+int ff_probe_fill_host(float* out, int64_t batch, int32_t K, int32_t dim, uint64_t seed, int64_t sample_offset, float scale);
 
 /*
  * out = x_coef * x + sum_s coef[s] * k[s]   over n contiguous fp32 elements (DEVICE pointers; x may be NULL,
