@@ -239,6 +239,8 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     L.ff_mlp_ode_launch.restype = ctypes.c_int
     L.ff_mlp_ode_launch.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p]
+    L.ff_mlp_ode_launch_probes.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_probes.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p]
     L.ff_mlp_samples_per_workgroup.restype = ctypes.c_int
     L.ff_mlp_samples_per_workgroup.argtypes = [ctypes.POINTER(PlanStruct), ctypes.c_int]
     L.ff_last_hip_error.restype = ctypes.c_int
@@ -712,8 +714,9 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
     return _AuxPtrs(*range(t.data_ptr(), t.data_ptr() + t.shape[0] * step, step))
 
 
-def _launch_ode(p: PlanStruct, dev, tensors: dict, **fields) -> None:
-    """The one ff_mlp_ode_launch of the four ops below, on torch's current stream of ``dev``.  ``tensors``: the caller's
+def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, **fields) -> None:
+    """The one launch of the five ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch, or
+    ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer.  ``tensors``: the caller's
     tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
     of what the op allocated itself.  A field named in neither stays zero."""
     a = OdeArgs(**fields)
@@ -722,9 +725,15 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, **fields) -> None:
             setattr(a, field, _chk(t, _ARG_NAMES[field], dev))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
+        if per_probe is None:
+            what = "ff_mlp_ode_launch"
+            rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
+        else:
+            what = "ff_mlp_ode_launch_probes"
+            rc = lib().ff_mlp_ode_launch_probes(ctypes.byref(p), ctypes.byref(a), _chk(per_probe, "per_probe", dev),
+                                                ctypes.c_void_p(stream))
     if rc != FF_OK:
-        raise _err(rc, "ff_mlp_ode_launch")
+        raise _err(rc, what)
 
 
 @torch.library.custom_op("flowfusion_amd::mlp_ode", mutates_args=())
@@ -769,6 +778,48 @@ def _(x, cond, probe, noise, wpack, etab, in_shift, in_scale, out_scale, out_shi
       tangent_first=0, tangent_count=0, rng_seed=0, rng_sample_offset=0, rng_noise_base=0):
     B = x.shape[0]
     return (torch.empty_like(x), x.new_empty(B if mode != MODE_STATE else 0),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_probes", mutates_args=())
+def mlp_ode_probes(x: torch.Tensor, cond: Optional[torch.Tensor], probe: torch.Tensor, wpack: torch.Tensor,
+                   etab: torch.Tensor, in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor],
+                   out_scale: Optional[torch.Tensor], out_shift: Optional[torch.Tensor], plan: List[int],
+                   tangent_count: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``mlp_ode`` in MODE_HUTCH with the divergence of every probe on its own (ff_mlp_ode_launch_probes): returns (final
+    state [B, D], integrated divergence [B], per-probe divergences [B, K], status [1]), K = max(1, tangent_count); the
+    first two are bitwise ``mlp_ode``'s, row k of the third is the integral of p_k^T J p_k for probe k as given."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_probes needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    B, D = x.shape
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    K = max(int(tangent_count), 1)
+    x_out = torch.empty_like(x)
+    dlogp = torch.zeros(B, dtype=torch.float32, device=dev)
+    per_probe = torch.zeros(B, K, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, dlogp, per_probe, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    _chk_probe(probe, B, D, MODE_HUTCH, tangent_count)
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": probe, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                per_probe=per_probe, x_out=x_out.data_ptr(), dlogp_out=dlogp.data_ptr(), status=status.data_ptr(),
+                batch=B, n_evals=etab.shape[0], mode=MODE_HUTCH, tangent_count=tangent_count,
+                stage_slots=_slots_hint(plan))
+    return x_out, dlogp, per_probe, status
+
+
+@mlp_ode_probes.register_fake
+def _(x, cond, probe, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, tangent_count=0):
+    B = x.shape[0]
+    return (torch.empty_like(x), x.new_empty(B), x.new_empty(B, max(int(tangent_count), 1)),
             torch.empty(1, dtype=torch.int32, device=x.device))
 
 

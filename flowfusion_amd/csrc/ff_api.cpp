@@ -718,6 +718,7 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
         t.x_in += row0 * D; t.x_out += row0 * D;
         if (t.cond) t.cond += row0 * C;
         if (t.probe) t.probe += row0 * D * (t.unit_tangents ? 1 : t.n_tangent);       // Hutchinson probes: [batch, n_tangent, dim]
+        if (t.dlogp_probe_out) t.dlogp_probe_out += row0 * t.n_tangent;                // per-probe divergences: [batch, n_tangent]
         if (t.dlogp_out) t.dlogp_out += row0;
         if (t.dlogp_in) t.dlogp_in += row0;
         if (t.noise) t.noise += row0 * D;
@@ -734,10 +735,18 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
     return FF_OK;
 }
 
-extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
+// ff_mlp_ode_launch (probe_out == NULL) and ff_mlp_ode_launch_probes: one argument check, one launch path
+static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream)
 {
     LaunchDesc d;
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
+    if (probe_out) {
+        // per-probe divergences: Hutchinson launches of the fp32 single-network family that are whole solves (an attempt
+        // launch carries a sample's stage-0 divergence on ONE lane: kl1_in / dlogp_in / aux_lp_out have no per-probe form)
+        if (a->mode != FF_MODE_HUTCH) return FF_ERR_BADARG;
+        if (d.family == kSplit) return FF_ERR_UNSUPPORTED;
+        if (a->k1_in || a->kl1_in || a->dlogp_in || a->n_aux > 0 || a->jac_out) return FF_ERR_BADARG;
+    }
     if (d.family == kSplit) return launch_split(plan, *d.split, a, hip_stream);
     if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
@@ -772,7 +781,18 @@ extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a
     if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
+    ka.dlogp_probe_out = probe_out;
     return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
+}
+
+extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a, void* hip_stream)
+{
+    return launch_ode(plan, a, nullptr, hip_stream);
+}
+
+extern "C" int ff_mlp_ode_launch_probes(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* dlogp_probe_out, void* hip_stream)
+{
+    return launch_ode(plan, a, dlogp_probe_out, hip_stream);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

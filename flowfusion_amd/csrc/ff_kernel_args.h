@@ -49,6 +49,7 @@ struct KernelArgs {
     int act_kind;        // FF_ACT_* (read by the run-time-choice instantiations only)
     float act_p0, act_p1;   // parameters of the hidden activation (FF_ACT_LEAKY_RELU / ELU / SOFTPLUS)
     const int* gate;     // ff_ode_args.gate: device word read at kernel start; 0 = this launch does nothing (NULL = run)
+    float* dlogp_probe_out;   // [batch, n_tangent] each tangent column's own integrated divergence (ff_mlp_ode_launch_probes) or NULL
 };
 
 // bits of the status word (ff_ode_args.status)

@@ -866,6 +866,23 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     float lp0 = 0.f;
     if constexpr (TANGENTS) {
         if (args.dlogp_in) lp0 = args.dlogp_in[sample];
+        // per-probe output (ff_mlp_ode_launch_probes; a wave-uniform test): tangent column j's own integral, summed over its
+        // lane groups in ascending order -- the order reduce_tangents takes them, so with one tangent column the value is
+        // dlogp_out bit for bit -- by all lanes; the sample's writer stores it as probe j - 1.  It reads what reduce_tangents
+        // reads and nothing else: the same sums formed on the tangent lanes themselves keep `role` (or the lane numbers it
+        // follows from) and a second mask until here, which costs 20 of the 38 tangent units one to four registers and the
+        // eleven at their register cap scratch (profiles/hutch_probe_out.txt).
+        if (args.dlogp_probe_out) {
+            for (int j = 1; j <= args.n_tangent; ++j) {
+                float own = 0.f;
+#pragma unroll
+                for (int g = 0; g < T::NQ; ++g) {
+                    const int src = ((g << T::SHIFT) | ((col + j) & (TILE - 1))) * 4;
+                    own += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, lp)));
+                }
+                if (writer && qd == 0) args.dlogp_probe_out[sample * args.n_tangent + (j - 1)] = own;
+            }
+        }
         const float tot = reduce_tangents(lp);
         if (writer && qd == 0 && args.dlogp_out) args.dlogp_out[sample] = lp0 + tot;
     }

@@ -570,9 +570,20 @@ class ScoreModel(nn.Module):
 
     @torch.no_grad()
     def solve_odes_forward(self, x0_samples, conditional=None, atol=1e-5, rtol=1e-5,
-                           method="dopri5", options=None, *, probe="torch", seed=None, sample_offset=0, num_probes=1):
+                           method="dopri5", options=None, *, probe="torch", seed=None, sample_offset=0, num_probes=1,
+                           return_stderr=False):
         """Probability-flow ODE from epsilon up to t=1 with the divergence integrated alongside;
         returns ``(xT, delta_logp[B,1])`` (reference: diffusion.py:642-754).
+
+        ``return_stderr=True`` (keyword only, extension; ``num_probes=K >= 2`` on a fixed grid): returns
+        ``(xT, delta_logp, stderr[B,1])`` -- the first two bitwise what the call without it returns, ``stderr`` the
+        standard error of ``delta_logp`` as the mean of K single-probe estimates (``trace_estimators.hutchinson_stderr``:
+        their sample standard deviation over sqrt(K)).  The K estimates stay in ``self.dlogp_probes`` [B, K], next to the
+        probes ``self.e`` [B, K, D]: column k is what a single-probe solve with probe k alone returns as ``delta_logp``.
+        They come out of the same launch (ff_mlp_ode_launch_probes: one more store per tangent column), so the solve costs
+        what it costs without them; a ``model=`` module on the generic route pays K more single-probe passes.  Adaptive
+        methods -- the default here -- are refused with the way out: ``method="rk4"`` / ``"dopri5_fixed"`` with
+        ``options={"step_size": h}``.
 
         Extension, keyword only (Hutchinson models): ``probe="torch"`` (default) draws the +-1 probe on the CPU and
         moves it, exactly as the reference does (:701), so ``torch.manual_seed`` reproduces its stream;
@@ -590,15 +601,16 @@ class ScoreModel(nn.Module):
         philox_ok = self.hutch or self.hutchpp or self.xtrace
         return self._solve_forward(x0_samples, conditional, atol, rtol, method, options, probe_rng=trace_estimators.probe_rng(
             probe, seed, sample_offset, philox_ok, "probe='philox' draws the probes of a Hutchinson / Hutch++ / XTrace model: "
-            "construct it with hutchinson=True, hutchpp=True or xtrace=True"), num_probes=num_probes)
+            "construct it with hutchinson=True, hutchpp=True or xtrace=True"), num_probes=num_probes, return_stderr=return_stderr)
 
     @torch.no_grad()
     def _solve_forward(self, x0_samples, conditional, atol, rtol, method, options, in_shift=None, in_scale=None,
-                       probe_rng=None, num_probes=1):
+                       probe_rng=None, num_probes=1, return_stderr=False):
         """solve_odes_forward proper; ``(x - in_shift) / in_scale`` (PopulationModel*.log_prob,
         diffusion.py:1633, 1837) is applied by the kernel's prologue."""
         K = trace_estimators.check_num_probes(num_probes, bool(self.hutch), "construct the model with hutchinson=True",
                                               estimator=bool((self.hutchpp or self.xtrace) and not self.hutch))
+        stderr = trace_estimators.check_stderr(return_stderr, K, method)
         fused = self._fusable()
         if fused:
             self._net()
@@ -615,10 +627,13 @@ class ScoreModel(nn.Module):
                 raise NotImplementedError("probe='philox': only [batch, dim] states")
             if K > 1:
                 t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
-                xT, dlogp = odeint.solve_hutchinson(self, x0_samples, t_span, method, options, atol, rtol, K, probe_rng,
-                                                    keep=lambda e: setattr(self, "e", e), cond=conditional,
-                                                    in_shift=in_shift, in_scale=in_scale)
-                return xT, dlogp.view(-1, 1)
+                out = odeint.solve_hutchinson(self, x0_samples, t_span, method, options, atol, rtol, K, probe_rng,
+                                              keep=lambda e: setattr(self, "e", e), per_probe=stderr, cond=conditional,
+                                              in_shift=in_shift, in_scale=in_scale)
+                if stderr:
+                    self.dlogp_probes = out[2]
+                    return out[0], out[1].view(-1, 1), trace_estimators.hutchinson_stderr(out[2]).view(-1, 1)
+                return out[0], out[1].view(-1, 1)
             self.e = probe = trace_estimators.hutchinson_probe(x0_samples, probe_rng)
             mode = MODE_HUTCH
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
@@ -660,13 +675,16 @@ class ScoreModel(nn.Module):
 
     @torch.no_grad()
     def log_prob(self, x0_samples, conditional=None, atol=1e-4, rtol=1e-4, method="dopri5",
-                 options={"min_step": 1e-6}, *, probe="torch", seed=None, sample_offset=0, num_probes=1):
+                 options={"min_step": 1e-6}, *, probe="torch", seed=None, sample_offset=0, num_probes=1, return_stderr=False):
         """log p(x0) = delta_logp + log prior(xT), shape [B,1] (reference: diffusion.py:756-815).  ``probe`` / ``seed`` /
-        ``sample_offset`` / ``num_probes``: see ``solve_odes_forward``."""
-        xT, lp = self.solve_odes_forward(x0_samples, conditional=conditional, atol=atol, rtol=rtol,
-                                         method=method, options=options, probe=probe, seed=seed,
-                                         sample_offset=sample_offset, num_probes=num_probes)
-        return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
+        ``sample_offset`` / ``num_probes`` / ``return_stderr``: see ``solve_odes_forward``; with ``return_stderr=True``
+        returns ``(log_p [B,1], stderr [B,1])`` (the prior term is exact, so the standard error is ``delta_logp``'s)."""
+        out = self.solve_odes_forward(x0_samples, conditional=conditional, atol=atol, rtol=rtol,
+                                      method=method, options=options, probe=probe, seed=seed,
+                                      sample_offset=sample_offset, num_probes=num_probes, return_stderr=return_stderr)
+        xT, lp = out[0], out[1]
+        logp = lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
+        return (logp, out[2]) if return_stderr else logp
 
 
 # ------------------------------------------------------------------------------------------------
@@ -699,6 +717,9 @@ class PopulationModelDiffusion(nn.Module):
         return self.score_model.sample_sde(shape, steps=100) * self.scale + self.shift
 
     def log_prob(self, x, atol=1e-5, rtol=1e-5, *, num_probes=1):
+        """(No ``return_stderr`` here: like the reference's, this solve is hard-wired to adaptive dopri5, and per-probe
+        divergences are carried by fixed-grid solves only -- ``self.score_model.log_prob(..., method="rk4",
+        options={"step_size": h}, num_probes=K, return_stderr=True)`` on the normalised points is the route.)"""
         # the reference does not forward self.method here: the solver default applies (diffusion.py:1633-1635)
         # (num_probes, extension: see ScoreModel.solve_odes_forward; a model built with hutchinson=True)
         xT, lp = self.score_model._solve_forward(x, None, atol, rtol, "dopri5", self.options,
@@ -737,6 +758,8 @@ class PopulationModelDiffusionConditional(nn.Module):
         return self.score_model.sample_sde(shape, conditional=self._cond(conditional), steps=100) * self.scale + self.shift
 
     def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5, *, num_probes=1):
+        """(No ``return_stderr`` here: like the reference's, this solve is hard-wired to adaptive dopri5 -- and this
+        wrapper's score model takes the exact trace, which has no probes to spread.)"""
         # (num_probes, extension: this wrapper's score model takes the exact trace, so more than one probe is refused there)
         xT, lp = self.score_model._solve_forward(x, self._cond(conditional), atol, rtol, "dopri5", self.options,
                                                  in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)

@@ -129,6 +129,17 @@ def _local_batch(x, local_x, n_total, conditional, local_conditional, group):
     return n, lo, hi, _local_rows(x, local_x, lo, hi, "x"), _local_rows(conditional, local_conditional, lo, hi, "conditional")
 
 
+def _finish_with_stderr(local, n: int, group, gather: bool):
+    """``_finish`` for a ``(estimate, stderr)`` pair of equal shapes ([rows, 1] or [rows]): the two travel as the columns
+    of ONE [rows, 2] tensor, so the single all-gather at the end stays single, and come back in their own shapes."""
+    est, se = local
+    if not gather:                  # this rank's rows and their bounds: ((estimate, stderr), (lo, hi)), nothing is packed
+        return (est, se), _shard(n, group)[2:]
+    out = _finish(torch.stack([est.reshape(-1), se.reshape(-1)], dim=1), n, group, True)
+    shape = lambda t: t.reshape((-1,) + tuple(est.shape[1:]))
+    return shape(out[:, 0]), shape(out[:, 1])
+
+
 def _finish(local: torch.Tensor, n: int, group, gather: bool):
     """The one collective at the end: the gathered [n, ...] result, or with ``gather=False`` this rank's rows and their
     bounds."""
@@ -204,7 +215,7 @@ def sample_sde_sharded(score_model, shape, conditional: Optional[torch.Tensor] =
 def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,
                      seed: int = 0, group=None, gather: bool = True, local_x: Optional[torch.Tensor] = None,
                      n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None,
-                     global_control: bool = True, **solver):
+                     global_control: bool = True, *, return_stderr: bool = False, **solver):
     """``ScoreModel.log_prob`` of a [B, dim] batch over all ranks; one all-gather of the [B, 1] result at the end.
 
     ``x`` (and ``conditional``) are the full tensors, every rank slicing its rows -- or ``local_x`` (and
@@ -216,12 +227,20 @@ def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional:
     Under an adaptive ``method`` (the reference's default) the step size comes from the error norm of the WHOLE batch, as
     torchdiffeq takes it (``global_step_control``: one small all-reduce per norm; every rank needs at least one row);
     results then agree across world sizes to the rounding of those norms.  ``global_control=False``: every rank
-    controls its steps from its own rows (agreement to the solver tolerances only)."""
+    controls its steps from its own rows (agreement to the solver tolerances only).
+    ``return_stderr=True`` (keyword only; ``num_probes=K >= 2`` and a fixed-grid ``method``, see
+    ``ScoreModel.solve_odes_forward``): returns ``(log_p [B, 1], stderr [B, 1])``; the two are gathered as the columns of
+    one [rows, 2] tensor, so there is still one all-gather.  With ``gather=False`` it returns
+    ``((log_p, stderr), (lo, hi))``: this rank's rows of both, and their bounds."""
     n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     randomised = any(getattr(score_model, k, False) for k in ("hutch", "hutchpp", "xtrace"))
     extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if randomised else {}
+    if return_stderr:
+        extra["return_stderr"] = True
     with _step_control(n, group, global_control, solver.get("method", "dopri5")):
         local = score_model.log_prob(rows, conditional=cond, **solver, **extra)
+    if return_stderr:
+        return _finish_with_stderr(local, n, group, gather)
     return _finish(local, n, group, gather)
 
 
@@ -272,18 +291,25 @@ def flow_sample_sharded(flow, n_total: int, seed: int = 0, conditional: Optional
 def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None, seed: int = 0,
                           group=None, gather: bool = True, local_x: Optional[torch.Tensor] = None,
                           n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None,
-                          global_control: bool = True, **solver):
+                          global_control: bool = True, *, return_stderr: bool = False, **solver):
     """``ODEFlow.log_prob`` / ``ConditionalODEFlow.log_prob`` of a [B, dim] batch over all ranks; one all-gather of the
     [B] result at the end.  ``x`` (and ``conditional``) are the full tensors, every rank slicing its rows -- or ``local_x``
     (and ``local_conditional``) this rank's rows already, with ``n_total`` the size of the whole batch.  With
     ``hutchinson=True`` the probe comes from the library's counter-based stream keyed by ``seed`` and the GLOBAL row
     (``probe="philox"``), so a row's result does not depend on the number of ranks; the exact trace (the reference's
     default, flow.py:158-161) needs no random numbers; ``num_probes=K`` (with ``hutchinson=True``) goes to ``log_prob``
-    with the rest of ``**solver``: K counter-based probes per global row.  Step control as in ``flow_sample_sharded``."""
+    with the rest of ``**solver``: K counter-based probes per global row.  Step control as in ``flow_sample_sharded``.
+    ``return_stderr=True`` (with ``hutchinson=True``, ``num_probes=K >= 2`` and a fixed-grid ``method``): returns
+    ``(log_p [B], stderr [B])``, gathered as the columns of one [rows, 2] tensor -- still one all-gather; with
+    ``gather=False``, ``((log_p, stderr), (lo, hi))``: this rank's rows of both, and their bounds."""
     n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if solver.get("hutchinson") else {}
+    if return_stderr:
+        extra["return_stderr"] = True
     with _step_control(n, group, global_control, solver.get("method", "dopri5")):
         local = flow.log_prob(rows, **solver, **extra) if cond is None else flow.log_prob(rows, cond, **solver, **extra)
+    if return_stderr:
+        return _finish_with_stderr(local, n, group, gather)
     return _finish(local, n, group, gather)
 
 

@@ -154,13 +154,27 @@ class _FlowBase(nn.Module):
                                           "probe='philox' is the Hutchinson probe: pass hutchinson=True")
 
     def _fused_forward(self, x, conditional, method, options, hutchinson, atol, rtol, norm_only=(), probe_rng=None,
-                       num_probes=1):
+                       num_probes=1, return_stderr=False):
         """``norm_only``: the raw conditional, which the reference keeps in the solver state (flow.py:779-796, 855-881).
         ``num_probes`` (keyword-only extension of ``solve_ode_forward`` / ``log_prob``, with ``hutchinson=True``): the
         divergence is the mean over that many independent +-1 probes per sample, carried by one launch
-        (``odeint.solve_hutchinson``); 1 = the reference's single probe."""
+        (``odeint.solve_hutchinson``); 1 = the reference's single probe.
+        ``return_stderr=True`` (keyword-only extension; ``hutchinson=True``, ``num_probes=K >= 2``, a fixed-grid ``method``):
+        returns ``(xT, log_jacobian, stderr [B,1])``, the first two bitwise those of the call without it; ``stderr`` is
+        ``trace_estimators.hutchinson_stderr`` of the K single-probe estimates, which stay in ``self.dlogp_probes`` [B, K]
+        (column k: the log-Jacobian a single-probe solve with probe k alone returns) next to the probes ``self.e``
+        [B, K, D].  Same launch, one more store per tangent column (ff_mlp_ode_launch_probes).  Only this path sets
+        ``self.e`` and ``self.dlogp_probes``, and both stay on the device until the next such call: the plain
+        ``num_probes=K`` solve keeps no probes on the flows (a [B, K, D] tensor held for nobody), and with
+        ``probe="philox"`` it fills the scaled probes directly, without the +-1 form."""
         t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
         K = trace_estimators.check_num_probes(num_probes, hutchinson, "pass hutchinson=True")
+        if trace_estimators.check_stderr(return_stderr, K, method):
+            xT, logj, d = odeint.solve_hutchinson(self, x, t_span, method, options, atol, rtol, K, probe_rng,
+                                                  keep=lambda e: setattr(self, "e", e), per_probe=True,
+                                                  cond=conditional, norm_only=norm_only)
+            self.dlogp_probes = d
+            return xT, logj.view(-1, 1), trace_estimators.hutchinson_stderr(d).view(-1, 1)
         if hutchinson and K > 1:
             xT, logj = odeint.solve_hutchinson(self, x, t_span, method, options, atol, rtol, K, probe_rng, cond=conditional,
                                                norm_only=norm_only)
@@ -218,23 +232,30 @@ class ODEFlow(_FlowBase):
 
     def solve_ode_forward(self, x, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                           options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
-                          probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1):
+                          probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1,
+                          return_stderr: bool = False):
         """Integrate t: 0 -> 1 with the divergence; returns ``(xT, log_jacobian[B,1])`` (flow.py:308-384).
-        ``probe`` / ``seed`` / ``sample_offset``: see ``_probe_rng``; ``num_probes``: see ``_fused_forward``."""
+        ``probe`` / ``seed`` / ``sample_offset``: see ``_probe_rng``; ``num_probes`` / ``return_stderr``: see
+        ``_fused_forward``."""
         if adjoint:
             raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
         return self._fused_forward(x, None, method, options, hutchinson, atol, rtol,
-                                   probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson), num_probes=num_probes)
+                                   probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson), num_probes=num_probes,
+                                   return_stderr=return_stderr)
 
     def log_prob(self, x, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
-                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1):
-        """Log-density of target-space points, shape [B] (flow.py:386-438)."""
+                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1,
+                 return_stderr: bool = False):
+        """Log-density of target-space points, shape [B] (flow.py:386-438); with ``return_stderr=True`` (see
+        ``_fused_forward``) ``(log_p [B], stderr [B])``."""
         x = (x - self.target_shift) / self.target_scale
-        xT, logj = self.solve_ode_forward(x, atol, rtol, method, options, adjoint, hutchinson=hutchinson,
-                                          probe=probe, seed=seed, sample_offset=sample_offset, num_probes=num_probes)
+        out = self.solve_ode_forward(x, atol, rtol, method, options, adjoint, hutchinson=hutchinson, probe=probe, seed=seed,
+                                     sample_offset=sample_offset, num_probes=num_probes, return_stderr=return_stderr)
+        xT, logj = out[0], out[1]
         base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
-        return base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
+        logp = base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
+        return (logp, out[2].squeeze(1)) if return_stderr else logp
 
 
 class ConditionalODEFlow(_FlowBase):
@@ -294,19 +315,23 @@ class ConditionalODEFlow(_FlowBase):
     def solve_ode_forward(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5,
                           method: str = "dopri5", options: Optional[dict] = None, adjoint: bool = False,
                           hutchinson: bool = False, *, probe: str = "torch", seed: Optional[int] = None,
-                          sample_offset: int = 0, num_probes: int = 1):
+                          sample_offset: int = 0, num_probes: int = 1, return_stderr: bool = False):
         if adjoint:
             raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
         return self._fused_forward(x, self._norm_cond(conditional), method, options, hutchinson, atol, rtol,
                                    norm_only=(conditional,), probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson),
-                                   num_probes=num_probes)
+                                   num_probes=num_probes, return_stderr=return_stderr)
 
     def log_prob(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
-                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1):
+                 probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1,
+                 return_stderr: bool = False):
+        """With ``return_stderr=True`` (see ``_fused_forward``) ``(log_p [B], stderr [B])``."""
         x = (x - self.target_shift) / self.target_scale
-        xT, logj = self.solve_ode_forward(x, conditional, atol, rtol, method, options, adjoint,
-                                          hutchinson=hutchinson, probe=probe, seed=seed, sample_offset=sample_offset,
-                                          num_probes=num_probes)
+        out = self.solve_ode_forward(x, conditional, atol, rtol, method, options, adjoint,
+                                     hutchinson=hutchinson, probe=probe, seed=seed, sample_offset=sample_offset,
+                                     num_probes=num_probes, return_stderr=return_stderr)
+        xT, logj = out[0], out[1]
         base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
-        return base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
+        logp = base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
+        return (logp, out[2].squeeze(1)) if return_stderr else logp

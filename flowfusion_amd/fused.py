@@ -166,8 +166,10 @@ class FusedNet:
                   cond: Optional[torch.Tensor] = None, probe: Optional[torch.Tensor] = None,
                   noise: Optional[torch.Tensor] = None,
                   in_shift=None, in_scale=None, out_scale=None, out_shift=None,
-                  rng: Optional[Tuple[int, int, int]] = None, stage_slots: int = 0, plan=None):
-        """Run the fused integration.  Returns (y_final [B,D], dlogp [B] or empty, status [1]).
+                  rng: Optional[Tuple[int, int, int]] = None, stage_slots: int = 0, plan=None, per_probe: bool = False):
+        """Run the fused integration.  Returns (y_final [B,D], dlogp [B] or empty, status [1]) -- with ``per_probe=True``
+        (MODE_HUTCH, fp32 kernels, no noise rows) (y_final, dlogp, per-probe divergences [B, K], status): the first two
+        bitwise what the call without it returns, column k of the third the integral of p_k^T J p_k of probe k as given.
         ``rng = (seed, global index of row 0, noise index of table row 0)`` selects in-kernel noise for
         tables with noise rows (instead of a ``noise`` buffer).  ``plan``: another plan of this network that shares the
         mode's packed weights (``FusedPair``'s select plan); default ``self.plan(mode)``."""
@@ -190,6 +192,10 @@ class FusedNet:
         args = (f32_on(x, dev), cond, f32_on(probe, dev), f32_on(noise, dev), self.wpack(dev, mode), f32_on(etab, dev),
                 f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
                 _native.plan_words(plan, stage_slots), mode)
+        if per_probe:
+            if mode != MODE_HUTCH or noise is not None or rng is not None or args[2] is None:
+                raise ValueError("per_probe=True: a Hutchinson solve (MODE_HUTCH with a probe, no noise rows)")
+            return torch.ops.flowfusion_amd.mlp_ode_probes(*args[:3], *args[4:11], _native.probe_count(args[2]))
         if rng is not None:
             if mode != MODE_STATE or noise is not None:
                 raise ValueError("in-kernel noise applies to state-only integration without a noise buffer")

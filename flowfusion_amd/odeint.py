@@ -22,9 +22,11 @@ from .host_stepper import RowStepper
 
 
 def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=None, norm_only=(), estimator=None,
-          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None):
+          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None, per_probe=False):
     """``odeint(front, x, t_span, method=, atol=, rtol=, options=)``; returns (y [B, D], dlogp [B] or None) and sets
-    ``front.last_solver_stats`` (fused fixed-grid solves leave it alone).
+    ``front.last_solver_stats`` (fused fixed-grid solves leave it alone).  ``per_probe=True`` (fused fixed-grid MODE_HUTCH
+    solves only; ``solve_hutchinson`` is the caller): returns (y, dlogp, per-probe divergences [B, K]) of the kernel's
+    probes as given (ff_mlp_ode_launch_probes).
 
     ``norm_only``: state components the reference carries with a zero derivative (a flow's raw conditional), seen by the
     adaptive error norm only.  ``estimator = (kind, probes)``: a Hutch++ / XTrace solve in MODE_EXACT (``div_fn(A)`` is its
@@ -36,15 +38,19 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
     fused = front._fusable()
     net = front._net() if fused else None
     adaptive_method = method in solvers.ALL_ADAPTIVE
+    if per_probe and not (fused and estimator is None and not adaptive_method):
+        raise ValueError("per_probe=True: per-probe divergences come from the fused fixed-grid launch only")
     if fused and estimator is None and not adaptive_method:
         key = (tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items())), mode) + front._schedule_key()
         if (options or {}).get("grid_constructor") is not None:      # the grid may depend on y0: built per call
             table = front._ode_table(t_span, method, options, mode, y0=x).to(x.device)
         else:
             table = net.cached_table(key, x.device, lambda: front._ode_table(t_span, method, options, mode))
-        y, lp, _ = net.integrate(x, table, mode, cond=cond, probe=probe, stage_slots=solvers.resolve_method(method).stages,
-                                 in_shift=in_shift, in_scale=in_scale, out_scale=out_scale, out_shift=out_shift)
-        return y, (lp if mode != MODE_STATE else None)
+        out = net.integrate(x, table, mode, cond=cond, probe=probe, stage_slots=solvers.resolve_method(method).stages,
+                            in_shift=in_shift, in_scale=in_scale, out_scale=out_scale, out_shift=out_shift, per_probe=per_probe)
+        if per_probe:
+            return out[0], out[1], out[2]
+        return out[0], (out[1] if mode != MODE_STATE else None)
     if in_shift is not None:
         x = (x - in_shift) / in_scale
     if fused and estimator is not None:
@@ -93,7 +99,8 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
 PROBE_BUFFER_FLOATS = 1 << 28      # a K-probe device buffer [rows, K, D] holds FEWER floats than this (under 1 GiB): fixed-grid solves cut their rows to fit
 
 
-def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, probe_rng=None, keep=None, **kw):
+def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, probe_rng=None, keep=None, per_probe=False,
+                     **kw):
     """``solve`` in MODE_HUTCH with ``num_probes`` = K > 1 independent +-1 probes per sample, averaged (extension; the
     reference has the single probe, which the front ends keep solving as before -- they come here for K > 1 only).
     ``probe_rng``: None = torch's generator, or (seed, global row of row 0) = the counter-based stream
@@ -106,12 +113,23 @@ def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, 
     does not depend on the cut.  Adaptive solves control the step over the whole batch and take it whole; so does a fixed
     grid from ``options["grid_constructor"]``, which may depend on the batch it is given.  The rule
     bounds device buffers only: torch's probes are drawn as ONE ``sign(randn(B, K, D))`` on the host (a row cut must
-    not change which numbers a seed gives), and ``keep`` is handed the whole [B, K, D] set."""
+    not change which numbers a seed gives), and ``keep`` is handed the whole [B, K, D] set.
+
+    ``per_probe=True`` (fixed grids; the front ends' ``return_stderr``): returns (y, dlogp, d [B, K]) with y and dlogp
+    bitwise those of the call without it and ``d[b, k]`` what a single-probe solve with probe k alone gives.  Fused: the
+    same launch also stores every tangent column's own integral (ff_mlp_ode_launch_probes); the kernel sees the probes
+    times 1/sqrt(K), so its output is scaled by K.  Where the rows are cut the pieces are concatenated.  A network on the
+    generic route (torch evaluates the module) makes the K-probe pass as before and then K single-probe passes over the
+    same state and grid, one per probe -- K + 1 passes instead of one; the module's right-hand side keeps returning one
+    divergence per row."""
     from . import trace_estimators
     from ._native import MODE_HUTCH
     K = int(num_probes)
     if K < 2:
         raise ValueError("solve_hutchinson is the K > 1 route; a single probe is solve(..., MODE_HUTCH, probe=e)")
+    if per_probe and method in solvers.ALL_ADAPTIVE:
+        raise ValueError(f"per_probe=True with the adaptive method={method!r}: per-probe divergences are carried by fixed-grid "
+                         "solves only (method=\"rk4\" / \"dopri5_fixed\" with options={\"step_size\": h})")
     if x.dim() != 2:
         raise NotImplementedError("num_probes > 1: only [batch, dim] states")
     fused = front._fusable()
@@ -135,7 +153,7 @@ def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, 
         """(+-1 probes or None, the kernel's probes) of rows [r0, r1)."""
         if probe_rng is None:
             e = whole_cpu[r0:r1].to(x.device)
-        elif keep is None:      # nobody asks for the +-1 form: fill the scaled probes directly
+        elif keep is None and (fused or not per_probe):      # nobody asks for the +-1 form: fill the scaled probes directly
             return None, _native.probe_fill(r1 - r0, K, D, probe_rng[0], probe_rng[1] + r0, x.device, scale=scale)
         else:
             e = trace_estimators.hutchinson_probe(x[r0:r1], (probe_rng[0], probe_rng[1] + r0), K)
@@ -146,18 +164,40 @@ def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, 
         e, p = draw(0, B, whole_cpu)
         if keep is not None:
             keep(e)
-        return solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kw)
-    ys, lps, es = [], [], []
+        if not per_probe:
+            return solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kw)
+        if fused:
+            y, lp, d = solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, per_probe=True, **kw)
+            return y, lp, d * float(K)
+        # generic route: the K-probe pass, then one single-probe pass per probe (a front end that reads the probe from its
+        # own attribute -- ScoreModel.forward -- is handed each probe through `keep`, and the whole set again at the end)
+        y, lp = solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kw)
+        cols = []
+        try:
+            for k in range(K):
+                ek = e[:, k].contiguous()
+                if keep is not None:
+                    keep(ek)
+                cols.append(solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=ek, **kw)[1])
+        finally:                    # whatever a pass raised, the front end holds the whole [B, K, D] set again
+            if keep is not None:
+                keep(e)
+        return y, lp, torch.stack(cols, dim=1)
+    ys, lps, es, ds = [], [], [], []
     for r0 in range(0, B, rows):
         r1 = min(B, r0 + rows)
         e, p = draw(r0, r1, whole_cpu)
         kc = dict(kw)
         if kc.get("cond") is not None:
             kc["cond"] = kc["cond"][r0:r1]
-        y, lp = solve(front, x[r0:r1], t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kc)
-        ys.append(y), lps.append(lp), es.append(e)
+        out = solve(front, x[r0:r1], t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, per_probe=per_probe, **kc)
+        ys.append(out[0]), lps.append(out[1]), es.append(e)
+        if per_probe:
+            ds.append(out[2] * float(K))
     if keep is not None:
         keep(torch.cat(es))
+    if per_probe:
+        return torch.cat(ys), torch.cat(lps), torch.cat(ds)
     return torch.cat(ys), torch.cat(lps)
 
 

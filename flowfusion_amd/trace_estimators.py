@@ -165,6 +165,36 @@ def check_num_probes(num_probes, hutchinson: bool, what: str, estimator: bool = 
     return K
 
 
+def check_stderr(return_stderr: bool, num_probes: int, method: str) -> bool:
+    """``return_stderr`` of a log-density method (after ``check_num_probes``): the standard error comes from the spread of
+    the K per-probe divergences of ONE fixed-grid launch (ff_mlp_ode_launch_probes), so it needs K >= 2 and a fixed grid.
+    Refusals are ValueErrors that name the way out, raised before anything touches the device."""
+    if not return_stderr:
+        return False
+    from . import solvers
+    if int(num_probes) < 2:
+        raise ValueError(f"return_stderr=True with num_probes={num_probes}: a standard error is the spread of at least two "
+                         "per-probe estimates; pass num_probes=K with K >= 2 (a Hutchinson model / hutchinson=True)")
+    if method in solvers.ALL_ADAPTIVE:
+        raise ValueError(f"return_stderr=True with the adaptive method={method!r} (the defaults of the log-density methods are "
+                         "adaptive): per-probe divergences are carried by fixed-grid solves only; pass method=\"rk4\" or "
+                         "method=\"dopri5_fixed\" with options={\"step_size\": h} (or a grid_constructor).  The estimate alone "
+                         "(return_stderr=False) is still available adaptively")
+    return True
+
+
+def hutchinson_stderr(d: torch.Tensor) -> torch.Tensor:
+    """Standard error [B] of the mean of the K single-probe estimates ``d`` [B, K]: their sample standard deviation
+    (K - 1 in the denominator) over sqrt(K), computed in double on ``d``'s device (CPU tensors too) and rounded to fp32
+    once.  K equal values give 0."""
+    if d.dim() != 2 or d.shape[1] < 2:
+        raise ValueError(f"hutchinson_stderr: per-probe estimates [B, K >= 2], got {tuple(d.shape)}")
+    K = d.shape[1]
+    dd = d.detach().to(torch.float64)
+    dev = dd - dd.sum(dim=1, keepdim=True) / K
+    return torch.sqrt((dev * dev).sum(dim=1) / (K - 1) / K).to(torch.float32)
+
+
 def probe_rng(probe: str, seed, sample_offset: int, philox_ok: bool, refusal: str):
     """``probe="torch"`` (default): None, the probes follow torch's generator.  ``probe="philox"`` (keyword-only extension of
     the log-density methods): ``(seed, sample_offset)`` keying the counter-based probes by the GLOBAL row, so that they do not

@@ -158,7 +158,8 @@ typedef struct ff_ode_args {
                                     samples per tile, K + 1 <= plan.tile (FF_ERR_BADARG
                                     beyond).  FF_PREC_F32 plans only: a split-precision plan
                                     answers FF_ERR_UNSUPPORTED for every K > 1, whether or
-                                    not K + 1 would fit a tile.                              */
+                                    not K + 1 would fit a tile.  The K terms one by one (not
+                                    only their sum): ff_mlp_ode_launch_probes below.         */
     /* --- adaptive stepping support (all optional; zero / NULL when unused) ---------------------
      * One attempt of an embedded Runge-Kutta step is one launch: the first stage k[0] is supplied
      * by the caller (FSAL), the evaluation rows fill the other slots WITHOUT a STEP_END flag, and
@@ -268,6 +269,26 @@ int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, const float* 
  * environment keeps one kernel).  Batches below one round run on the twin alone where it wins (FF_COOP=0/1 pins that).
  */
 int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* args, void* hip_stream);
+
+/*
+ * ff_mlp_ode_launch with the Hutchinson divergence of every probe on its own: the same launch (same kernels, same x_out
+ * and dlogp_out, bit for bit) also stores
+ *     dlogp_probe_out[b][k] = integral of p_k^T (a I + b J_net) p_k      probe k of row b, in the units of dlogp_out
+ * for k < K = max(1, args->tangent_count); the row sums are dlogp_out up to the order of the additions.  From them a
+ * caller gets the spread of the K single-probe estimates (scale by K if the probes carry 1/sqrt(K)) and so a standard
+ * error of their mean.  `dlogp_probe_out` is DEVICE memory of batch * K floats; NULL makes this ff_mlp_ode_launch.
+ * With the pointer set, refused before anything is enqueued:
+ *     args->mode != FF_MODE_HUTCH                                           FF_ERR_BADARG
+ *     K + 1 > plan->tile                                                    FF_ERR_BADARG (as for tangent_count)
+ *     k1_in, kl1_in, dlogp_in, jac_out set or n_aux > 0                     FF_ERR_BADARG (an attempt launch carries the
+ *                                                                           stage-0 divergence of a sample on one lane;
+ *                                                                           per-probe state across attempts is not kept)
+ *     a split-precision plan                                                FF_ERR_UNSUPPORTED
+ *     a two-network (pair / row-select) plan                                FF_ERR_BADARG (no divergence modes there)
+ */
+int ff_mlp_ode_launch_probes(const ff_mlp_plan_t* plan, const ff_ode_args* args,
+                             float* dlogp_probe_out /* [batch, K], K = max(1, args->tangent_count) */,
+                             void* hip_stream);
 
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
