@@ -599,15 +599,16 @@ class ScoreModel(nn.Module):
         under 1 GiB (``odeint.solve_hutchinson``; ``probe="torch"`` still draws the whole [B, K, D] set on the host, and
         ``self.e`` holds it whole).  f32 kernels only."""
         philox_ok = self.hutch or self.hutchpp or self.xtrace
-        return self._solve_forward(x0_samples, conditional, atol, rtol, method, options, probe_rng=trace_estimators.probe_rng(
+        out = self._solve_forward(x0_samples, conditional, atol, rtol, method, options, probe_rng=trace_estimators.probe_rng(
             probe, seed, sample_offset, philox_ok, "probe='philox' draws the probes of a Hutchinson / Hutch++ / XTrace model: "
             "construct it with hutchinson=True, hutchpp=True or xtrace=True"), num_probes=num_probes, return_stderr=return_stderr)
+        return out if return_stderr else out[:2]
 
     @torch.no_grad()
     def _solve_forward(self, x0_samples, conditional, atol, rtol, method, options, in_shift=None, in_scale=None,
                        probe_rng=None, num_probes=1, return_stderr=False):
-        """solve_odes_forward proper; ``(x - in_shift) / in_scale`` (PopulationModel*.log_prob,
-        diffusion.py:1633, 1837) is applied by the kernel's prologue."""
+        """solve_odes_forward proper; returns ``(xT, delta_logp [B,1], stderr [B,1] or None)``.  ``(x - in_shift) / in_scale``
+        (PopulationModel*.log_prob, diffusion.py:1633, 1837) is applied by the kernel's prologue."""
         K = trace_estimators.check_num_probes(num_probes, bool(self.hutch), "construct the model with hutchinson=True",
                                               estimator=bool((self.hutchpp or self.xtrace) and not self.hutch))
         stderr = trace_estimators.check_stderr(return_stderr, K, method)
@@ -619,27 +620,20 @@ class ScoreModel(nn.Module):
         if (self.hutchpp or self.xtrace) and not self.hutch:
             if in_shift is not None:
                 x0_samples = (x0_samples - in_shift) / in_scale
-            return self._solve_with_estimator(x0_samples, conditional, atol, rtol, method, options, fused, probe_rng)
-        probe = None
-        mode = MODE_EXACT
-        if self.hutch:
-            if probe_rng is not None and x0_samples.dim() != 2:
-                raise NotImplementedError("probe='philox': only [batch, dim] states")
-            if K > 1:
-                t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
-                out = odeint.solve_hutchinson(self, x0_samples, t_span, method, options, atol, rtol, K, probe_rng,
-                                              keep=lambda e: setattr(self, "e", e), per_probe=stderr, cond=conditional,
-                                              in_shift=in_shift, in_scale=in_scale)
-                if stderr:
-                    self.dlogp_probes = out[2]
-                    return out[0], out[1].view(-1, 1), trace_estimators.hutchinson_stderr(out[2]).view(-1, 1)
-                return out[0], out[1].view(-1, 1)
-            self.e = probe = trace_estimators.hutchinson_probe(x0_samples, probe_rng)
-            mode = MODE_HUTCH
+            return self._solve_with_estimator(x0_samples, conditional, atol, rtol, method, options, fused, probe_rng) + (None,)
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
-        xT, dlogp = odeint.solve(self, x0_samples, t_span, method, options, mode, atol, rtol, cond=conditional, probe=probe,
-                                 in_shift=in_shift, in_scale=in_scale)
-        return xT, dlogp.view(-1, 1)
+        if not self.hutch:
+            xT, dlogp = odeint.solve(self, x0_samples, t_span, method, options, MODE_EXACT, atol, rtol, cond=conditional,
+                                     in_shift=in_shift, in_scale=in_scale)
+            return xT, dlogp.view(-1, 1), None
+        if probe_rng is not None and x0_samples.dim() != 2:
+            raise NotImplementedError("probe='philox': only [batch, dim] states")
+        xT, dlogp, d = odeint.solve_hutchinson(self, x0_samples, t_span, method, options, atol, rtol, K, probe_rng,
+                                               keep=lambda e: setattr(self, "e", e), per_probe=stderr, cond=conditional,
+                                               in_shift=in_shift, in_scale=in_scale)
+        if stderr:
+            self.dlogp_probes = d
+        return xT, dlogp.view(-1, 1), (trace_estimators.hutchinson_stderr(d).view(-1, 1) if stderr else None)
 
     def _solve_with_estimator(self, x0, conditional, atol, rtol, method, options, fused, probe_rng=None):
         """Hutch++ / XTrace log-density solve.  The state never depends on the divergence, so the fused launches are those
@@ -690,77 +684,84 @@ class ScoreModel(nn.Module):
 # ------------------------------------------------------------------------------------------------
 # population-model wrappers (affine pre/post-processing; reference: diffusion.py:1466-1848)
 # ------------------------------------------------------------------------------------------------
-class PopulationModelDiffusion(nn.Module):
-    def __init__(self, model=None, sde=None, shift=None, scale=None, method="dopri5", no_sigma=False,
-                 hutchinson=False, options=None, *, precision="f32"):
-        """Arguments as in the reference (diffusion.py:1466-1530); ``precision`` (keyword only, extension) is handed to the
-        inner ``ScoreModel`` (see there)."""
+class _PopulationModel(nn.Module):
+    """What the two wrappers share: a ``ScoreModel`` between ``(x - shift) / scale`` and ``x * scale + shift``."""
+
+    def __init__(self, model, sde, score_model, shift, scale, method, options):
         super().__init__()
         self.model = model
         self.sde = sde
-        self.score_model = ScoreModel(model=self.model, sde=self.sde, hutchinson=hutchinson, no_sigma=no_sigma, precision=precision)
+        self.score_model = score_model
         n = self.model.n_dimensions
         self.register_buffer("shift", shift if shift is not None else torch.zeros(n, dtype=torch.float32))
         self.register_buffer("scale", scale if scale is not None else torch.ones(n, dtype=torch.float32))
         self.method = method
         self.options = options
 
+    def _cond(self, conditional):
+        return None
+
+    def _forward(self, base_samples, conditional):
+        kernel_maps = self.scale.dtype == torch.float32 and self.shift.dtype == torch.float32
+        x = self.score_model._sample_ode(base_samples, self._cond(conditional), 1e-5, 1e-5, self.method, self.options,
+                                         **({"out_scale": self.scale, "out_shift": self.shift} if kernel_maps else {}))
+        # (e.g. float64 statistics from numpy: the reference's `* scale + shift` then promotes the result -- so does this)
+        return x if kernel_maps else x * self.scale + self.shift
+
+    def _sample_sde(self, shape, conditional):
+        # the reference ignores `steps` here and always takes 100 (diffusion.py:1608)
+        return self.score_model.sample_sde(shape, conditional=self._cond(conditional), steps=100) * self.scale + self.shift
+
+    def _log_prob(self, x, conditional, atol, rtol, num_probes):
+        # the reference does not forward self.method here: the solver default applies (diffusion.py:1633-1635)
+        xT, lp, _ = self.score_model._solve_forward(x, self._cond(conditional), atol, rtol, "dopri5", self.options,
+                                                    in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)
+        return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), 1, keepdim=True)
+
+
+class PopulationModelDiffusion(_PopulationModel):
+    def __init__(self, model=None, sde=None, shift=None, scale=None, method="dopri5", no_sigma=False,
+                 hutchinson=False, options=None, *, precision="f32"):
+        """Arguments as in the reference (diffusion.py:1466-1530); ``precision`` (keyword only, extension) is handed to the
+        inner ``ScoreModel`` (see there)."""
+        score_model = ScoreModel(model=model, sde=sde, hutchinson=hutchinson, no_sigma=no_sigma, precision=precision)
+        super().__init__(model, sde, score_model, shift, scale, method, options)
+
     def forward(self, base_samples):
-        if self.scale.dtype != torch.float32 or self.shift.dtype != torch.float32:
-            # (e.g. float64 statistics from numpy: the reference's `* scale + shift` then promotes the result -- so does this)
-            return self.score_model._sample_ode(base_samples, None, 1e-5, 1e-5, self.method, self.options) * self.scale + self.shift
-        return self.score_model._sample_ode(base_samples, None, 1e-5, 1e-5, self.method, self.options,
-                                            out_scale=self.scale, out_shift=self.shift)
+        return self._forward(base_samples, None)
 
     def sample_sde(self, shape, steps=100):
-        # the reference ignores `steps` here and always takes 100 (diffusion.py:1608)
-        return self.score_model.sample_sde(shape, steps=100) * self.scale + self.shift
+        return self._sample_sde(shape, None)
 
     def log_prob(self, x, atol=1e-5, rtol=1e-5, *, num_probes=1):
         """(No ``return_stderr`` here: like the reference's, this solve is hard-wired to adaptive dopri5, and per-probe
         divergences are carried by fixed-grid solves only -- ``self.score_model.log_prob(..., method="rk4",
-        options={"step_size": h}, num_probes=K, return_stderr=True)`` on the normalised points is the route.)"""
-        # the reference does not forward self.method here: the solver default applies (diffusion.py:1633-1635)
-        # (num_probes, extension: see ScoreModel.solve_odes_forward; a model built with hutchinson=True)
-        xT, lp = self.score_model._solve_forward(x, None, atol, rtol, "dopri5", self.options,
-                                                 in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)
-        return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), 1, keepdim=True)
+        options={"step_size": h}, num_probes=K, return_stderr=True)`` on the normalised points is the route.)
+        ``num_probes`` (extension): see ``ScoreModel.solve_odes_forward``; a model built with ``hutchinson=True``."""
+        return self._log_prob(x, None, atol, rtol, num_probes)
 
 
-class PopulationModelDiffusionConditional(nn.Module):
+class PopulationModelDiffusionConditional(_PopulationModel):
     def __init__(self, model=None, sde=None, shift=None, scale=None, conditional_shift=None,
                  conditional_scale=None, no_sigma=False, method="dopri5", options=None, *, precision="f32"):
-        super().__init__()
-        self.model = model
-        self.sde = sde
-        self.score_model = ScoreModel(model=self.model, sde=self.sde, no_sigma=no_sigma, precision=precision)
-        n, c = self.model.n_dimensions, self.model.n_conditionals
-        self.register_buffer("shift", shift if shift is not None else torch.zeros(n, dtype=torch.float32))
-        self.register_buffer("scale", scale if scale is not None else torch.ones(n, dtype=torch.float32))
+        score_model = ScoreModel(model=model, sde=sde, no_sigma=no_sigma, precision=precision)
+        super().__init__(model, sde, score_model, shift, scale, method, options)
+        c = self.model.n_conditionals
         self.register_buffer("conditional_shift",
                              conditional_shift if conditional_shift is not None else torch.zeros(c, dtype=torch.float32))
         self.register_buffer("conditional_scale",
                              conditional_scale if conditional_scale is not None else torch.ones(c, dtype=torch.float32))
-        self.options = options
-        self.method = method
 
     def _cond(self, conditional):
         return (conditional - self.conditional_shift) / self.conditional_scale
 
     def forward(self, base_samples, conditional=None):
-        if self.scale.dtype != torch.float32 or self.shift.dtype != torch.float32:
-            return self.score_model._sample_ode(base_samples, self._cond(conditional), 1e-5, 1e-5, self.method,
-                                                self.options) * self.scale + self.shift
-        return self.score_model._sample_ode(base_samples, self._cond(conditional), 1e-5, 1e-5, self.method,
-                                            self.options, out_scale=self.scale, out_shift=self.shift)
+        return self._forward(base_samples, conditional)
 
     def sample_sde(self, shape, conditional=None, steps=100):
-        return self.score_model.sample_sde(shape, conditional=self._cond(conditional), steps=100) * self.scale + self.shift
+        return self._sample_sde(shape, conditional)
 
     def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5, *, num_probes=1):
         """(No ``return_stderr`` here: like the reference's, this solve is hard-wired to adaptive dopri5 -- and this
-        wrapper's score model takes the exact trace, which has no probes to spread.)"""
-        # (num_probes, extension: this wrapper's score model takes the exact trace, so more than one probe is refused there)
-        xT, lp = self.score_model._solve_forward(x, self._cond(conditional), atol, rtol, "dopri5", self.options,
-                                                 in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)
-        return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), 1, keepdim=True)
+        wrapper's score model takes the exact trace, which has no probes to spread; ``num_probes`` > 1 is refused there.)"""
+        return self._log_prob(x, conditional, atol, rtol, num_probes)

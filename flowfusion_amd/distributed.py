@@ -129,24 +129,47 @@ def _local_batch(x, local_x, n_total, conditional, local_conditional, group):
     return n, lo, hi, _local_rows(x, local_x, lo, hi, "x"), _local_rows(conditional, local_conditional, lo, hi, "conditional")
 
 
-def _finish_with_stderr(local, n: int, group, gather: bool):
-    """``_finish`` for a ``(estimate, stderr)`` pair of equal shapes ([rows, 1] or [rows]): the two travel as the columns
-    of ONE [rows, 2] tensor, so the single all-gather at the end stays single, and come back in their own shapes."""
-    est, se = local
-    if not gather:                  # this rank's rows and their bounds: ((estimate, stderr), (lo, hi)), nothing is packed
-        return (est, se), _shard(n, group)[2:]
-    out = _finish(torch.stack([est.reshape(-1), se.reshape(-1)], dim=1), n, group, True)
-    shape = lambda t: t.reshape((-1,) + tuple(est.shape[1:]))
-    return shape(out[:, 0]), shape(out[:, 1])
-
-
-def _finish(local: torch.Tensor, n: int, group, gather: bool):
+def _finish(local, n: int, group, gather: bool):
     """The one collective at the end: the gathered [n, ...] result, or with ``gather=False`` this rank's rows and their
-    bounds."""
+    bounds.  ``local``: a tensor, or an ``(estimate, stderr)`` pair of equal shapes ([rows, 1] or [rows]) -- the two travel
+    as the columns of ONE [rows, 2] tensor, so the single all-gather stays single, and come back in their own shapes."""
     world, _, lo, hi = _shard(n, group)
     if not gather:
         return local, (lo, hi)
-    return gather_rows(local, n, group) if world > 1 else local
+    if world == 1:
+        return local
+    if torch.is_tensor(local):
+        return gather_rows(local, n, group)
+    est, se = local
+    out = gather_rows(torch.stack([est.reshape(-1), se.reshape(-1)], dim=1), n, group)
+    return tuple(col.reshape((-1,) + tuple(est.shape[1:])) for col in (out[:, 0], out[:, 1]))
+
+
+def _sample_sharded(run, n_total, dim, seed, dev, conditional, local_conditional, group, gather, control=None, scale=1.0):
+    """What every sampling entry point below does: shard, draw this rank's rows of the base samples from the counter-based
+    stream (``ff_normal_fill`` keyed by ``seed`` and the GLOBAL row), take its rows of the conditional, run
+    ``run(z, cond, lo)`` -- under ``_step_control(.., *control)`` where ``control = (global_control, method)`` -- and finish."""
+    from . import _native
+    n = int(n_total)
+    _, _, lo, hi = _shard(n, group)
+    z = _native.normal_fill(hi - lo, int(dim), int(seed), lo, dev, scale=scale)
+    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
+    with contextlib.nullcontext() if control is None else _step_control(n, group, *control):
+        local = run(z, cond, lo)
+    return _finish(local, n, group, gather)
+
+
+def _log_prob_sharded(log_prob, randomised, x, conditional, seed, group, gather, local_x, n_total, local_conditional,
+                      global_control, return_stderr, solver):
+    """What ``log_prob_sharded`` and ``flow_log_prob_sharded`` do: ``log_prob(rows, cond, **solver, **extra)`` on this
+    rank's rows, ``extra`` keying the probes of a ``randomised`` model by ``seed`` and the global row."""
+    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
+    extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if randomised else {}
+    if return_stderr:
+        extra["return_stderr"] = True
+    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
+        local = log_prob(rows, cond, **solver, **extra)
+    return _finish(local, n, group, gather)
 
 
 def gather_rows(local: torch.Tensor, n_total: int, group=None) -> torch.Tensor:
@@ -197,19 +220,14 @@ def sample_sde_sharded(score_model, shape, conditional: Optional[torch.Tensor] =
     noise index; steps: ``noise="philox"``), so a rank only ever touches its own rows.  One all-gather at the
     end.  ``conditional`` is the full [B, C] tensor (every rank slices its rows); ``local_conditional`` is this rank's
     [hi - lo, C] rows already (a consumer that never materialises the full batch)."""
-    from . import _native
     batch, *dims = shape
     if len(dims) != 1:
         raise NotImplementedError("sample_sde_sharded: only [batch, dim] states are supported")
-    _, _, lo, hi = _shard(batch, group)
-    dev = next(score_model.model.parameters()).device
-    # the prior is Normal(0, scale) (diffusion.py:1003, 1093)
     sde = score_model.sde
-    scale = float(sde.sigma_max) if hasattr(sde, "sigma_max") else 1.0
-    x = _native.normal_fill(hi - lo, dims[0], int(seed), lo, dev, scale=scale)
-    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
-    local = score_model._sample_sde_from(x, None, cond, steps, rng=(int(seed), lo))
-    return _finish(local, batch, group, gather)
+    scale = float(sde.sigma_max) if hasattr(sde, "sigma_max") else 1.0      # the prior is Normal(0, scale) (diffusion.py:1003, 1093)
+    run = lambda x, cond, lo: score_model._sample_sde_from(x, None, cond, steps, rng=(int(seed), lo))
+    return _sample_sharded(run, batch, dims[0], seed, next(score_model.model.parameters()).device, conditional,
+                           local_conditional, group, gather, scale=scale)
 
 
 def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,
@@ -232,16 +250,10 @@ def log_prob_sharded(score_model, x: Optional[torch.Tensor] = None, conditional:
     ``ScoreModel.solve_odes_forward``): returns ``(log_p [B, 1], stderr [B, 1])``; the two are gathered as the columns of
     one [rows, 2] tensor, so there is still one all-gather.  With ``gather=False`` it returns
     ``((log_p, stderr), (lo, hi))``: this rank's rows of both, and their bounds."""
-    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
     randomised = any(getattr(score_model, k, False) for k in ("hutch", "hutchpp", "xtrace"))
-    extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if randomised else {}
-    if return_stderr:
-        extra["return_stderr"] = True
-    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
-        local = score_model.log_prob(rows, conditional=cond, **solver, **extra)
-    if return_stderr:
-        return _finish_with_stderr(local, n, group, gather)
-    return _finish(local, n, group, gather)
+    return _log_prob_sharded(lambda rows, cond, **kw: score_model.log_prob(rows, conditional=cond, **kw), randomised, x,
+                             conditional, seed, group, gather, local_x, n_total, local_conditional, global_control,
+                             return_stderr, solver)
 
 
 def sample_ode_sharded(score_model, n_total: int, dim: int, seed: int = 0, conditional: Optional[torch.Tensor] = None,
@@ -252,15 +264,9 @@ def sample_ode_sharded(score_model, n_total: int, dim: int, seed: int = 0, condi
     size transports the same points and a rank only ever touches its rows; one all-gather at the end.  ``**solver`` (atol,
     rtol, method, options) goes to ``sample_ode_from_base`` unchanged; with an adaptive method (the reference's default)
     and ``global_control`` the step size comes from the error norm of the whole batch (``global_step_control``)."""
-    from . import _native
-    n = int(n_total)
-    _, _, lo, hi = _shard(n, group)
-    dev = next(score_model.model.parameters()).device
-    z = _native.normal_fill(hi - lo, int(dim), int(seed), lo, dev)
-    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
-    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
-        local, _ = score_model.sample_ode_from_base(z, conditional=cond, **solver)
-    return _finish(local, n, group, gather)
+    run = lambda z, cond, lo: score_model.sample_ode_from_base(z, conditional=cond, **solver)[0]
+    return _sample_sharded(run, n_total, dim, seed, next(score_model.model.parameters()).device, conditional,
+                           local_conditional, group, gather, control=(global_control, solver.get("method", "dopri5")))
 
 
 # ---- the flows (flowfusion/flow.py:259-306, 386-438; 750-799, 885-941) -- BASELINE configs[3] is worded "sharded over 8xMI355X"
@@ -275,17 +281,11 @@ def flow_sample_sharded(flow, n_total: int, seed: int = 0, conditional: Optional
     shard and returns its bounds).  ``**solver`` (method, options, atol, rtol) goes to ``sample`` unchanged; under an
     adaptive method -- the reference's default -- the step size comes from the error norm of the whole batch
     (``global_step_control``), ``global_control=False``: from the rank's own rows."""
-    from . import _native
     from .flow import _DEFAULT_SAMPLE_METHOD
-    n = int(n_total)
-    _, _, lo, hi = _shard(n, group)
-    dev = next(flow.parameters()).device
-    xT = _native.normal_fill(hi - lo, int(flow.target_dimension), int(seed), lo, dev)
-    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
-    method = solver.get("method") or _DEFAULT_SAMPLE_METHOD
-    with _step_control(n, group, global_control, method):
-        local = flow.sample(xT, **solver) if cond is None else flow.sample(xT, cond, **solver)
-    return _finish(local, n, group, gather)
+    run = lambda xT, cond, lo: flow.sample(xT, **solver) if cond is None else flow.sample(xT, cond, **solver)
+    return _sample_sharded(run, n_total, flow.target_dimension, seed, next(flow.parameters()).device, conditional,
+                           local_conditional, group, gather,
+                           control=(global_control, solver.get("method") or _DEFAULT_SAMPLE_METHOD))
 
 
 def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None, seed: int = 0,
@@ -302,15 +302,9 @@ def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: O
     ``return_stderr=True`` (with ``hutchinson=True``, ``num_probes=K >= 2`` and a fixed-grid ``method``): returns
     ``(log_p [B], stderr [B])``, gathered as the columns of one [rows, 2] tensor -- still one all-gather; with
     ``gather=False``, ``((log_p, stderr), (lo, hi))``: this rank's rows of both, and their bounds."""
-    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
-    extra = {"probe": "philox", "seed": int(seed), "sample_offset": lo} if solver.get("hutchinson") else {}
-    if return_stderr:
-        extra["return_stderr"] = True
-    with _step_control(n, group, global_control, solver.get("method", "dopri5")):
-        local = flow.log_prob(rows, **solver, **extra) if cond is None else flow.log_prob(rows, cond, **solver, **extra)
-    if return_stderr:
-        return _finish_with_stderr(local, n, group, gather)
-    return _finish(local, n, group, gather)
+    log_prob = lambda rows, cond, **kw: flow.log_prob(rows, **kw) if cond is None else flow.log_prob(rows, cond, **kw)
+    return _log_prob_sharded(log_prob, bool(solver.get("hutchinson")), x, conditional, seed, group, gather, local_x, n_total,
+                             local_conditional, global_control, return_stderr, solver)
 
 
 # ---- the symplectic flows (flowfusion/symplectic.py:166-253) ------------------------------------------------------------------
@@ -327,16 +321,11 @@ def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: O
     collective but the final all-gather (``gather=False`` keeps the shard and returns its bounds); a rank without rows is
     fine.  ``conditional`` is the raw [n_total, C] tensor (every rank slices its rows) or ``local_conditional`` this
     rank's rows.  More than one rank over RCCL has not been run on hardware, like everything else multi-rank here."""
-    from . import _native
-    n = int(n_total)
-    _, _, lo, hi = _shard(n, group)
-    dev = next(model.model.parameters()).device
     # the joint state is [q | p]: 2 D columns (a model built without `shift` is asked for its networks' state width)
     dim = 2 * int(model.shift.numel()) if model.shift is not None else int(model._net().dim)
-    x = _native.normal_fill(hi - lo, dim, int(seed), lo, dev)
-    cond = _local_rows(conditional, local_conditional, lo, hi, "conditional")
-    local = model._sample_from(x, cond, int(num_steps), **({} if method == "euler" else {"method": method}))
-    return _finish(local, n, group, gather)
+    run = lambda x, cond, lo: model._sample_from(x, cond, int(num_steps), **({} if method == "euler" else {"method": method}))
+    return _sample_sharded(run, n_total, dim, seed, next(model.model.parameters()).device, conditional, local_conditional,
+                           group, gather)
 
 
 def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditional: Optional[torch.Tensor] = None,

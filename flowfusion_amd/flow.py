@@ -132,6 +132,10 @@ class _FlowBase(nn.Module):
     def _norm_cond(self, conditional):
         return (conditional - self.conditional_shift) / self.conditional_scale
 
+    def _cond_args(self, conditional):
+        """(normalised conditional, ``norm_only``) of a public method's raw ``conditional``; None: the unconditional flow."""
+        return (None, ()) if conditional is None else (self._norm_cond(conditional), (conditional,))
+
     def _solve(self, x, t_span, method, options, mode, atol, rtol, **kw):
         """``odeint(self, x, t_span, ...)``: the flow's solve through the shared dispatcher (odeint.py)."""
         return odeint.solve(self, x, t_span, method, options, mode, atol, rtol, **kw)
@@ -155,12 +159,13 @@ class _FlowBase(nn.Module):
 
     def _fused_forward(self, x, conditional, method, options, hutchinson, atol, rtol, norm_only=(), probe_rng=None,
                        num_probes=1, return_stderr=False):
-        """``norm_only``: the raw conditional, which the reference keeps in the solver state (flow.py:779-796, 855-881).
+        """Returns ``(xT, log_jacobian [B,1], stderr [B,1] or None)``.
+        ``norm_only``: the raw conditional, which the reference keeps in the solver state (flow.py:779-796, 855-881).
         ``num_probes`` (keyword-only extension of ``solve_ode_forward`` / ``log_prob``, with ``hutchinson=True``): the
         divergence is the mean over that many independent +-1 probes per sample, carried by one launch
         (``odeint.solve_hutchinson``); 1 = the reference's single probe.
         ``return_stderr=True`` (keyword-only extension; ``hutchinson=True``, ``num_probes=K >= 2``, a fixed-grid ``method``):
-        returns ``(xT, log_jacobian, stderr [B,1])``, the first two bitwise those of the call without it; ``stderr`` is
+        the public methods return ``(xT, log_jacobian, stderr [B,1])``, the first two bitwise those of the call without it; ``stderr`` is
         ``trace_estimators.hutchinson_stderr`` of the K single-probe estimates, which stay in ``self.dlogp_probes`` [B, K]
         (column k: the log-Jacobian a single-probe solve with probe k alone returns) next to the probes ``self.e``
         [B, K, D].  Same launch, one more store per tangent column (ff_mlp_ode_launch_probes).  Only this path sets
@@ -169,20 +174,47 @@ class _FlowBase(nn.Module):
         ``probe="philox"`` it fills the scaled probes directly, without the +-1 form."""
         t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
         K = trace_estimators.check_num_probes(num_probes, hutchinson, "pass hutchinson=True")
-        if trace_estimators.check_stderr(return_stderr, K, method):
-            xT, logj, d = odeint.solve_hutchinson(self, x, t_span, method, options, atol, rtol, K, probe_rng,
-                                                  keep=lambda e: setattr(self, "e", e), per_probe=True,
-                                                  cond=conditional, norm_only=norm_only)
+        stderr = trace_estimators.check_stderr(return_stderr, K, method)
+        if not hutchinson:
+            xT, logj = self._solve(x, t_span, method, options, MODE_EXACT, atol, rtol, cond=conditional, norm_only=norm_only)
+            return xT, logj.view(-1, 1), None
+        xT, logj, d = odeint.solve_hutchinson(self, x, t_span, method, options, atol, rtol, K, probe_rng,
+                                              keep=(lambda e: setattr(self, "e", e)) if stderr else None, per_probe=stderr,
+                                              cond=conditional, norm_only=norm_only)
+        if stderr:
             self.dlogp_probes = d
-            return xT, logj.view(-1, 1), trace_estimators.hutchinson_stderr(d).view(-1, 1)
-        if hutchinson and K > 1:
-            xT, logj = odeint.solve_hutchinson(self, x, t_span, method, options, atol, rtol, K, probe_rng, cond=conditional,
-                                               norm_only=norm_only)
-            return xT, logj.view(-1, 1)
-        probe = trace_estimators.hutchinson_probe(x, probe_rng) if hutchinson else None
-        xT, logj = self._solve(x, t_span, method, options, MODE_HUTCH if hutchinson else MODE_EXACT, atol, rtol,
-                               cond=conditional, probe=probe, norm_only=norm_only)
-        return xT, logj.view(-1, 1)
+        return xT, logj.view(-1, 1), (trace_estimators.hutchinson_stderr(d).view(-1, 1) if stderr else None)
+
+    # -- the public methods' bodies, written once (``conditional=None``: the unconditional flow) -----------------------------
+    def compute_linear_velocity_field(self, x0, xT, t):
+        x0 = (x0 - self.target_shift) / self.target_scale
+        return (1 - t) * x0 + t * xT, xT - x0
+
+    def _sample(self, xT, conditional, gradients, method, options, atol, rtol):
+        if gradients:
+            raise NotImplementedError("sample(gradients=True) uses odeint_adjoint in the reference "
+                                      f"(flow.py:{'286-295' if conditional is None else '779-788'}); differentiable solves are "
+                                      "out of scope")
+        cond, norm_only = self._cond_args(conditional)
+        return self._fused_sample(xT, cond, method, options, atol, rtol, norm_only=norm_only)
+
+    def _solve_ode_forward(self, x, conditional, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
+                           num_probes, return_stderr):
+        """``(xT, log_jacobian [B,1], stderr [B,1] or None)`` of the normalised points ``x``."""
+        if adjoint:
+            raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
+        cond, norm_only = self._cond_args(conditional)
+        return self._fused_forward(x, cond, method, options, hutchinson, atol, rtol, norm_only=norm_only,
+                                   probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson), num_probes=num_probes,
+                                   return_stderr=return_stderr)
+
+    def _log_prob(self, x, conditional, *solver):
+        """``(log_p [B], stderr [B] or None)`` of target-space points; ``solver``: the rest of ``_solve_ode_forward``."""
+        x = (x - self.target_shift) / self.target_scale
+        xT, logj, se = self._solve_ode_forward(x, conditional, *solver)
+        base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
+        logp = base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
+        return logp, (None if se is None else se.squeeze(1))
 
 
 class ODEFlow(_FlowBase):
@@ -217,18 +249,11 @@ class ODEFlow(_FlowBase):
     def forward(self, t, states):
         return self.dynamics(t, states)
 
-    def compute_linear_velocity_field(self, x0, xT, t):
-        x0 = (x0 - self.target_shift) / self.target_scale
-        return (1 - t) * x0 + t * xT, xT - x0
-
     # -- fused ------------------------------------------------------------------------------------
     def sample(self, xT: torch.Tensor, gradients: bool = False, method: Optional[str] = None,
                options: Optional[dict] = None, atol: float = 1e-9, rtol: float = 1e-7):
         """Transport base samples xT (t=1) to the target (t=0), then ``* target_scale + target_shift``."""
-        if gradients:
-            raise NotImplementedError("sample(gradients=True) uses odeint_adjoint in the reference "
-                                      "(flow.py:286-295); differentiable solves are out of scope")
-        return self._fused_sample(xT, None, method, options, atol, rtol)
+        return self._sample(xT, None, gradients, method, options, atol, rtol)
 
     def solve_ode_forward(self, x, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                           options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
@@ -237,11 +262,9 @@ class ODEFlow(_FlowBase):
         """Integrate t: 0 -> 1 with the divergence; returns ``(xT, log_jacobian[B,1])`` (flow.py:308-384).
         ``probe`` / ``seed`` / ``sample_offset``: see ``_probe_rng``; ``num_probes`` / ``return_stderr``: see
         ``_fused_forward``."""
-        if adjoint:
-            raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
-        return self._fused_forward(x, None, method, options, hutchinson, atol, rtol,
-                                   probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson), num_probes=num_probes,
-                                   return_stderr=return_stderr)
+        out = self._solve_ode_forward(x, None, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
+                                      num_probes, return_stderr)
+        return out if return_stderr else out[:2]
 
     def log_prob(self, x, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
@@ -249,13 +272,9 @@ class ODEFlow(_FlowBase):
                  return_stderr: bool = False):
         """Log-density of target-space points, shape [B] (flow.py:386-438); with ``return_stderr=True`` (see
         ``_fused_forward``) ``(log_p [B], stderr [B])``."""
-        x = (x - self.target_shift) / self.target_scale
-        out = self.solve_ode_forward(x, atol, rtol, method, options, adjoint, hutchinson=hutchinson, probe=probe, seed=seed,
-                                     sample_offset=sample_offset, num_probes=num_probes, return_stderr=return_stderr)
-        xT, logj = out[0], out[1]
-        base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
-        logp = base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
-        return (logp, out[2].squeeze(1)) if return_stderr else logp
+        out = self._log_prob(x, None, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
+                             num_probes, return_stderr)
+        return out if return_stderr else out[0]
 
 
 class ConditionalODEFlow(_FlowBase):
@@ -300,38 +319,24 @@ class ConditionalODEFlow(_FlowBase):
     def forward(self, t, states):
         return self.dynamics(t, states)
 
-    def compute_linear_velocity_field(self, x0, xT, t):
-        x0 = (x0 - self.target_shift) / self.target_scale
-        return (1 - t) * x0 + t * xT, xT - x0
-
     # -- fused ------------------------------------------------------------------------------------
     def sample(self, xT, conditional, gradients: bool = False, method: Optional[str] = None,
                options: Optional[dict] = None, atol: float = 1e-9, rtol: float = 1e-7):
-        if gradients:
-            raise NotImplementedError("sample(gradients=True) uses odeint_adjoint in the reference "
-                                      "(flow.py:779-788); differentiable solves are out of scope")
-        return self._fused_sample(xT, self._norm_cond(conditional), method, options, atol, rtol, norm_only=(conditional,))
+        return self._sample(xT, conditional, gradients, method, options, atol, rtol)
 
     def solve_ode_forward(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5,
                           method: str = "dopri5", options: Optional[dict] = None, adjoint: bool = False,
                           hutchinson: bool = False, *, probe: str = "torch", seed: Optional[int] = None,
                           sample_offset: int = 0, num_probes: int = 1, return_stderr: bool = False):
-        if adjoint:
-            raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
-        return self._fused_forward(x, self._norm_cond(conditional), method, options, hutchinson, atol, rtol,
-                                   norm_only=(conditional,), probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson),
-                                   num_probes=num_probes, return_stderr=return_stderr)
+        out = self._solve_ode_forward(x, conditional, atol, rtol, method, options, adjoint, hutchinson, probe, seed,
+                                      sample_offset, num_probes, return_stderr)
+        return out if return_stderr else out[:2]
 
     def log_prob(self, x, conditional, atol: float = 1e-5, rtol: float = 1e-5, method: str = "dopri5",
                  options: Optional[dict] = None, adjoint: bool = False, hutchinson: bool = False, *,
                  probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0, num_probes: int = 1,
                  return_stderr: bool = False):
         """With ``return_stderr=True`` (see ``_fused_forward``) ``(log_p [B], stderr [B])``."""
-        x = (x - self.target_shift) / self.target_scale
-        out = self.solve_ode_forward(x, conditional, atol, rtol, method, options, adjoint,
-                                     hutchinson=hutchinson, probe=probe, seed=seed, sample_offset=sample_offset,
-                                     num_probes=num_probes, return_stderr=return_stderr)
-        xT, logj = out[0], out[1]
-        base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
-        logp = base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
-        return (logp, out[2].squeeze(1)) if return_stderr else logp
+        out = self._log_prob(x, conditional, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
+                             num_probes, return_stderr)
+        return out if return_stderr else out[0]

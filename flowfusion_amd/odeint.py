@@ -14,19 +14,28 @@ from __future__ import annotations
 
 import torch
 
-from . import _native, adaptive, device_adaptive, solvers
-from ._native import MODE_EXACT, MODE_STATE
+from . import _native, adaptive, device_adaptive, solvers, trace_estimators
+from ._native import MODE_EXACT, MODE_HUTCH, MODE_STATE
 from .fused import require_fp32
 from .generic import ModuleStepper, _need_gpu
 from .host_stepper import RowStepper
 
 
+def _fixed_grid(front, net, x, t_span, method, options, mode, **launch):
+    """The fused fixed-grid solve: the evaluation table (cached on the device; built per call where a ``grid_constructor``
+    may make it depend on y0), then ONE ``net.integrate(x, table, mode, **launch)``, whose result it returns."""
+    if (options or {}).get("grid_constructor") is not None:
+        table = front._ode_table(t_span, method, options, mode, y0=x).to(x.device)
+    else:
+        key = (tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items())), mode) + front._schedule_key()
+        table = net.cached_table(key, x.device, lambda: front._ode_table(t_span, method, options, mode))
+    return net.integrate(x, table, mode, stage_slots=solvers.resolve_method(method).stages, **launch)
+
+
 def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=None, norm_only=(), estimator=None,
-          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None, per_probe=False):
+          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None):
     """``odeint(front, x, t_span, method=, atol=, rtol=, options=)``; returns (y [B, D], dlogp [B] or None) and sets
-    ``front.last_solver_stats`` (fused fixed-grid solves leave it alone).  ``per_probe=True`` (fused fixed-grid MODE_HUTCH
-    solves only; ``solve_hutchinson`` is the caller): returns (y, dlogp, per-probe divergences [B, K]) of the kernel's
-    probes as given (ff_mlp_ode_launch_probes).
+    ``front.last_solver_stats`` (fused fixed-grid solves leave it alone).
 
     ``norm_only``: state components the reference carries with a zero derivative (a flow's raw conditional), seen by the
     adaptive error norm only.  ``estimator = (kind, probes)``: a Hutch++ / XTrace solve in MODE_EXACT (``div_fn(A)`` is its
@@ -38,18 +47,9 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
     fused = front._fusable()
     net = front._net() if fused else None
     adaptive_method = method in solvers.ALL_ADAPTIVE
-    if per_probe and not (fused and estimator is None and not adaptive_method):
-        raise ValueError("per_probe=True: per-probe divergences come from the fused fixed-grid launch only")
     if fused and estimator is None and not adaptive_method:
-        key = (tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items())), mode) + front._schedule_key()
-        if (options or {}).get("grid_constructor") is not None:      # the grid may depend on y0: built per call
-            table = front._ode_table(t_span, method, options, mode, y0=x).to(x.device)
-        else:
-            table = net.cached_table(key, x.device, lambda: front._ode_table(t_span, method, options, mode))
-        out = net.integrate(x, table, mode, cond=cond, probe=probe, stage_slots=solvers.resolve_method(method).stages,
-                            in_shift=in_shift, in_scale=in_scale, out_scale=out_scale, out_shift=out_shift, per_probe=per_probe)
-        if per_probe:
-            return out[0], out[1], out[2]
+        out = _fixed_grid(front, net, x, t_span, method, options, mode, cond=cond, probe=probe, in_shift=in_shift,
+                          in_scale=in_scale, out_scale=out_scale, out_shift=out_shift)
         return out[0], (out[1] if mode != MODE_STATE else None)
     if in_shift is not None:
         x = (x - in_shift) / in_scale
@@ -100,12 +100,15 @@ PROBE_BUFFER_FLOATS = 1 << 28      # a K-probe device buffer [rows, K, D] holds 
 
 
 def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, probe_rng=None, keep=None, per_probe=False,
-                     **kw):
-    """``solve`` in MODE_HUTCH with ``num_probes`` = K > 1 independent +-1 probes per sample, averaged (extension; the
-    reference has the single probe, which the front ends keep solving as before -- they come here for K > 1 only).
+                     cond=None, norm_only=(), in_shift=None, in_scale=None):
+    """``solve`` in MODE_HUTCH with ``num_probes`` = K >= 1 independent +-1 probes per sample, averaged; every Hutchinson
+    log-density solve of the front ends.  Returns (y, dlogp, d): ``d`` [B, K] with ``per_probe``, else None.
     ``probe_rng``: None = torch's generator, or (seed, global row of row 0) = the counter-based stream
-    (trace_estimators.hutchinson_probe).  ``keep(e)`` receives the +-1 probes [B, K, D] -- before the solve where it is one
+    (trace_estimators.hutchinson_probe).  ``keep(e)`` receives the +-1 probes -- before the solve where it is one
     launch sequence (ScoreModel.forward reads them on the generic route), after it where the rows were cut.
+
+    K = 1 is the reference's single probe: ``hutchinson_probe(x, probe_rng)`` [B, D] handed to ``solve`` as it is (states
+    of any rank that route takes, every precision, never cut).  What follows is K > 1 (extension), probes [B, K, D].
 
     The fused kernel carries the K probes of a sample in K tangent columns of its tile (ff_ode_args.tangent_count) and
     returns the SUM of their p^T J p, so it gets the probes times 1/sqrt(K).  On fixed grids the rows are cut so that a
@@ -115,26 +118,24 @@ def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, 
     bounds device buffers only: torch's probes are drawn as ONE ``sign(randn(B, K, D))`` on the host (a row cut must
     not change which numbers a seed gives), and ``keep`` is handed the whole [B, K, D] set.
 
-    ``per_probe=True`` (fixed grids; the front ends' ``return_stderr``): returns (y, dlogp, d [B, K]) with y and dlogp
-    bitwise those of the call without it and ``d[b, k]`` what a single-probe solve with probe k alone gives.  Fused: the
+    ``per_probe=True`` (fixed grids, K >= 2; the front ends' ``return_stderr``): y and dlogp are bitwise those of the call
+    without it and ``d[b, k]`` is what a single-probe solve with probe k alone gives.  Fused: the
     same launch also stores every tangent column's own integral (ff_mlp_ode_launch_probes); the kernel sees the probes
     times 1/sqrt(K), so its output is scaled by K.  Where the rows are cut the pieces are concatenated.  A network on the
     generic route (torch evaluates the module) makes the K-probe pass as before and then K single-probe passes over the
     same state and grid, one per probe -- K + 1 passes instead of one; the module's right-hand side keeps returning one
     divergence per row."""
-    from . import trace_estimators
-    from ._native import MODE_HUTCH
     K = int(num_probes)
-    if K < 2:
-        raise ValueError("solve_hutchinson is the K > 1 route; a single probe is solve(..., MODE_HUTCH, probe=e)")
+    if K < 1 or (per_probe and K < 2):
+        raise ValueError(f"num_probes={num_probes}: at least one probe per sample, two for per_probe=True")
     if per_probe and method in solvers.ALL_ADAPTIVE:
         raise ValueError(f"per_probe=True with the adaptive method={method!r}: per-probe divergences are carried by fixed-grid "
                          "solves only (method=\"rk4\" / \"dopri5_fixed\" with options={\"step_size\": h})")
-    if x.dim() != 2:
+    if K > 1 and x.dim() != 2:
         raise NotImplementedError("num_probes > 1: only [batch, dim] states")
     fused = front._fusable()
-    if fused:
-        net = front._net()
+    net = front._net() if fused else None
+    if fused and K > 1:
         if net.precision != "f32":
             raise ValueError(f"num_probes={K} with precision={net.precision!r}: the split-precision kernels carry one probe per "
                              "sample; use precision='f32'")
@@ -142,63 +143,69 @@ def solve_hutchinson(front, x, t_span, method, options, atol, rtol, num_probes, 
         if K > tile - 1:
             raise ValueError(f"num_probes={K}: the kernel of this network holds a sample and its probes in the {tile} columns of "
                              f"one tile, so at most {tile - 1} probes; use num_probes <= {tile - 1} (or the exact trace)")
-    B, D = x.shape
-    scale = K ** -0.5
-    rows = B
+    B = x.shape[0]
+    rows = max(1, B)
     # (a grid_constructor may build the grid from y0 -- the batch it is handed: such a solve is not cut either)
-    if fused and method not in solvers.ALL_ADAPTIVE and (options or {}).get("grid_constructor") is None:
-        rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D))
+    if K > 1 and fused and method not in solvers.ALL_ADAPTIVE and (options or {}).get("grid_constructor") is None:
+        rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * x.shape[1]))
+    pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
+    scale = K ** -0.5
+    whole_cpu = torch.sign(torch.randn(B, K, x.shape[1])) if K > 1 and probe_rng is None else None      # (the reference's draw, with a K axis)
 
-    def draw(r0, r1, whole_cpu):
+    def draw(r0, r1):
         """(+-1 probes or None, the kernel's probes) of rows [r0, r1)."""
+        if K == 1:
+            e = trace_estimators.hutchinson_probe(x, probe_rng)
+            return e, e
         if probe_rng is None:
             e = whole_cpu[r0:r1].to(x.device)
         elif keep is None and (fused or not per_probe):      # nobody asks for the +-1 form: fill the scaled probes directly
-            return None, _native.probe_fill(r1 - r0, K, D, probe_rng[0], probe_rng[1] + r0, x.device, scale=scale)
+            return None, _native.probe_fill(r1 - r0, K, x.shape[1], probe_rng[0], probe_rng[1] + r0, x.device, scale=scale)
         else:
             e = trace_estimators.hutchinson_probe(x[r0:r1], (probe_rng[0], probe_rng[1] + r0), K)
         return e, e * scale
 
-    whole_cpu = torch.sign(torch.randn(B, K, D)) if probe_rng is None else None      # (the reference's draw, with a K axis)
-    if rows >= B:
-        e, p = draw(0, B, whole_cpu)
+    whole = len(pieces) == 1
+    outs, es = [], []
+    for r0, r1 in pieces:
+        e, p = draw(r0, r1)
+        if whole and keep is not None:
+            keep(e)
+        kw = dict(cond=cond if whole or cond is None else cond[r0:r1], in_shift=in_shift, in_scale=in_scale)
+        xs = x if whole else x[r0:r1]
+        if not per_probe:
+            outs.append(solve(front, xs, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, norm_only=norm_only, **kw)
+                        + (None,))
+        elif fused:                 # the same launch stores every tangent column's own integral
+            require_fp32(front, xs, kw["cond"], p, what="an ODE solve")
+            y, lp, d, _ = _fixed_grid(front, net, xs, t_span, method, options, MODE_HUTCH, probe=p, per_probe=True, **kw)
+            outs.append((y, lp, d * float(K)))
+        else:
+            outs.append(_generic_per_probe(front, xs, t_span, method, options, atol, rtol, e, p, keep, norm_only, kw))
+        es.append(e)
+    if not whole and keep is not None:
+        keep(torch.cat(es))
+    cat = (lambda ts: ts[0]) if whole else torch.cat
+    y, lp, d = zip(*outs)
+    return cat(y), cat(lp), (cat(d) if per_probe else None)
+
+
+def _generic_per_probe(front, x, t_span, method, options, atol, rtol, e, p, keep, norm_only, kw):
+    """Per-probe divergences of a network on the generic route: the K-probe pass (probes ``p``), then one single-probe pass
+    per +-1 probe ``e[:, k]`` (a front end that reads the probe from its own attribute -- ScoreModel.forward -- is handed
+    each probe through ``keep``, and the whole set again at the end); returns (y, dlogp, d [B, K])."""
+    y, lp = solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, norm_only=norm_only, **kw)
+    cols = []
+    try:
+        for k in range(e.shape[1]):
+            ek = e[:, k].contiguous()
+            if keep is not None:
+                keep(ek)
+            cols.append(solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=ek, norm_only=norm_only, **kw)[1])
+    finally:                    # whatever a pass raised, the front end holds the whole [B, K, D] set again
         if keep is not None:
             keep(e)
-        if not per_probe:
-            return solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kw)
-        if fused:
-            y, lp, d = solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, per_probe=True, **kw)
-            return y, lp, d * float(K)
-        # generic route: the K-probe pass, then one single-probe pass per probe (a front end that reads the probe from its
-        # own attribute -- ScoreModel.forward -- is handed each probe through `keep`, and the whole set again at the end)
-        y, lp = solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, **kw)
-        cols = []
-        try:
-            for k in range(K):
-                ek = e[:, k].contiguous()
-                if keep is not None:
-                    keep(ek)
-                cols.append(solve(front, x, t_span, method, options, MODE_HUTCH, atol, rtol, probe=ek, **kw)[1])
-        finally:                    # whatever a pass raised, the front end holds the whole [B, K, D] set again
-            if keep is not None:
-                keep(e)
-        return y, lp, torch.stack(cols, dim=1)
-    ys, lps, es, ds = [], [], [], []
-    for r0 in range(0, B, rows):
-        r1 = min(B, r0 + rows)
-        e, p = draw(r0, r1, whole_cpu)
-        kc = dict(kw)
-        if kc.get("cond") is not None:
-            kc["cond"] = kc["cond"][r0:r1]
-        out = solve(front, x[r0:r1], t_span, method, options, MODE_HUTCH, atol, rtol, probe=p, per_probe=per_probe, **kc)
-        ys.append(out[0]), lps.append(out[1]), es.append(e)
-        if per_probe:
-            ds.append(out[2] * float(K))
-    if keep is not None:
-        keep(torch.cat(es))
-    if per_probe:
-        return torch.cat(ys), torch.cat(lps), torch.cat(ds)
-    return torch.cat(ys), torch.cat(lps)
+    return y, lp, torch.stack(cols, dim=1)
 
 
 def solve_leapfrog(front, x, grid, cond=None):
