@@ -182,6 +182,8 @@ MOMENTUM_NOISE_BASE = 0xFFFD0000   # FF_MOMENTUM_NOISE_BASE (+ k: momentum k of 
 MAX_MOMENTA = 4096                 # 1 <= K <= 4096
 HUTCH_PROBE_NOISE_BASE = 0xFFFC0000  # FF_HUTCH_PROBE_NOISE_BASE (+ k: probe k >= 1 of a K-probe Hutchinson launch, ff_probe_fill)
 MAX_HUTCH_PROBES = 65535           # FF_MAX_HUTCH_PROBES
+OBS_NOISE_BASE = 0xFFFB0000        # FF_OBS_NOISE_BASE (+ k: noise draw k of an observation, ff_observe_expand)
+MAX_OBS_DRAWS = 4096               # FF_MAX_OBS_DRAWS
 
 _lib = None
 
@@ -266,6 +268,13 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_marginal_reduce.restype = L.ff_marginal_reduce_host.restype = ctypes.c_int
     L.ff_marginal_expand.argtypes, L.ff_marginal_expand_host.argtypes = expand + [ctypes.c_void_p], expand
     L.ff_marginal_reduce.argtypes, L.ff_marginal_reduce_host.argtypes = reduce + [ctypes.c_void_p], reduce
+    obs_expand = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                  ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+    lme = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_observe_expand.restype = L.ff_observe_expand_host.restype = ctypes.c_int
+    L.ff_logmeanexp.restype = L.ff_logmeanexp_host.restype = ctypes.c_int
+    L.ff_observe_expand.argtypes, L.ff_observe_expand_host.argtypes = obs_expand + [ctypes.c_void_p], obs_expand
+    L.ff_logmeanexp.argtypes, L.ff_logmeanexp_host.argtypes = lme + [ctypes.c_void_p], lme
     L.ff_mlp_ode_adaptive.restype = ctypes.c_int
     L.ff_mlp_ode_adaptive.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.POINTER(AdaptConfig),
                                       ctypes.POINTER(AdaptBuffers), ctypes.c_double, ctypes.c_double, ctypes.c_int32,
@@ -559,6 +568,69 @@ def marginal_reduce(z1: torch.Tensor, num_momenta: int, seed: int, sample_offset
                      _chk(out, "out", dev), _chk(ess, "ess", dev)))
     if rc != FF_OK:
         raise _err(rc, "ff_marginal_reduce")
+    return out
+
+
+def observe_expand(x: torch.Tensor, noise_std: torch.Tensor, num_draws: int, seed: int, sample_offset: int = 0,
+                   cond: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """ff_observe_expand: (y [B K, D], cond_out [B K, C] or None) from ``x`` [B, D]: row r K + k is
+    ``x[r] - noise_std[r] * z`` with z noise draw k of global row sample_offset + r (two fp32 roundings), and ``cond[r]``.
+    ``noise_std``: [D] (one vector for every row) or [B, D].  Device tensors on the current stream; CPU tensors go to
+    ff_observe_expand_host."""
+    dev = x.device
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise RuntimeError(f"observe_expand: x has shape {tuple(x.shape)}, expected [B, D >= 1]")
+    B, D = x.shape
+    K = int(num_draws)
+    if not 1 <= K <= MAX_OBS_DRAWS:
+        raise ValueError(f"num_draws={num_draws}: 1 .. {MAX_OBS_DRAWS} noise draws per data point")
+    if tuple(noise_std.shape) == (D,):
+        stride = 0
+    elif tuple(noise_std.shape) == (B, D):
+        stride = D
+    else:
+        raise RuntimeError(f"observe_expand: noise_std has shape {tuple(noise_std.shape)}, expected [{D}] or [{B}, {D}]")
+    if cond is not None and (cond.dim() != 2 or cond.shape[0] != B or cond.shape[1] < 1):
+        raise RuntimeError(f"observe_expand: cond has shape {tuple(cond.shape)}, expected [{B}, C >= 1]")
+    C = 0 if cond is None else int(cond.shape[1])
+    y = torch.empty(B * K, D, dtype=torch.float32, device=dev)
+    cond_out = None if cond is None else torch.empty(B * K, C, dtype=torch.float32, device=dev)
+    ptrs = (_chk(x, "x", dev), _chk(noise_std, "noise_std", dev), _chk(cond, "cond", dev))
+    if B == 0:
+        return y, cond_out
+    L = lib()
+    rc = _on_stream(dev, L.ff_observe_expand, L.ff_observe_expand_host,
+                    (ptrs[0], ptrs[1], stride, ptrs[2], B, D, C, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset),
+                     y.data_ptr(), 0 if cond is None else cond_out.data_ptr()))
+    if rc != FF_OK:
+        raise _err(rc, "ff_observe_expand")
+    return y, cond_out
+
+
+def logmeanexp(lp: torch.Tensor, num_draws: int, out: Optional[torch.Tensor] = None,
+               ess: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ff_logmeanexp: ``out`` [B] = logsumexp over the K consecutive entries of a data point in ``lp`` (B K elements:
+    [B K] or [B K, 1]) - log K, in double, rounded once; ``ess`` [B], if given, takes the effective sample size of the K
+    weights.  ``out`` is allocated if None.  Device tensors on the current stream; CPU tensors go to ff_logmeanexp_host."""
+    dev = lp.device
+    K = int(num_draws)
+    if not 1 <= K <= MAX_OBS_DRAWS:
+        raise ValueError(f"num_draws={num_draws}: 1 .. {MAX_OBS_DRAWS} noise draws per data point")
+    if lp.numel() % K or lp.dim() > 2 or (lp.dim() == 2 and lp.shape[1] != 1):
+        raise RuntimeError(f"logmeanexp: lp has shape {tuple(lp.shape)}, expected [B * {K}] or [B * {K}, 1]")
+    B = lp.numel() // K
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    for t, name in ((out, "out"), (ess, "ess")):
+        if t is not None and t.numel() != B:
+            raise RuntimeError(f"logmeanexp: {name} has {t.numel()} elements for {B} data points")
+    ptrs = (_chk(lp, "lp", dev), _chk(out, "out", dev), _chk(ess, "ess", dev))
+    if B == 0:
+        return out
+    L = lib()
+    rc = _on_stream(dev, L.ff_logmeanexp, L.ff_logmeanexp_host, (ptrs[0], B, K, ptrs[1], ptrs[2]))
+    if rc != FF_OK:
+        raise _err(rc, "ff_logmeanexp")
     return out
 
 

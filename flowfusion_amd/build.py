@@ -297,6 +297,7 @@ const int g_n_pair_kernels = {len(PAIR_INSTANCES)};
     files.append(CSRC / "ff_trace.hip")
     files.append(CSRC / "ff_marginal.hip")
     files.append(CSRC / "ff_probe.hip")
+    files.append(CSRC / "ff_observe.hip")
     return files
 
 

@@ -680,6 +680,31 @@ class ScoreModel(nn.Module):
         logp = lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
         return (logp, out[2]) if return_stderr else logp
 
+    @torch.no_grad()
+    def log_prob_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-4, rtol=1e-4, method="dopri5",
+                       options={"min_step": 1e-6}, *, seed=None, sample_offset=0, chunk_points=None, return_ess=False,
+                       num_probes=1):
+        """Extension: the log-density of noisy observations.  ``x`` [B, D] (fp32, on the GPU) was measured with Gaussian
+        errors of known standard deviation ``noise_std`` ([B, D], [D] or a scalar; finite, >= 0), so what a likelihood
+        needs is the convolved density ``p_obs(x | noise_std) = E_{z ~ N(0, I)}[p(x - noise_std z)]``.  Returns its estimate
+        from ``num_draws`` = K draws per point, ``logsumexp_k log p(x - noise_std z_k) - log K`` [B, 1]; with
+        ``return_ess=True`` ``(log_p [B, 1], ess [B])``, ess the effective sample size of the K weights, in (0, K].
+        ``log_prob`` itself (``conditional``, ``atol``, ``rtol``, ``method``, ``options``, ``num_probes`` as there) runs on
+        the B K expanded rows; ``seed`` / ``sample_offset`` / ``chunk_points`` and the chunking rules:
+        ``odeint.log_prob_noisy``.  With ``noise_std = 0, num_draws = 1`` this is ``log_prob`` bit for bit.
+
+        A model built with ``hutchinson=True`` takes the probes of the expanded rows from ``probe="philox"`` under the same
+        ``seed``, keyed by the expanded global row.  Mind what it estimates: the Hutchinson divergence is unbiased for
+        log p, but here it sits inside an exponent, and E[exp(noisy)] > exp(E[noisy]) -- the estimate of p_obs is biased
+        upwards by about half the variance of the divergence estimate (``num_probes`` shrinks it).  Exact-trace models are
+        the clean case.  Hutch++ / XTrace models go through their ``log_prob`` as they are (probes from torch's generator
+        per chunk)."""
+        rows = lambda y, c, extra: self.log_prob(y, conditional=c, atol=atol, rtol=rtol, method=method, options=options,
+                                                 num_probes=num_probes, **extra)
+        out = odeint.log_prob_noisy(rows, bool(self.hutch), x, noise_std, conditional, num_draws, method, seed,
+                                    sample_offset, chunk_points, return_ess)
+        return (out[0].view(-1, 1), out[1]) if return_ess else out.view(-1, 1)
+
 
 # ------------------------------------------------------------------------------------------------
 # population-model wrappers (affine pre/post-processing; reference: diffusion.py:1466-1848)
@@ -712,11 +737,26 @@ class _PopulationModel(nn.Module):
         # the reference ignores `steps` here and always takes 100 (diffusion.py:1608)
         return self.score_model.sample_sde(shape, conditional=self._cond(conditional), steps=100) * self.scale + self.shift
 
-    def _log_prob(self, x, conditional, atol, rtol, num_probes):
+    def _log_prob(self, x, conditional, atol, rtol, num_probes, probe_rng=None):
         # the reference does not forward self.method here: the solver default applies (diffusion.py:1633-1635)
         xT, lp, _ = self.score_model._solve_forward(x, self._cond(conditional), atol, rtol, "dopri5", self.options,
-                                                    in_shift=self.shift, in_scale=self.scale, num_probes=num_probes)
+                                                    in_shift=self.shift, in_scale=self.scale, num_probes=num_probes,
+                                                    probe_rng=probe_rng)
         return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), 1, keepdim=True)
+
+    @torch.no_grad()
+    def _log_prob_noisy(self, x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
+                        return_ess, num_probes):
+        """``log_prob_noisy`` of the two wrappers: ``ScoreModel.log_prob_noisy`` around this wrapper's own ``log_prob`` --
+        the noise lives in the data space of ``x``, before ``(x - shift) / scale``, and the expanded rows take the affine
+        map where every row of ``log_prob`` does.  The solve is hard-wired to adaptive dopri5, like
+        ``log_prob``'s: all B K rows are one solve, and ``chunk_points`` raises."""
+        def rows(y, c, extra):
+            rng = (extra["seed"], extra["sample_offset"]) if extra else None
+            return self._log_prob(y, c, atol, rtol, num_probes, probe_rng=rng)
+        out = odeint.log_prob_noisy(rows, bool(self.score_model.hutch), x, noise_std, conditional, num_draws, "dopri5",
+                                    seed, sample_offset, chunk_points, return_ess)
+        return (out[0].view(-1, 1), out[1]) if return_ess else out.view(-1, 1)
 
 
 class PopulationModelDiffusion(_PopulationModel):
@@ -739,6 +779,15 @@ class PopulationModelDiffusion(_PopulationModel):
         options={"step_size": h}, num_probes=K, return_stderr=True)`` on the normalised points is the route.)
         ``num_probes`` (extension): see ``ScoreModel.solve_odes_forward``; a model built with ``hutchinson=True``."""
         return self._log_prob(x, None, atol, rtol, num_probes)
+
+    def log_prob_noisy(self, x, noise_std, num_draws=16, atol=1e-5, rtol=1e-5, *, seed=None, sample_offset=0,
+                       chunk_points=None, return_ess=False, num_probes=1):
+        """Extension: ``log_prob`` of observations ``x`` measured with Gaussian errors ``noise_std`` (in the units of ``x``),
+        from ``num_draws`` noise draws per point: [B, 1], with ``return_ess=True`` ``(log_p [B, 1], ess [B])``.  See
+        ``ScoreModel.log_prob_noisy`` (a ``hutchinson=True`` model: the bias of a noisy divergence inside an exponent)
+        and ``_log_prob_noisy``."""
+        return self._log_prob_noisy(x, noise_std, None, num_draws, atol, rtol, seed, sample_offset, chunk_points,
+                                    return_ess, num_probes)
 
 
 class PopulationModelDiffusionConditional(_PopulationModel):
@@ -765,3 +814,11 @@ class PopulationModelDiffusionConditional(_PopulationModel):
         """(No ``return_stderr`` here: like the reference's, this solve is hard-wired to adaptive dopri5 -- and this
         wrapper's score model takes the exact trace, which has no probes to spread; ``num_probes`` > 1 is refused there.)"""
         return self._log_prob(x, conditional, atol, rtol, num_probes)
+
+    def log_prob_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-5, rtol=1e-5, *, seed=None,
+                       sample_offset=0, chunk_points=None, return_ess=False, num_probes=1):
+        """Extension: ``log_prob`` of observations ``x`` measured with Gaussian errors ``noise_std`` (in the units of ``x``),
+        from ``num_draws`` noise draws per point; the raw ``conditional`` [B, C] is repeated for the draws.  See
+        ``PopulationModelDiffusion.log_prob_noisy``."""
+        return self._log_prob_noisy(x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
+                                    return_ess, num_probes)

@@ -307,6 +307,58 @@ def flow_log_prob_sharded(flow, x: Optional[torch.Tensor] = None, conditional: O
                              local_conditional, global_control, return_stderr, solver)
 
 
+# ---- noisy observations: score models and flows alike (extension; no counterpart in the reference) --------------------------
+def log_prob_noisy_sharded(model, x: Optional[torch.Tensor] = None, noise_std=None, conditional: Optional[torch.Tensor] = None,
+                           *, local_x: Optional[torch.Tensor] = None, local_noise_std: Optional[torch.Tensor] = None,
+                           n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None, seed: int = 0,
+                           num_draws: int = 16, group=None, gather: bool = True, global_control: bool = True,
+                           return_ess: bool = False, **solver):
+    """``log_prob_noisy`` (``ScoreModel``, ``ODEFlow``, ``ConditionalODEFlow``) of a [B, dim] batch of observations over all
+    ranks; one all-gather at the end, of the model's own result shape ([B, 1] for a score model, [B] for a flow).  ``x``
+    (with ``noise_std`` and ``conditional``) are the full tensors, every rank slicing its rows of the contiguous balanced
+    shards -- or ``local_x`` (with ``local_noise_std`` / ``local_conditional``) this rank's rows already, with ``n_total``
+    the size of the whole batch.  A [B, D] ``noise_std`` is cut like ``x``; a [D] vector or a scalar is replicated (pass it
+    as ``noise_std`` with ``local_x`` too).  The noise draws -- and the probes of a Hutchinson model -- are keyed by
+    ``seed`` and the GLOBAL row (``sample_offset`` = the rank's first row), so with a fixed-grid ``method`` a row's result
+    is bitwise independent of the number of ranks.  Under an adaptive ``method`` (the default) every rank's ``local * K``
+    rows are one solve whose step size comes from the error norm of the WHOLE expanded batch (``global_step_control``;
+    every rank needs at least one row), ``global_control=False``: from the rank's own rows.  ``**solver`` (atol, rtol,
+    method, options, hutchinson, num_probes, chunk_points) goes to ``log_prob_noisy`` unchanged.  ``return_ess=True``:
+    ``(log_p, ess [B])``, the two gathered as the columns of one [rows, 2] tensor -- still one all-gather; with
+    ``gather=False`` ``((log_p, ess), (lo, hi))``: this rank's rows of both, and their bounds."""
+    if local_noise_std is not None and (noise_std is not None or local_x is None):
+        raise ValueError("local_noise_std holds this rank's [rows, dim] of a per-object noise_std: it goes with local_x and "
+                         "excludes `noise_std` (which then is a [dim] vector or a scalar, the same on every rank)")
+    if local_noise_std is None and noise_std is None:
+        raise ValueError("pass noise_std (or local_noise_std with local_x)")
+
+    def run(rows, cond, probe, seed, sample_offset, **kw):
+        lo, hi = sample_offset, sample_offset + rows.shape[0]
+        if local_noise_std is not None:
+            if local_noise_std.shape[0] != hi - lo:
+                raise ValueError(f"local_noise_std must hold exactly this rank's rows [{lo}, {hi})")
+            std = local_noise_std
+        elif torch.is_tensor(noise_std) and noise_std.dim() == 2:
+            if local_x is not None:
+                raise ValueError("a per-object noise_std beside local_x is local_noise_std (this rank's rows)")
+            std = noise_std[lo:hi]
+        else:
+            std = noise_std
+        out = model.log_prob_noisy(rows, std, *(() if cond is None else (cond,)), num_draws=num_draws, seed=seed,
+                                   sample_offset=sample_offset, return_ess=return_ess, **kw)
+        return (out[0], out[1].view_as(out[0])) if return_ess else out
+
+    # (randomised: `_log_prob_sharded` hands `run` the seed and the rank's first row -- the noise needs them with any model)
+    res = _log_prob_sharded(run, True, x, conditional, seed, group, gather, local_x, n_total, local_conditional, global_control,
+                            False, solver)
+    if not return_ess:
+        return res
+    if not gather:
+        (lp, ess), span = res
+        return (lp, ess.reshape(-1)), span
+    return res[0], res[1].reshape(-1)
+
+
 # ---- the symplectic flows (flowfusion/symplectic.py:166-253) ------------------------------------------------------------------
 def symplectic_sample_sharded(model, n_total: int, seed: int = 0, conditional: Optional[torch.Tensor] = None,
                               num_steps: int = 1, group=None, gather: bool = True,

@@ -216,6 +216,28 @@ class _FlowBase(nn.Module):
         logp = base + logj.squeeze(1) - torch.sum(torch.log(self.target_scale))
         return logp, (None if se is None else se.squeeze(1))
 
+    @torch.no_grad()
+    def _log_prob_noisy(self, x, noise_std, conditional, num_draws, atol, rtol, method, options, hutchinson, seed,
+                        sample_offset, chunk_points, return_ess, num_probes):
+        """``log_prob_noisy`` of both flows (extension): target-space points ``x`` [B, D] (fp32, on the GPU) were measured
+        with Gaussian errors of known standard deviation ``noise_std`` ([B, D], [D] or a scalar; finite, >= 0, in the units
+        of ``x``: before ``(x - target_shift) / target_scale``), and a likelihood needs the convolved density
+        ``p_obs(x | noise_std) = E_{z ~ N(0, I)}[p(x - noise_std z)]``.  Returns ``logsumexp_k log p(x - noise_std z_k) -
+        log K`` [B] from ``num_draws`` = K draws per point; with ``return_ess=True`` ``(log_p [B], ess [B])``, ess the
+        effective sample size of the K weights, in (0, K].  The flow's own ``log_prob`` runs on the B K expanded rows
+        (its affine map and ``- sum log target_scale`` apply unchanged; the raw ``conditional`` is repeated for the draws);
+        ``seed`` / ``sample_offset`` / ``chunk_points`` and the chunking rules: ``odeint.log_prob_noisy``.  With
+        ``noise_std = 0, num_draws = 1`` this is ``log_prob`` bit for bit.
+
+        ``hutchinson=True`` takes the probes of the expanded rows from ``probe="philox"`` under the same ``seed``, keyed by
+        the expanded global row.  Mind what it estimates: the Hutchinson divergence is unbiased for log p, but here it sits
+        inside an exponent, and E[exp(noisy)] > exp(E[noisy]) -- the estimate of p_obs is biased upwards by about half the
+        variance of the divergence estimate (``num_probes`` shrinks it).  The exact trace is the clean case."""
+        rows = lambda y, c, extra: self.log_prob(y, *(() if c is None else (c,)), atol=atol, rtol=rtol, method=method,
+                                                 options=options, hutchinson=hutchinson, num_probes=num_probes, **extra)
+        return odeint.log_prob_noisy(rows, bool(hutchinson), x, noise_std, conditional, num_draws, method, seed,
+                                     sample_offset, chunk_points, return_ess)
+
 
 class ODEFlow(_FlowBase):
     """Unconditional flow-matching CNF (reference: flow.py:9-438)."""
@@ -275,6 +297,15 @@ class ODEFlow(_FlowBase):
         out = self._log_prob(x, None, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
                              num_probes, return_stderr)
         return out if return_stderr else out[0]
+
+    def log_prob_noisy(self, x, noise_std, num_draws: int = 16, atol: float = 1e-5, rtol: float = 1e-5,
+                       method: str = "dopri5", options: Optional[dict] = None, *, hutchinson: bool = False,
+                       seed: Optional[int] = None, sample_offset: int = 0, chunk_points: Optional[int] = None,
+                       return_ess: bool = False, num_probes: int = 1):
+        """Log-density [B] of target-space observations with Gaussian errors ``noise_std``, from ``num_draws`` noise draws
+        per point (extension; see ``_log_prob_noisy``)."""
+        return self._log_prob_noisy(x, noise_std, None, num_draws, atol, rtol, method, options, hutchinson, seed,
+                                    sample_offset, chunk_points, return_ess, num_probes)
 
 
 class ConditionalODEFlow(_FlowBase):
@@ -340,3 +371,12 @@ class ConditionalODEFlow(_FlowBase):
         out = self._log_prob(x, conditional, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
                              num_probes, return_stderr)
         return out if return_stderr else out[0]
+
+    def log_prob_noisy(self, x, noise_std, conditional, num_draws: int = 16, atol: float = 1e-5, rtol: float = 1e-5,
+                       method: str = "dopri5", options: Optional[dict] = None, *, hutchinson: bool = False,
+                       seed: Optional[int] = None, sample_offset: int = 0, chunk_points: Optional[int] = None,
+                       return_ess: bool = False, num_probes: int = 1):
+        """Log-density [B] of target-space observations with Gaussian errors ``noise_std``, from ``num_draws`` noise draws
+        per point (extension; see ``_log_prob_noisy``)."""
+        return self._log_prob_noisy(x, noise_std, conditional, num_draws, atol, rtol, method, options, hutchinson, seed,
+                                    sample_offset, chunk_points, return_ess, num_probes)

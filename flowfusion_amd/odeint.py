@@ -228,6 +228,78 @@ def solve_leapfrog(front, x, grid, cond=None):
     return y
 
 
+# ---- extension: the log-density of noisy observations over K noise draws (the front ends' ``log_prob_noisy``) -----------
+OBSERVE_CHUNK_ROWS = 1 << 22        # rows (data points x noise draws) in flight by default on a fixed grid
+
+
+def noise_std_tensor(noise_std, x):
+    """``noise_std`` of a ``log_prob_noisy`` as the contiguous fp32 tensor ff_observe_expand takes, on ``x``'s device: [B, D]
+    or [D] as given, a Python or 0-dim scalar expanded to [D] on the host.  Finite and >= 0, else ValueError."""
+    B, D = x.shape
+    if torch.is_tensor(noise_std) and noise_std.dim() > 0:
+        if tuple(noise_std.shape) not in ((D,), (B, D)):
+            raise ValueError(f"noise_std has shape {tuple(noise_std.shape)}: [{B}, {D}] (per object and dimension), [{D}] (one "
+                             "vector for every object) or a scalar")
+        std = _native.f32_on(noise_std, x.device)
+    else:
+        std = torch.full((D,), float(noise_std), dtype=torch.float32).to(x.device)
+    if not bool((torch.isfinite(std) & (std >= 0)).all()):
+        raise ValueError("noise_std must be finite and >= 0 everywhere (0: that coordinate was measured exactly)")
+    return std
+
+
+def log_prob_noisy(log_prob_rows, randomised, x, noise_std, cond, num_draws, method, seed, sample_offset, chunk_points,
+                   return_ess):
+    """What every front end's ``log_prob_noisy`` does: ``log p_obs(x | noise_std) = log E_{z ~ N(0, I)} p(x - noise_std z)``
+    [B] from K = ``num_draws`` draws per point (with ``return_ess`` also the effective sample size of the K weights [B]).
+    Per chunk of points: ff_observe_expand writes the K rows ``x[r] - noise_std[r] * z_k`` (and repeats ``cond``), the
+    model's own log-density runs on them -- ``log_prob_rows(y, cond_rows, extra)`` -> [rows] or [rows, 1], ``extra`` the
+    keywords that key the probes of a ``randomised`` (Hutchinson) model by ``seed`` and the expanded GLOBAL row,
+    ``probe="philox"`` with ``sample_offset = (sample_offset + lo) K``: a host draw would depend on the chunking --
+    and ff_logmeanexp combines them in double.  The draws come from the counter-based stream keyed by ``seed`` and the
+    global row ``sample_offset + r`` (noise indices FF_OBS_NOISE_BASE + k); ``seed=None`` draws a 63-bit one from torch's
+    default generator.  On a fixed-grid ``method`` the points go through in chunks of ``chunk_points`` (default:
+    ``chunk_points * K <= OBSERVE_CHUNK_ROWS``) with bitwise the same result whatever the chunking; an adaptive method
+    takes its step from the whole batch, so all B K rows are one solve and ``chunk_points`` raises."""
+    K = int(num_draws)
+    if not 1 <= K <= _native.MAX_OBS_DRAWS:
+        raise ValueError(f"num_draws={num_draws}: 1 .. {_native.MAX_OBS_DRAWS} noise draws per data point")
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("log_prob_noisy: x must be a [batch, dim] float32 tensor")
+    B = int(x.shape[0])
+    std = noise_std_tensor(noise_std, x)
+    if method not in solvers.FIXED_METHODS:
+        if chunk_points is not None:
+            raise ValueError(f"chunk_points with method={method!r}: an adaptive solve takes its step size from the error "
+                             "norm of the whole batch, so chunks would change every row's steps; all B * num_draws rows "
+                             "are one solve.  A fixed-grid method (method='rk4' with options={'step_size': h}) processes "
+                             "chunks with bitwise the same result")
+        chunk = max(B, 1)
+    elif chunk_points is None:
+        chunk = max(1, OBSERVE_CHUNK_ROWS // K)
+    else:
+        chunk = int(chunk_points)
+        if chunk < 1:
+            raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    seed, first = int(seed), int(sample_offset)
+    x = x.detach().contiguous()
+    cond = _native.f32_on(cond, x.device)
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    ess = torch.empty(B, dtype=torch.float32, device=x.device) if return_ess else None
+    for lo in range(0, B, chunk):
+        hi = min(B, lo + chunk)
+        y, ck = _native.observe_expand(x[lo:hi], std if std.dim() == 1 else std[lo:hi], K, seed, first + lo,
+                                       None if cond is None else cond[lo:hi])
+        extra = {"probe": "philox", "seed": seed, "sample_offset": (first + lo) * K} if randomised else {}
+        lp = log_prob_rows(y, ck, extra)
+        del y, ck
+        _native.logmeanexp(lp.detach().to(torch.float32).contiguous(), K, out[lo:hi], None if ess is None else ess[lo:hi])
+        del lp
+    return (out, ess) if return_ess else out
+
+
 def _host_adaptive(front, step, x, t, sign, method, options, mode, atol, rtol, norm_only):
     """The host controller around any of the three step functions (``FusedNet`` / ``RowStepper`` / ``ModuleStepper``)."""
     has_lp = mode != MODE_STATE

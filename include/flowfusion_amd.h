@@ -486,6 +486,51 @@ int ff_marginal_expand_host(const float* x, const float* shift, const float* sca
 int ff_marginal_reduce_host(const float* z1, int64_t B, int32_t D, int32_t K, uint64_t seed, int64_t sample_offset,
                             double log_det, float* out_logp, float* out_ess);
 
+/* ---- log-density of noisy observations over K noise draws (csrc/ff_observe.hip, csrc/ff_observe.h) ------------------
+ *
+ * Every log-density of the reference (ScoreModel.log_prob diffusion.py:756-815, ODEFlow.log_prob flow.py:386-438, the
+ * PopulationModelDiffusion wrappers :1633, :1837) is that of an exact point.  An observation xhat = x + n with
+ * n ~ N(0, diag(sigma^2)), sigma known per object and per dimension, has the convolved density
+ *     p_obs(xhat | sigma) = E_{z ~ N(0, I)}[p(xhat - sigma z)]
+ * These two kernels are the ends of its K-draw estimate, around ANY log-density evaluated on the B K rows between them:
+ * data point r, draw k is row r K + k (the K rows of a point are contiguous), 1 <= K <= FF_MAX_OBS_DRAWS.
+ *
+ * ff_observe_expand:  y[r K + k][d]     = x[r][d] - noise_std[r std_row_stride + d] * z(seed, sample_offset + r, FF_OBS_NOISE_BASE + k, d)
+ *                     cond_out[r K + k] = cond[r]
+ *   x [B][D]; noise_std [D] (std_row_stride = 0: one vector for every row) or [B][D] (std_row_stride = D); cond [B][C] or
+ *   NULL (C and cond_out are then ignored); y [B K][D]; cond_out [B K][C].  The product is rounded to fp32, then the
+ *   difference is (no fused multiply-add), and z is bit for bit what ff_normal_fill writes for that noise index and global
+ *   row: the result is bit for bit the torch composition `x - noise_std * z` of K such fills.  One pass, write-only
+ *   beyond x, noise_std and cond; 16-byte accesses where x, noise_std, y are 16-byte aligned and D % 4 == 0 (cond,
+ *   cond_out and C likewise, on their own), a scalar body with the same arithmetic in the same order otherwise.
+ *   FF_ERR_BADARG: x, noise_std or y NULL; B < 0; D < 1; K outside 1 .. FF_MAX_OBS_DRAWS; std_row_stride neither 0 nor D;
+ *   cond given with C < 1 or cond_out NULL.
+ * ff_logmeanexp:      out[r]     = logsumexp_k lp[r K + k] - log K
+ *                     out_ess[r] = (sum_k w_k)^2 / sum_k w_k^2,   w_k = exp(lp[r K + k] - max_k lp[r K + k])
+ *   lp [B K]; out [B]; out_ess [B] or NULL.  The sums run in double and are rounded to fp32 once.  Non-finite input
+ *   follows torch.logsumexp in float64, exactly as ff_marginal_reduce: a NaN in any lp gives NaN, all -inf gives -inf
+ *   (and an effective sample size of NaN: no draw has weight), a +inf gives +inf.  At K = 1 out[r] is lp[r] bit for bit.
+ *   FF_ERR_BADARG: lp or out NULL; B < 0; K outside 1 .. FF_MAX_OBS_DRAWS.
+ * A data point's results do not depend on B, on its position in the batch or on the launch geometry, so a batch may be
+ * processed in chunks (sample_offset + first point of the chunk) or sharded over ranks with bitwise the same results.
+ * All pointers are DEVICE pointers; both enqueue on hip_stream; B == 0 is FF_OK without a launch.  The _host twins run
+ * the same arithmetic (csrc/ff_observe.h) on HOST pointers for tests without a GPU: their normals come through libm and
+ * agree with the device's to rounding, not bit for bit.
+ */
+/* Noise indices reserved for the K noise draws of an observation: draw k of global row g is
+ * z(seed, g, FF_OBS_NOISE_BASE + k, d), k < 4096 -- a range of its own below FF_HUTCH_PROBE_NOISE_BASE, so a seed shared
+ * with the Hutchinson probes of the expanded rows, a prior draw or a momentum gives unrelated noise. */
+#define FF_OBS_NOISE_BASE 0xFFFB0000u
+#define FF_MAX_OBS_DRAWS  4096
+int ff_observe_expand(const float* x, const float* noise_std, int32_t std_row_stride, const float* cond, int64_t B,
+                      int32_t D, int32_t C, int32_t K, uint64_t seed, int64_t sample_offset, float* y, float* cond_out,
+                      void* hip_stream);
+int ff_logmeanexp(const float* lp, int64_t B, int32_t K, float* out, float* out_ess, void* hip_stream);
+int ff_observe_expand_host(const float* x, const float* noise_std, int32_t std_row_stride, const float* cond, int64_t B,
+                           int32_t D, int32_t C, int32_t K, uint64_t seed, int64_t sample_offset, float* y,
+                           float* cond_out);
+int ff_logmeanexp_host(const float* lp, int64_t B, int32_t K, float* out, float* out_ess);
+
 /* ---- Hutch++ / XTrace divergence estimates from recorded Jacobians (csrc/ff_trace.hip, csrc/ff_trace_est.h) ----
  *
  * Replaces the two estimator branches of ScoreModel.forward, diffusion.py:336-400 (Hutch++) and :402-481 (XTrace), for
