@@ -184,6 +184,8 @@ HUTCH_PROBE_NOISE_BASE = 0xFFFC0000  # FF_HUTCH_PROBE_NOISE_BASE (+ k: probe k >
 MAX_HUTCH_PROBES = 65535           # FF_MAX_HUTCH_PROBES
 OBS_NOISE_BASE = 0xFFFB0000        # FF_OBS_NOISE_BASE (+ k: noise draw k of an observation, ff_observe_expand)
 MAX_OBS_DRAWS = 4096               # FF_MAX_OBS_DRAWS
+OBS_RESAMPLE_NOISE_INDEX = 0xFFFA0000  # FF_OBS_RESAMPLE_NOISE_INDEX (the uniforms of ff_weighted_resample: block m >> 2, word m & 3)
+MAX_OBS_SAMPLES = 4096             # FF_MAX_OBS_SAMPLES
 
 _lib = None
 
@@ -275,6 +277,10 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_logmeanexp.restype = L.ff_logmeanexp_host.restype = ctypes.c_int
     L.ff_observe_expand.argtypes, L.ff_observe_expand_host.argtypes = obs_expand + [ctypes.c_void_p], obs_expand
     L.ff_logmeanexp.argtypes, L.ff_logmeanexp_host.argtypes = lme + [ctypes.c_void_p], lme
+    resample = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_weighted_resample.restype = L.ff_weighted_resample_host.restype = ctypes.c_int
+    L.ff_weighted_resample.argtypes, L.ff_weighted_resample_host.argtypes = resample + [ctypes.c_void_p], resample
     L.ff_mlp_ode_adaptive.restype = ctypes.c_int
     L.ff_mlp_ode_adaptive.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.POINTER(AdaptConfig),
                                       ctypes.POINTER(AdaptBuffers), ctypes.c_double, ctypes.c_double, ctypes.c_int32,
@@ -632,6 +638,43 @@ def logmeanexp(lp: torch.Tensor, num_draws: int, out: Optional[torch.Tensor] = N
     if rc != FF_OK:
         raise _err(rc, "ff_logmeanexp")
     return out
+
+
+def weighted_resample(y: torch.Tensor, lp: torch.Tensor, num_draws: int, num_samples: int, seed: int, sample_offset: int = 0,
+                      want_index: bool = True, want_moments: bool = True):
+    """ff_weighted_resample: ``(samples [B, M, D], index [B, M] int32, mean [B, D], var [B, D])`` from the particles ``y``
+    [B K, D] and their log-weights ``lp`` (B K elements: [B K] or [B K, 1]): M = ``num_samples`` multinomial draws of
+    every point's K rows by the weights ``exp(lp - max lp)`` (uniforms of global row sample_offset + r from the
+    counter-based stream), and the weighted mean and variance, in double.  ``index`` is None without ``want_index``,
+    ``mean`` and ``var`` without ``want_moments``.  Device tensors on the current stream; CPU tensors go to
+    ff_weighted_resample_host."""
+    dev = y.device
+    K, M = int(num_draws), int(num_samples)
+    if not 1 <= K <= MAX_OBS_DRAWS:
+        raise ValueError(f"num_draws={num_draws}: 1 .. {MAX_OBS_DRAWS} noise draws per data point")
+    if not 0 <= M <= MAX_OBS_SAMPLES:
+        raise ValueError(f"num_samples={num_samples}: 0 .. {MAX_OBS_SAMPLES} posterior draws per data point")
+    if y.dim() != 2 or y.shape[1] < 1 or y.shape[0] % K:
+        raise RuntimeError(f"weighted_resample: y has shape {tuple(y.shape)}, expected [B * {K}, D >= 1]")
+    rows, D = y.shape
+    if lp.numel() != rows or lp.dim() > 2 or (lp.dim() == 2 and lp.shape[1] != 1):
+        raise RuntimeError(f"weighted_resample: lp has shape {tuple(lp.shape)}, expected [{rows}] or [{rows}, 1]")
+    B = rows // K
+    samples = torch.empty(B, M, D, dtype=torch.float32, device=dev)
+    index = torch.empty(B, M, dtype=torch.int32, device=dev) if want_index else None
+    mean = torch.empty(B, D, dtype=torch.float32, device=dev) if want_moments else None
+    var = torch.empty(B, D, dtype=torch.float32, device=dev) if want_moments else None
+    ptrs = (_chk(y, "y", dev), _chk(lp, "lp", dev))
+    if B == 0 or (M == 0 and not want_moments):             # nothing to compute
+        return samples, index, mean, var
+    L = lib()
+    rc = _on_stream(dev, L.ff_weighted_resample, L.ff_weighted_resample_host,
+                    (ptrs[0], ptrs[1], B, D, K, M, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), samples.data_ptr(),
+                     0 if index is None else index.data_ptr(), 0 if mean is None else mean.data_ptr(),
+                     0 if var is None else var.data_ptr()))
+    if rc != FF_OK:
+        raise _err(rc, "ff_weighted_resample")
+    return samples, index, mean, var
 
 
 def trace_kind_and_probes(kind: str, probes):

@@ -62,6 +62,25 @@ FF_HD void normals4(uint64_t seed, uint64_t gs, uint32_t noise_index, uint32_t b
 #endif
 }
 
+// the four raw words of the same block of the stream, for consumers that want uniforms, not normals: integer arithmetic
+// on both sides, so host and device agree bit for bit
+FF_HD void words4(uint64_t seed, uint64_t gs, uint32_t noise_index, uint32_t blk, uint32_t (&w)[4])
+{
+    w[0] = (uint32_t)gs; w[1] = (uint32_t)(gs >> 32); w[2] = noise_index; w[3] = blk;
+#if defined(__HIP_DEVICE_COMPILE__)
+    philox4x32_10(w, (uint32_t)seed, (uint32_t)(seed >> 32));
+#else
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * w[0], p1 = (uint64_t)0xCD9E8D57u * w[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ w[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ w[3] ^ k1;
+        w[0] = n0; w[1] = (uint32_t)p1; w[2] = n2; w[3] = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+#endif
+}
+
 // q0 = (x - shift) / scale as torch computes it: one fp32 subtraction, one correctly rounded fp32 division
 FF_HD float whiten(float x, const float* shift, const float* scale, int d)
 {

@@ -1,6 +1,7 @@
 // ff_observe.h -- the arithmetic of the K-draw log-density of noisy observations, shared by the gfx950 kernels
-// (ff_observe.hip: observe_expand_kernel / logmeanexp_kernel) and the host entry points the CPU tests call
-// (ff_observe_expand_host / ff_logmeanexp_host, compiled from the host pass of the same file).
+// (ff_observe.hip: observe_expand_kernel / logmeanexp_kernel / weighted_resample_kernel) and the host entry points the
+// CPU tests call (ff_observe_expand_host / ff_logmeanexp_host / ff_weighted_resample_host, compiled from the host pass of
+// the same file).
 //
 // An observation xhat = x + n, n ~ N(0, diag(sigma^2)) with sigma known per object and dimension, has the convolved
 // density p_obs(xhat | sigma) = E_{z ~ N(0, I)}[p(xhat - sigma z)]; the extension estimates it from K draws per point,
@@ -55,6 +56,47 @@ FF_HD int lanes_per_point(int K)
     int g = 1;
     while (g < K && g < 64) g *= 2;
     return g;
+}
+
+// ---- the posterior of a point from its K weighted particles (ff_weighted_resample) ------------------------------------
+// The K rows y_k with weights w_k = exp(lp_k - max lp) are a self-normalised importance sample of p(x | xhat, sigma):
+// M multinomial draws (index m: the smallest k of positive weight whose running sum exceeds u_m W) and the weighted mean
+// and variance, all sums in double.  The uniforms are integer arithmetic on the raw words of the stream: the same bits
+// on host and device.
+constexpr int kMaxSamples = FF_MAX_OBS_SAMPLES;
+
+// a point without a posterior: a NaN or +inf among its log-weights (not (v < inf)), or none above -inf (max = -inf, W = 0)
+FF_HD bool weight_bad(float lp) { return !(lp < INFINITY); }
+
+// w = exp(lp - max) in double: 1 for the maximum itself, 0 for -inf
+FF_HD double weight(float lp, double mx) { return exp((double)lp - mx); }
+
+// u in [0, 1) from a raw word: its upper 24 bits
+FF_HD double resample_uniform(uint32_t word) { return (double)(word >> 8) * 0x1p-24; }
+
+// the four targets u_m W of the samples m = 4 q .. 4 q + 3 of global row gs
+FF_HD void resample_targets(uint64_t seed, uint64_t gs, uint32_t q, double W, double (&t)[4])
+{
+#pragma clang fp contract(off)
+    uint32_t w[4];
+    marginal::words4(seed, gs, FF_OBS_RESAMPLE_NOISE_INDEX, q, w);
+    for (int j = 0; j < 4; ++j) t[j] = resample_uniform(w[j]) * W;
+}
+
+// one draw's share of a block of four dimensions: acc += w v (first moment), acc += w (v - mean)^2 (second, about the
+// double mean: never negative)
+FF_HD void moment1_add(double (&acc)[4], double w, const float (&v)[4])
+{
+#pragma clang fp contract(off)
+    for (int j = 0; j < 4; ++j) acc[j] += w * (double)v[j];
+}
+FF_HD void moment2_add(double (&acc)[4], double w, const float (&v)[4], const double (&mean)[4])
+{
+#pragma clang fp contract(off)
+    for (int j = 0; j < 4; ++j) {
+        const double d = (double)v[j] - mean[j];
+        acc[j] += w * (d * d);
+    }
 }
 
 } // namespace observe

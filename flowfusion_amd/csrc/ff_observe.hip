@@ -8,7 +8,18 @@
 //   ff_logmeanexp       out[r] = logsumexp_k lp[r K + k] - log K and the effective sample size of the K weights.  Written
 //                       in torch ops: a float64 copy, logsumexp, a max, an exp and two sums -- here one read of lp.
 //
-// Both are streaming kernels in the style of ff_marginal.hip (roofline: HBM): grid-stride loops, 16-byte accesses where
+//   ff_weighted_resample  the posterior of observation r from the same K rows and their log-densities: M multinomial
+//                       draws (rows copied bit for bit, and their indices) and the weighted mean and variance.  Written
+//                       in torch ops: a float64 softmax, a cumsum, a searchsorted, a gather and the weighted moments over
+//                       [B K, D] temporaries, on torch's generator -- here one pass over lp and y, uniforms from the
+//                       counter-based stream.  A group of G lanes per point as in the reduction, but every lane holds a
+//                       CONTIGUOUS segment of ceil(K / G) draws: the running sum of the weights is the scan of the
+//                       segment sums over the group plus the lane's own running sum, so the draw a target falls on is
+//                       found by one walk of every lane over its segment (four targets -- one Philox block -- per walk)
+//                       and a minimum over the group.  The moments take one block of four dimensions at a time: every
+//                       lane adds its segment, a butterfly adds the lanes; the variance is a second pass about the mean.
+//
+// All are streaming kernels in the style of ff_marginal.hip (roofline: HBM): grid-stride loops, 16-byte accesses where
 // the pointers and D allow (a scalar body otherwise, same arithmetic in the same order), consecutive lanes on consecutive
 // addresses, no LDS, no atomics.  A row of the expansion is shared by P = lanes_per_row(D) lanes (one block of four
 // dimensions each); a data point of the reduction by a group of G = lanes_per_point(K) lanes (draws k = lane, lane + G,
@@ -120,6 +131,183 @@ __global__ __launch_bounds__(256) void logmeanexp_kernel(const ReduceArgs a)
     }
 }
 
+struct ResampleArgs {
+    const float* y;
+    const float* lp;
+    float* samples;
+    int32_t* index;
+    float* mean;
+    float* var;
+    long long B;
+    int D, K, M;
+    unsigned long long seed;
+    long long sample_offset;
+    int log_g;                      // log2 of the lanes per data point
+    int seg;                        // draws per lane: lane l holds the draws [l seg, (l + 1) seg) below K
+    int vec;                        // y and samples move as 16-byte elements
+};
+
+// the (up to four) dimensions 4 blk .. of one row, zero beyond D
+__device__ __forceinline__ void load_block(const float* row, int d0, int D, int vec, float (&v)[4])
+{
+    if (vec) {
+        const v4f t = *(const v4f*)(row + d0);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = d0 + j < D ? row[d0 + j] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void group_sum4(double (&acc)[4], int G)
+{
+    for (int off = 1; off < G; off <<= 1)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);       // (a + b == b + a: every lane holds the same bits)
+}
+
+__global__ __launch_bounds__(256) void weighted_resample_kernel(const ResampleArgs a)
+{
+    const int G = 1 << a.log_g, K = a.K, D = a.D, M = a.M, nblk = (D + 3) / 4;
+    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = (int)(gtid & (G - 1));
+    const long long ngroups = ((long long)gridDim.x * blockDim.x) >> a.log_g;
+    const int k0 = lane * a.seg < K ? lane * a.seg : K, k1 = k0 + a.seg < K ? k0 + a.seg : K;
+    const float qnan = __builtin_nanf("");
+    // (the bound is uniform over a group, as in logmeanexp_kernel: the shuffles below always find their partners)
+    for (long long pt = gtid >> a.log_g; pt < a.B; pt += ngroups) {
+        const float* lr = a.lp + pt * K;
+        const float* yr = a.y + pt * K * D;
+        float* sr = a.samples ? a.samples + pt * M * D : nullptr;
+        int32_t* ir = a.index ? a.index + pt * M : nullptr;
+
+        // the maximum (exact in any order) and whether the point has a posterior at all
+        float mx = -INFINITY;
+        int bad = 0;
+        for (int k = k0; k < k1; ++k) {
+            const float v = lr[k];
+            bad |= weight_bad(v);
+            mx = v > mx ? v : mx;
+        }
+        for (int off = 1; off < G; off <<= 1) {
+            const float o = __shfl_xor(mx, off);
+            mx = o > mx ? o : mx;
+            bad |= __shfl_xor(bad, off);
+        }
+        if (bad || mx == -INFINITY) {
+            if (sr)
+                for (long long i = lane; i < (long long)M * D; i += G) sr[i] = qnan;
+            if (ir)
+                for (int m = lane; m < M; m += G) ir[m] = -1;
+            for (int d = lane; d < D; d += G) {
+                if (a.mean) a.mean[pt * D + d] = qnan;
+                if (a.var) a.var[pt * D + d] = qnan;
+            }
+            continue;
+        }
+
+        // the lane's segment: its sum and its last draw of positive weight; then the scan of the segment sums
+        const double m = (double)mx;
+        double s = 0.0, w_first = 0.0;
+        int last = -1;
+        for (int k = k0; k < k1; ++k) {
+            const double w = weight(lr[k], m);
+            if (k == k0) w_first = w;
+            s += w;
+            if (w > 0.0) last = k;
+        }
+        double inc = s;
+        for (int off = 1; off < G; off <<= 1) {
+            const double o = __shfl_up(inc, off, G);
+            if (lane >= off) inc += o;
+            const int l = __shfl_xor(last, off);
+            last = l > last ? l : last;
+        }
+        double excl = __shfl_up(inc, 1, G);
+        if (lane == 0) excl = 0.0;
+        const double W = __shfl(excl + s, G - 1, G);          // the running sum as the last lane sees it at its last draw
+        const double rW = 1.0 / W;                            // one division per point: the moments are sums times 1 / W
+
+        if (M > 0 && (sr || ir))
+            for (int m0 = 0; m0 < M; m0 += 4) {
+                double t[4];
+                resample_targets(a.seed, (unsigned long long)(a.sample_offset + pt), (uint32_t)(m0 >> 2), W, t);
+                int c[4] = {K, K, K, K};
+                double run = 0.0;
+                for (int k = k0; k < k1; ++k) {
+                    const double w = k == k0 ? w_first : weight(lr[k], m);
+                    run += w;
+                    const double cum = excl + run;
+                    if (w > 0.0) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (cum > t[j] && k < c[j]) c[j] = k;
+                    }
+                }
+                for (int off = 1; off < G; off <<= 1)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int o = __shfl_xor(c[j], off);
+                        c[j] = o < c[j] ? o : c[j];
+                    }
+                // (a target within rounding of W that no lane's running sum exceeds: the last draw of positive weight)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c[j] >= K) c[j] = last;
+                const int nrow = M - m0 < 4 ? M - m0 : 4;
+                if (ir && lane == 0)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (j < nrow) ir[m0 + j] = c[j];
+                if (sr)
+                    for (int u = lane; u < nrow * nblk; u += G) {
+                        const int j = u / nblk, d0 = 4 * (u - j * nblk);
+                        const int src = j == 0 ? c[0] : j == 1 ? c[1] : j == 2 ? c[2] : c[3];
+                        const float* from = yr + (long long)src * D;
+                        float* to = sr + (long long)(m0 + j) * D;
+                        if (a.vec) {
+                            *(v4f*)(to + d0) = *(const v4f*)(from + d0);
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i)
+                                if (d0 + i < D) to[d0 + i] = from[d0 + i];
+                        }
+                    }
+            }
+
+        if (a.mean || a.var)
+            for (int blk = 0; blk < nblk; ++blk) {
+                const int d0 = 4 * blk;
+                double acc[4] = {0.0, 0.0, 0.0, 0.0}, mu[4];
+                for (int k = k0; k < k1; ++k) {
+                    float v[4];
+                    load_block(yr + (long long)k * D, d0, D, a.vec, v);
+                    moment1_add(acc, k == k0 ? w_first : weight(lr[k], m), v);
+                }
+                group_sum4(acc, G);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mu[j] = acc[j] * rW;
+                if (a.mean && lane == 0)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (d0 + j < D) a.mean[pt * D + d0 + j] = (float)mu[j];
+                if (!a.var) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = 0.0;
+                for (int k = k0; k < k1; ++k) {
+                    float v[4];
+                    load_block(yr + (long long)k * D, d0, D, a.vec, v);
+                    moment2_add(acc, k == k0 ? w_first : weight(lr[k], m), v, mu);
+                }
+                group_sum4(acc, G);
+                if (lane == 0)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (d0 + j < D) a.var[pt * D + d0 + j] = (float)(acc[j] * rW);
+            }
+    }
+}
+
 static unsigned stream_grid(long long threads)
 {
     // a few workgroups per CU (256 CUs) saturate HBM with 16-byte accesses; never more than needed (ff_aux.hip)
@@ -147,6 +335,13 @@ static bool expand_args_ok(const float* x, const float* noise_std, int32_t std_r
 static bool reduce_args_ok(const float* lp, int64_t B, int32_t K, const float* out)
 {
     return lp && out && B >= 0 && K >= 1 && K <= kMaxDraws;
+}
+
+static bool resample_args_ok(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M,
+                             const float* samples, const int32_t* index, const float* mean, const float* var)
+{
+    if (!y || !lp || B < 0 || D < 1 || K < 1 || K > kMaxDraws || M < 0 || M > kMaxSamples) return false;
+    return samples || index || mean || var;
 }
 
 } // namespace observe
@@ -191,7 +386,103 @@ extern "C" int ff_logmeanexp(const float* lp, int64_t B, int32_t K, float* out, 
     return hipGetLastError() == hipSuccess ? FF_OK : FF_ERR_HIP;
 }
 
+extern "C" int ff_weighted_resample(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M,
+                                    uint64_t seed, int64_t sample_offset, float* samples, int32_t* index, float* mean,
+                                    float* var, void* hip_stream)
+{
+    if (!resample_args_ok(y, lp, B, D, K, M, samples, index, mean, var)) return FF_ERR_BADARG;
+    if (M == 0) { samples = nullptr; index = nullptr; }
+    if (B == 0 || !(samples || index || mean || var)) return FF_OK;
+    ResampleArgs a;
+    a.y = y; a.lp = lp; a.samples = samples; a.index = index; a.mean = mean; a.var = var;
+    a.B = B; a.D = D; a.K = K; a.M = M;
+    a.seed = seed; a.sample_offset = sample_offset;
+    const int G = lanes_per_point(K);
+    a.log_g = log2_of(G);
+    a.seg = (K + G - 1) / G;
+    a.vec = (D & 3) == 0 && (((uintptr_t)y | (uintptr_t)samples) & 15) == 0;
+    hipLaunchKernelGGL(weighted_resample_kernel, dim3(stream_grid((long long)B * G)), dim3(256), 0, (hipStream_t)hip_stream, a);
+    return hipGetLastError() == hipSuccess ? FF_OK : FF_ERR_HIP;
+}
+
 // ---- the host twins (CPU tests): the same header, rows and draws in index order ---------------------------------------
+extern "C" int ff_weighted_resample_host(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M,
+                                         uint64_t seed, int64_t sample_offset, float* samples, int32_t* index, float* mean,
+                                         float* var)
+{
+    if (!resample_args_ok(y, lp, B, D, K, M, samples, index, mean, var)) return FF_ERR_BADARG;
+    if (M == 0) { samples = nullptr; index = nullptr; }
+    const float qnan = nanf("");
+    const int nblk = (D + 3) / 4;
+    for (int64_t r = 0; r < B; ++r) {
+        const float* lr = lp + r * K;
+        const float* yr = y + r * K * D;
+        float* sr = samples ? samples + r * M * D : nullptr;
+        int32_t* ir = index ? index + r * M : nullptr;
+        float mx = -INFINITY;
+        bool bad = false;
+        for (int k = 0; k < K; ++k) {
+            bad = bad || weight_bad(lr[k]);
+            mx = lr[k] > mx ? lr[k] : mx;
+        }
+        if (bad || mx == -INFINITY) {
+            for (int64_t i = 0; sr && i < (int64_t)M * D; ++i) sr[i] = qnan;
+            for (int m = 0; ir && m < M; ++m) ir[m] = -1;
+            for (int d = 0; d < D; ++d) {
+                if (mean) mean[r * D + d] = qnan;
+                if (var) var[r * D + d] = qnan;
+            }
+            continue;
+        }
+        const double m = (double)mx;
+        double W = 0.0;
+        int last = -1;
+        for (int k = 0; k < K; ++k) {
+            const double w = weight(lr[k], m);
+            W += w;
+            if (w > 0.0) last = k;
+        }
+        const double rW = 1.0 / W;
+        for (int m0 = 0; (sr || ir) && m0 < M; m0 += 4) {
+            double t[4];
+            resample_targets(seed, (uint64_t)(sample_offset + r), (uint32_t)(m0 >> 2), W, t);
+            int c[4] = {K, K, K, K};
+            double cum = 0.0;
+            for (int k = 0; k < K; ++k) {
+                const double w = weight(lr[k], m);
+                cum += w;
+                if (w > 0.0)
+                    for (int j = 0; j < 4; ++j)
+                        if (cum > t[j] && k < c[j]) c[j] = k;
+            }
+            for (int j = 0; j < 4 && m0 + j < M; ++j) {
+                const int src = c[j] >= K ? last : c[j];
+                if (ir) ir[m0 + j] = src;
+                for (int d = 0; sr && d < D; ++d) sr[(int64_t)(m0 + j) * D + d] = yr[(int64_t)src * D + d];
+            }
+        }
+        for (int blk = 0; (mean || var) && blk < nblk; ++blk) {
+            const int d0 = 4 * blk;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0}, mu[4];
+            float v[4];
+            for (int k = 0; k < K; ++k) {
+                for (int j = 0; j < 4; ++j) v[j] = d0 + j < D ? yr[(int64_t)k * D + d0 + j] : 0.f;
+                moment1_add(acc, weight(lr[k], m), v);
+            }
+            for (int j = 0; j < 4; ++j) mu[j] = acc[j] * rW;
+            for (int j = 0; mean && j < 4 && d0 + j < D; ++j) mean[r * D + d0 + j] = (float)mu[j];
+            if (!var) continue;
+            for (int j = 0; j < 4; ++j) acc[j] = 0.0;
+            for (int k = 0; k < K; ++k) {
+                for (int j = 0; j < 4; ++j) v[j] = d0 + j < D ? yr[(int64_t)k * D + d0 + j] : 0.f;
+                moment2_add(acc, weight(lr[k], m), v, mu);
+            }
+            for (int j = 0; j < 4 && d0 + j < D; ++j) var[r * D + d0 + j] = (float)(acc[j] * rW);
+        }
+    }
+    return FF_OK;
+}
+
 extern "C" int ff_observe_expand_host(const float* x, const float* noise_std, int32_t std_row_stride, const float* cond,
                                       int64_t B, int32_t D, int32_t C, int32_t K, uint64_t seed, int64_t sample_offset,
                                       float* y, float* cond_out)

@@ -31,6 +31,7 @@ from torch.distributions import Normal
 from . import _native, device_adaptive, generic, odeint, solvers, trace_estimators
 from .fused import FusedNet, MODE_EXACT, MODE_HUTCH, MODE_STATE, activation_spec, require_fp32, within_envelope
 from .generic import _need_gpu
+from .odeint import NoisyPosterior  # noqa: F401  (what ``posterior_noisy`` returns)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -705,6 +706,30 @@ class ScoreModel(nn.Module):
                                     sample_offset, chunk_points, return_ess)
         return (out[0].view(-1, 1), out[1]) if return_ess else out.view(-1, 1)
 
+    @torch.no_grad()
+    def posterior_noisy(self, x, noise_std, conditional=None, num_draws=16, num_samples=1, atol=1e-4, rtol=1e-4,
+                        method="dopri5", options={"min_step": 1e-6}, *, seed=None, sample_offset=0, chunk_points=None,
+                        num_probes=1):
+        """Extension: the per-object posterior ``p(x_true | x, noise_std) ~ p(x_true) N(x; x_true, diag noise_std^2)``
+        of observations ``x`` [B, D] under the learned population, from the same ``num_draws`` = K draws that
+        ``log_prob_noisy`` makes (arguments, seed and chunking rules as there).  The K candidates ``x - noise_std z_k``
+        with weights ``w_k ~ p(candidate k)`` are a self-normalised importance sample of it.  Returns a
+        ``NoisyPosterior``: ``samples`` [B, M, D] (M = ``num_samples`` multinomial draws of the K candidates by their
+        weights, in the units of ``x``), ``log_prob`` [B, 1] and ``ess`` [B] (bit for bit
+        ``log_prob_noisy(..., return_ess=True)`` under the same seed), ``mean`` and ``var`` [B, D] (the weighted mean --
+        the denoised, "shrunk" estimate -- and variance of the candidates) and ``index`` [B, M] (int32: which candidate
+        each sample is).
+
+        The samples are a RESAMPLE of K particles: only as many distinct points as the effective sample size allows.
+        Read ``ess`` before trusting ``samples`` (an ess near 1: every draw is the same candidate, ``var`` near 0), and
+        raise ``num_draws``, not ``num_samples``, to get more of them.  With a ``hutchinson=True`` model the weights carry
+        the noise of the divergence estimate (see ``log_prob_noisy``); exact-trace models are the clean case."""
+        rows = lambda y, c, extra: self.log_prob(y, conditional=c, atol=atol, rtol=rtol, method=method, options=options,
+                                                 num_probes=num_probes, **extra)
+        post = odeint.posterior_noisy(rows, bool(self.hutch), x, noise_std, conditional, num_draws, num_samples, method, seed,
+                                      sample_offset, chunk_points)
+        return post._replace(log_prob=post.log_prob.view(-1, 1))
+
 
 # ------------------------------------------------------------------------------------------------
 # population-model wrappers (affine pre/post-processing; reference: diffusion.py:1466-1848)
@@ -758,6 +783,19 @@ class _PopulationModel(nn.Module):
                                     seed, sample_offset, chunk_points, return_ess)
         return (out[0].view(-1, 1), out[1]) if return_ess else out.view(-1, 1)
 
+    @torch.no_grad()
+    def _posterior_noisy(self, x, noise_std, conditional, num_draws, num_samples, atol, rtol, seed, sample_offset,
+                         chunk_points, num_probes):
+        """``posterior_noisy`` of the two wrappers, around this wrapper's own ``log_prob`` like ``_log_prob_noisy``: the
+        candidates, and so ``samples``, ``mean`` and ``var``, are in the data space of ``x`` (before ``(x - shift) /
+        scale``)."""
+        def rows(y, c, extra):
+            rng = (extra["seed"], extra["sample_offset"]) if extra else None
+            return self._log_prob(y, c, atol, rtol, num_probes, probe_rng=rng)
+        post = odeint.posterior_noisy(rows, bool(self.score_model.hutch), x, noise_std, conditional, num_draws, num_samples,
+                                      "dopri5", seed, sample_offset, chunk_points)
+        return post._replace(log_prob=post.log_prob.view(-1, 1))
+
 
 class PopulationModelDiffusion(_PopulationModel):
     def __init__(self, model=None, sde=None, shift=None, scale=None, method="dopri5", no_sigma=False,
@@ -788,6 +826,15 @@ class PopulationModelDiffusion(_PopulationModel):
         and ``_log_prob_noisy``."""
         return self._log_prob_noisy(x, noise_std, None, num_draws, atol, rtol, seed, sample_offset, chunk_points,
                                     return_ess, num_probes)
+
+    def posterior_noisy(self, x, noise_std, num_draws=16, num_samples=1, atol=1e-5, rtol=1e-5, *, seed=None,
+                        sample_offset=0, chunk_points=None, num_probes=1):
+        """Extension: the per-object posterior of observations ``x`` measured with Gaussian errors ``noise_std`` under this
+        population model, from the ``num_draws`` candidates of ``log_prob_noisy``: a ``NoisyPosterior`` whose ``samples``
+        [B, ``num_samples``, D], ``mean`` and ``var`` are in the units of ``x``.  Read ``ess`` before trusting ``samples``
+        and raise ``num_draws``, not ``num_samples``: see ``ScoreModel.posterior_noisy`` and ``_posterior_noisy``."""
+        return self._posterior_noisy(x, noise_std, None, num_draws, num_samples, atol, rtol, seed, sample_offset,
+                                     chunk_points, num_probes)
 
 
 class PopulationModelDiffusionConditional(_PopulationModel):
@@ -822,3 +869,11 @@ class PopulationModelDiffusionConditional(_PopulationModel):
         ``PopulationModelDiffusion.log_prob_noisy``."""
         return self._log_prob_noisy(x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
                                     return_ess, num_probes)
+
+    def posterior_noisy(self, x, noise_std, conditional=None, num_draws=16, num_samples=1, atol=1e-5, rtol=1e-5, *,
+                        seed=None, sample_offset=0, chunk_points=None, num_probes=1):
+        """Extension: the per-object posterior of observations ``x`` measured with Gaussian errors ``noise_std`` given the
+        raw ``conditional`` [B, C] (repeated for the draws): a ``NoisyPosterior`` in the units of ``x``.  Read ``ess`` before
+        trusting ``samples`` and raise ``num_draws``, not ``num_samples``: see ``PopulationModelDiffusion.posterior_noisy``."""
+        return self._posterior_noisy(x, noise_std, conditional, num_draws, num_samples, atol, rtol, seed, sample_offset,
+                                     chunk_points, num_probes)

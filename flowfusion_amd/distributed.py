@@ -333,17 +333,7 @@ def log_prob_noisy_sharded(model, x: Optional[torch.Tensor] = None, noise_std=No
         raise ValueError("pass noise_std (or local_noise_std with local_x)")
 
     def run(rows, cond, probe, seed, sample_offset, **kw):
-        lo, hi = sample_offset, sample_offset + rows.shape[0]
-        if local_noise_std is not None:
-            if local_noise_std.shape[0] != hi - lo:
-                raise ValueError(f"local_noise_std must hold exactly this rank's rows [{lo}, {hi})")
-            std = local_noise_std
-        elif torch.is_tensor(noise_std) and noise_std.dim() == 2:
-            if local_x is not None:
-                raise ValueError("a per-object noise_std beside local_x is local_noise_std (this rank's rows)")
-            std = noise_std[lo:hi]
-        else:
-            std = noise_std
+        std = _local_noise_std(noise_std, local_noise_std, local_x, sample_offset, sample_offset + rows.shape[0])
         out = model.log_prob_noisy(rows, std, *(() if cond is None else (cond,)), num_draws=num_draws, seed=seed,
                                    sample_offset=sample_offset, return_ess=return_ess, **kw)
         return (out[0], out[1].view_as(out[0])) if return_ess else out
@@ -357,6 +347,62 @@ def log_prob_noisy_sharded(model, x: Optional[torch.Tensor] = None, noise_std=No
         (lp, ess), span = res
         return (lp, ess.reshape(-1)), span
     return res[0], res[1].reshape(-1)
+
+
+def _local_noise_std(noise_std, local_noise_std, local_x, lo, hi):
+    """This rank's ``noise_std`` for the rows [lo, hi): ``local_noise_std``, its rows of a [B, D] one, or the replicated
+    vector / scalar (the rules of ``log_prob_noisy_sharded``)."""
+    if local_noise_std is not None:
+        if local_noise_std.shape[0] != hi - lo:
+            raise ValueError(f"local_noise_std must hold exactly this rank's rows [{lo}, {hi})")
+        return local_noise_std
+    if torch.is_tensor(noise_std) and noise_std.dim() == 2:
+        if local_x is not None:
+            raise ValueError("a per-object noise_std beside local_x is local_noise_std (this rank's rows)")
+        return noise_std[lo:hi]
+    return noise_std
+
+
+def posterior_noisy_sharded(model, x: Optional[torch.Tensor] = None, noise_std=None, conditional: Optional[torch.Tensor] = None,
+                            *, local_x: Optional[torch.Tensor] = None, local_noise_std: Optional[torch.Tensor] = None,
+                            n_total: Optional[int] = None, local_conditional: Optional[torch.Tensor] = None, seed: int = 0,
+                            num_draws: int = 16, num_samples: int = 1, group=None, gather: bool = True,
+                            global_control: bool = True, **solver):
+    """``posterior_noisy`` (``ScoreModel``, ``ODEFlow``, ``ConditionalODEFlow``) of a [B, dim] batch of observations over all
+    ranks: a ``NoisyPosterior`` of the whole batch on every rank -- with ``gather=False`` ``(NoisyPosterior of this rank's
+    rows, (lo, hi))``.  ``x`` / ``local_x`` / ``noise_std`` / ``local_noise_std`` / ``n_total`` / ``conditional`` /
+    ``local_conditional``, the keying of the noise draws, the resampling uniforms and a Hutchinson model's probes by
+    ``seed`` and the GLOBAL row, and the step control of an adaptive ``method``: exactly ``log_prob_noisy_sharded``; on a
+    fixed grid every row of every field is bitwise independent of the number of ranks.  ONE all-gather: the fields travel
+    as the columns of one [rows, M D + 2 D + 2 + M] fp32 tensor (samples, mean, var, log_prob, ess, index -- indices up to
+    4095 are exact in fp32) and come back in their own shapes and dtypes.  ``**solver`` (atol, rtol, method, options,
+    hutchinson, num_probes, chunk_points) goes to ``posterior_noisy`` unchanged."""
+    if local_noise_std is not None and (noise_std is not None or local_x is None):
+        raise ValueError("local_noise_std holds this rank's [rows, dim] of a per-object noise_std: it goes with local_x and "
+                         "excludes `noise_std` (which then is a [dim] vector or a scalar, the same on every rank)")
+    if local_noise_std is None and noise_std is None:
+        raise ValueError("pass noise_std (or local_noise_std with local_x)")
+    from .odeint import NoisyPosterior
+    M = int(num_samples)
+    lp_shape = []
+
+    def run(rows, cond, probe, seed, sample_offset, **kw):
+        std = _local_noise_std(noise_std, local_noise_std, local_x, sample_offset, sample_offset + rows.shape[0])
+        post = model.posterior_noisy(rows, std, *(() if cond is None else (cond,)), num_draws=num_draws, num_samples=M,
+                                     seed=seed, sample_offset=sample_offset, **kw)
+        n = rows.shape[0]
+        lp_shape.append(tuple(post.log_prob.shape[1:]))
+        return torch.cat([post.samples.reshape(n, -1), post.mean, post.var, post.log_prob.reshape(n, 1),
+                          post.ess.reshape(n, 1), post.index.to(torch.float32)], dim=1)
+
+    res = _log_prob_sharded(run, True, x, conditional, seed, group, gather, local_x, n_total, local_conditional, global_control,
+                            False, solver)
+    packed, span = res if not gather else (res, None)
+    n, D = packed.shape[0], (packed.shape[1] - 2 - M) // (M + 2)
+    samples, mean, var, lp, ess, index = torch.split(packed, [M * D, D, D, 1, 1, M], dim=1)
+    post = NoisyPosterior(samples.reshape(n, M, D), lp.reshape((n,) + lp_shape[0]), ess.reshape(n), mean.contiguous(),
+                          var.contiguous(), index.to(torch.int32))
+    return post if gather else (post, span)
 
 
 # ---- the symplectic flows (flowfusion/symplectic.py:166-253) ------------------------------------------------------------------

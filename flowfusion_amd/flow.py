@@ -23,6 +23,7 @@ from torch import nn
 
 from . import _native, device_adaptive, odeint, solvers, trace_estimators
 from .fused import FusedNet, MODE_EXACT, MODE_HUTCH, MODE_STATE, activation_spec, within_envelope
+from .odeint import NoisyPosterior  # noqa: F401  (what ``posterior_noisy`` returns)
 
 _DEFAULT_SAMPLE_METHOD = "dopri5"     # what odeint() picks when the reference passes no method
 
@@ -238,6 +239,27 @@ class _FlowBase(nn.Module):
         return odeint.log_prob_noisy(rows, bool(hutchinson), x, noise_std, conditional, num_draws, method, seed,
                                      sample_offset, chunk_points, return_ess)
 
+    @torch.no_grad()
+    def _posterior_noisy(self, x, noise_std, conditional, num_draws, num_samples, atol, rtol, method, options, hutchinson,
+                         seed, sample_offset, chunk_points, num_probes):
+        """``posterior_noisy`` of both flows (extension): the per-object posterior ``p(x_true | x, noise_std) ~ p(x_true)
+        N(x; x_true, diag noise_std^2)`` of target-space observations ``x`` [B, D], from the same ``num_draws`` = K draws
+        that ``_log_prob_noisy`` makes (arguments, seed and chunking rules as there).  The K candidates ``x - noise_std z_k``
+        with weights ``w_k ~ p(candidate k)`` are a self-normalised importance sample of it.  Returns a ``NoisyPosterior``:
+        ``samples`` [B, M, D] (M = ``num_samples`` multinomial draws of the candidates by their weights, in the units of
+        ``x``), ``log_prob`` [B] and ``ess`` [B] (bit for bit ``log_prob_noisy(..., return_ess=True)`` under the same
+        seed), ``mean`` and ``var`` [B, D] (the weighted mean -- the denoised estimate -- and variance of the candidates)
+        and ``index`` [B, M] (int32: which candidate each sample is).
+
+        The samples are a RESAMPLE of K particles: only as many distinct points as the effective sample size allows.  Read
+        ``ess`` before trusting ``samples``, and raise ``num_draws``, not ``num_samples``, to get more of them.  With
+        ``hutchinson=True`` the weights carry the noise of the divergence estimate (see ``_log_prob_noisy``); the exact
+        trace is the clean case."""
+        rows = lambda y, c, extra: self.log_prob(y, *(() if c is None else (c,)), atol=atol, rtol=rtol, method=method,
+                                                 options=options, hutchinson=hutchinson, num_probes=num_probes, **extra)
+        return odeint.posterior_noisy(rows, bool(hutchinson), x, noise_std, conditional, num_draws, num_samples, method, seed,
+                                      sample_offset, chunk_points)
+
 
 class ODEFlow(_FlowBase):
     """Unconditional flow-matching CNF (reference: flow.py:9-438)."""
@@ -306,6 +328,16 @@ class ODEFlow(_FlowBase):
         per point (extension; see ``_log_prob_noisy``)."""
         return self._log_prob_noisy(x, noise_std, None, num_draws, atol, rtol, method, options, hutchinson, seed,
                                     sample_offset, chunk_points, return_ess, num_probes)
+
+    def posterior_noisy(self, x, noise_std, num_draws: int = 16, num_samples: int = 1, atol: float = 1e-5,
+                        rtol: float = 1e-5, method: str = "dopri5", options: Optional[dict] = None, *,
+                        hutchinson: bool = False, seed: Optional[int] = None, sample_offset: int = 0,
+                        chunk_points: Optional[int] = None, num_probes: int = 1):
+        """Posterior draws, mean and variance of target-space observations with Gaussian errors ``noise_std``, from the
+        ``num_draws`` candidates of ``log_prob_noisy``: a ``NoisyPosterior`` (extension; see ``_posterior_noisy`` -- read
+        ``ess`` before trusting ``samples``)."""
+        return self._posterior_noisy(x, noise_std, None, num_draws, num_samples, atol, rtol, method, options, hutchinson,
+                                     seed, sample_offset, chunk_points, num_probes)
 
 
 class ConditionalODEFlow(_FlowBase):
@@ -380,3 +412,13 @@ class ConditionalODEFlow(_FlowBase):
         per point (extension; see ``_log_prob_noisy``)."""
         return self._log_prob_noisy(x, noise_std, conditional, num_draws, atol, rtol, method, options, hutchinson, seed,
                                     sample_offset, chunk_points, return_ess, num_probes)
+
+    def posterior_noisy(self, x, noise_std, conditional, num_draws: int = 16, num_samples: int = 1, atol: float = 1e-5,
+                        rtol: float = 1e-5, method: str = "dopri5", options: Optional[dict] = None, *,
+                        hutchinson: bool = False, seed: Optional[int] = None, sample_offset: int = 0,
+                        chunk_points: Optional[int] = None, num_probes: int = 1):
+        """Posterior draws, mean and variance of target-space observations with Gaussian errors ``noise_std`` given the raw
+        ``conditional``, from the ``num_draws`` candidates of ``log_prob_noisy``: a ``NoisyPosterior`` (extension; see
+        ``_posterior_noisy`` -- read ``ess`` before trusting ``samples``)."""
+        return self._posterior_noisy(x, noise_std, conditional, num_draws, num_samples, atol, rtol, method, options,
+                                     hutchinson, seed, sample_offset, chunk_points, num_probes)

@@ -12,6 +12,8 @@ route.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import _native, adaptive, device_adaptive, solvers, trace_estimators
@@ -261,11 +263,27 @@ def log_prob_noisy(log_prob_rows, randomised, x, noise_std, cond, num_draws, met
     default generator.  On a fixed-grid ``method`` the points go through in chunks of ``chunk_points`` (default:
     ``chunk_points * K <= OBSERVE_CHUNK_ROWS``) with bitwise the same result whatever the chunking; an adaptive method
     takes its step from the whole batch, so all B K rows are one solve and ``chunk_points`` raises."""
+    out, ess, _ = _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, method, seed, sample_offset,
+                                  chunk_points, return_ess, None)
+    return (out, ess) if return_ess else out
+
+
+def _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, method, seed, sample_offset, chunk_points,
+                    want_ess, num_samples):
+    """The loop over chunks of ``log_prob_noisy`` and ``posterior_noisy``: its checks, the chunk rule and the seed draw,
+    then per chunk expand -> the model's ``log_prob`` -> the reductions.  Returns ``(log_p [B], ess [B] or None,
+    posterior)``; with ``num_samples`` = M not None the chunk's particles and log-densities also go through
+    ff_weighted_resample before they are dropped, ``posterior`` = (samples [B, M, D], index [B, M], mean, var [B, D]) --
+    else None."""
     K = int(num_draws)
     if not 1 <= K <= _native.MAX_OBS_DRAWS:
         raise ValueError(f"num_draws={num_draws}: 1 .. {_native.MAX_OBS_DRAWS} noise draws per data point")
+    M = None if num_samples is None else int(num_samples)
+    if M is not None and not 0 <= M <= _native.MAX_OBS_SAMPLES:
+        raise ValueError(f"num_samples={num_samples}: 0 .. {_native.MAX_OBS_SAMPLES} posterior draws per data point")
+    what = "log_prob_noisy" if M is None else "posterior_noisy"
     if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError("log_prob_noisy: x must be a [batch, dim] float32 tensor")
+        raise ValueError(f"{what}: x must be a [batch, dim] float32 tensor")
     B = int(x.shape[0])
     std = noise_std_tensor(noise_std, x)
     if method not in solvers.FIXED_METHODS:
@@ -287,17 +305,52 @@ def log_prob_noisy(log_prob_rows, randomised, x, noise_std, cond, num_draws, met
     x = x.detach().contiguous()
     cond = _native.f32_on(cond, x.device)
     out = torch.empty(B, dtype=torch.float32, device=x.device)
-    ess = torch.empty(B, dtype=torch.float32, device=x.device) if return_ess else None
+    ess = torch.empty(B, dtype=torch.float32, device=x.device) if want_ess else None
+    parts = []
     for lo in range(0, B, chunk):
         hi = min(B, lo + chunk)
         y, ck = _native.observe_expand(x[lo:hi], std if std.dim() == 1 else std[lo:hi], K, seed, first + lo,
                                        None if cond is None else cond[lo:hi])
         extra = {"probe": "philox", "seed": seed, "sample_offset": (first + lo) * K} if randomised else {}
         lp = log_prob_rows(y, ck, extra)
-        del y, ck
-        _native.logmeanexp(lp.detach().to(torch.float32).contiguous(), K, out[lo:hi], None if ess is None else ess[lo:hi])
-        del lp
-    return (out, ess) if return_ess else out
+        del ck
+        lp = lp.detach().to(torch.float32).contiguous()
+        _native.logmeanexp(lp, K, out[lo:hi], None if ess is None else ess[lo:hi])
+        if M is not None:
+            parts.append(_native.weighted_resample(y, lp, K, M, seed, first + lo))
+        del y, lp
+    if M is None:
+        return out, ess, None
+    if len(parts) == 1:
+        return out, ess, parts[0]
+    if not parts:
+        parts = [_native.weighted_resample(x.new_empty(0, x.shape[1]), x.new_empty(0), K, M, seed, first)]
+    return out, ess, tuple(torch.cat(cols) for cols in zip(*parts))
+
+
+class NoisyPosterior(NamedTuple):
+    """What ``posterior_noisy`` returns about the per-object posterior ``p(x | x_obs, noise_std)``."""
+    samples: torch.Tensor       # [B, M, D]: M draws per object, in the units of x
+    log_prob: torch.Tensor      # what log_prob_noisy returns for the same arguments and seed
+    ess: torch.Tensor           # [B]: the effective sample size of the K weights
+    mean: torch.Tensor          # [B, D]: the weighted mean of the K particles
+    var: torch.Tensor           # [B, D]: their weighted variance about it
+    index: torch.Tensor         # [B, M] int32: samples[r, m] is particle index[r, m] of object r
+
+
+def posterior_noisy(log_prob_rows, randomised, x, noise_std, cond, num_draws, num_samples, method, seed, sample_offset,
+                    chunk_points):
+    """What every front end's ``posterior_noisy`` does: the loop of ``log_prob_noisy`` (same arguments, checks, chunk rule
+    and seed), keeping what that one throws away.  The K rows ``y_k = x - noise_std z_k`` of a point with weights
+    ``w_k ~ p(y_k)`` are a self-normalised importance sample of its posterior ``p(x | x_obs, noise_std) ~ p(x)
+    N(x_obs; x, diag noise_std^2)``: ff_weighted_resample draws ``num_samples`` = M of them per point by their weights
+    (uniforms of the counter-based stream under the same ``seed`` and global row, FF_OBS_RESAMPLE_NOISE_INDEX) and forms
+    the weighted mean and variance, in double.  Returns a ``NoisyPosterior`` whose ``log_prob`` [B] and ``ess`` are the
+    ff_logmeanexp results of ``log_prob_noisy(..., return_ess=True)``, bit for bit; every field is bitwise independent of
+    the chunking on a fixed grid."""
+    out, ess, (samples, index, mean, var) = _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, method,
+                                                            seed, sample_offset, chunk_points, True, num_samples)
+    return NoisyPosterior(samples, out, ess, mean, var, index)
 
 
 def _host_adaptive(front, step, x, t, sign, method, options, mode, atol, rtol, norm_only):

@@ -531,6 +531,40 @@ int ff_observe_expand_host(const float* x, const float* noise_std, int32_t std_r
                            float* cond_out);
 int ff_logmeanexp_host(const float* lp, int64_t B, int32_t K, float* out, float* out_ess);
 
+/* ---- posterior draws and moments from the K weighted particles of an observation (csrc/ff_observe.hip) -------------
+ *
+ * The K rows of a data point with weights w_k proportional to p(y_k) are a self-normalised importance sample of its
+ * posterior p(x | xhat, sigma) ~ p(x) N(xhat; x, diag sigma^2).  ff_weighted_resample turns them into M multinomial
+ * draws and the weighted mean and variance, per data point r, in double:
+ *     w_k = exp((double)lp[r K + k] - max_k lp),   W = sum_k w_k
+ *     index[r][m]     = the smallest k with sum_{j <= k} w_j > u_m W  (strict, u_m < 1: a row of weight 0 is never chosen)
+ *     samples[r][m][] = y[r K + index[r][m]][], copied bit for bit
+ *     mean[r][d]      = sum_k w_k y_kd / W
+ *     var[r][d]       = sum_k w_k (y_kd - mean_d)^2 / W   (about the double mean, a second pass: never negative; the
+ *                       weight-normalised form, no Bessel correction)
+ *   y [B K][D] (the rows of ff_observe_expand, or any particles); lp [B K]; samples [B][M][D]; index [B][M]; mean, var
+ *   [B][D].  Each of the four outputs may be NULL (samples and index are ignored when M == 0); mean and var are rounded to
+ *   fp32 once (the double sums times the double 1 / W: one division per point).  A point is degenerate if any of its lp is NaN or +inf, or if W is 0 (all -inf): index = -1, NaN in
+ *   samples, mean and var.  K = 1 with a finite lp: index 0, every sample and the mean are the row, var = 0.
+ *   The uniforms of the resampling step: u_m of global row g is (word[m & 3] >> 8) * 2^-24 in [0, 1), word = the Philox4x32-10
+ *   block of counter (g lo, g hi, FF_OBS_RESAMPLE_NOISE_INDEX, m >> 2) under the seed -- an index of its own below
+ *   FF_OBS_NOISE_BASE, so a seed shared with the noise draws, probes, momenta or a prior gives unrelated uniforms.
+ *   A data point's results are fixed by K and its own data (a group of lanes_per_point(K) lanes: contiguous segments of
+ *   draws, a scan of the segment sums, the moments one block of four dimensions at a time), not by B, its position or
+ *   the launch: chunks (sample_offset + first point of the chunk) and shards give bitwise the same.  16-byte accesses on
+ *   y and samples where they are 16-byte aligned and D % 4 == 0, a scalar body otherwise.
+ *   FF_ERR_BADARG, before anything is enqueued: y or lp NULL; B < 0; D < 1; K outside 1 .. FF_MAX_OBS_DRAWS; M outside
+ *   0 .. FF_MAX_OBS_SAMPLES; all four outputs NULL.  B == 0 is FF_OK without a launch.  DEVICE pointers, enqueued on
+ *   hip_stream; the _host twin runs the same header arithmetic on HOST pointers with the draws in index order (the same
+ *   uniforms bit for bit; sums agree to double rounding).
+ */
+#define FF_OBS_RESAMPLE_NOISE_INDEX 0xFFFA0000u
+#define FF_MAX_OBS_SAMPLES 4096
+int ff_weighted_resample(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M, uint64_t seed,
+                         int64_t sample_offset, float* samples, int32_t* index, float* mean, float* var, void* hip_stream);
+int ff_weighted_resample_host(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M, uint64_t seed,
+                              int64_t sample_offset, float* samples, int32_t* index, float* mean, float* var);
+
 /* ---- Hutch++ / XTrace divergence estimates from recorded Jacobians (csrc/ff_trace.hip, csrc/ff_trace_est.h) ----
  *
  * Replaces the two estimator branches of ScoreModel.forward, diffusion.py:336-400 (Hutch++) and :402-481 (XTrace), for
