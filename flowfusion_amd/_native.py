@@ -91,6 +91,9 @@ STATUS_NAN, STATUS_BAD_SLOT = 1, 2          # FF_STATUS_*
 SCHED_FLOW, SCHED_VE, SCHED_VP, SCHED_SUBVP, SCHED_FOURIER = 0, 1, 2, 3, 4     # FF_SCHED_*
 PAIR_KERNEL_BASE = 0x10000                                  # FF_PAIR_KERNEL_BASE
 PAIR_SELECT_KERNEL_BASE = 0x20000                           # FF_PAIR_SELECT_KERNEL_BASE
+PUSH_KERNEL_BASE = 0x40000                                  # FF_PUSH_KERNEL_BASE
+STATUS_NOISE_ROW = 4                                        # FF_STATUS_NOISE_ROW
+MAX_PUSH_TANGENTS = 15                                      # tangent columns beside the value column of a 16-column tile
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -245,6 +248,15 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_ode_launch.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p]
     L.ff_mlp_ode_launch_probes.restype = ctypes.c_int
     L.ff_mlp_ode_launch_probes.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_push_kernel_count.restype = ctypes.c_int
+    L.ff_push_kernel_name.restype = ctypes.c_char_p
+    L.ff_push_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_push_plan.restype = ctypes.c_int
+    L.ff_mlp_push_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                   ctypes.c_int, ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_ode_launch_push.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_push.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]
     L.ff_mlp_samples_per_workgroup.restype = ctypes.c_int
     L.ff_mlp_samples_per_workgroup.argtypes = [ctypes.POINTER(PlanStruct), ctypes.c_int]
     L.ff_last_hip_error.restype = ctypes.c_int
@@ -388,11 +400,34 @@ def make_pair_plan(dim: int, cond_dim: int, hidden: List[int], select: bool = Fa
 
 
 def is_pair_plan(plan: PlanStruct) -> bool:
-    return int(plan.kernel_id) >= PAIR_KERNEL_BASE
+    return PAIR_KERNEL_BASE <= int(plan.kernel_id) < PUSH_KERNEL_BASE
 
 
 def is_select_plan(plan: PlanStruct) -> bool:
-    return int(plan.kernel_id) >= PAIR_SELECT_KERNEL_BASE
+    return PAIR_SELECT_KERNEL_BASE <= int(plan.kernel_id) < PUSH_KERNEL_BASE
+
+
+PUSH_ENVELOPE = ("the push-forward kernels (flow_jvp / flow_jacobian) hold SiLU networks in f32 with hidden widths up to 256, "
+                 "up to 32 state dimensions and up to 16 conditional inputs, and up to 15 tangents per sample")
+
+
+def make_push_plan(dim: int, cond_dim: int, hidden: List[int], act: Tuple[int, float, float] = (ACT_SILU, 0.0, 0.0),
+                   precision: int = PREC_F32) -> PlanStruct:
+    """ff_mlp_push_plan: the smallest push-forward unit that holds the network (NotImplementedError with the envelope if
+    none does)."""
+    p = PlanStruct()
+    arr = (ctypes.c_int * len(hidden))(*hidden)
+    rc = lib().ff_mlp_push_plan(dim, cond_dim, len(hidden), arr, int(act[0]), int(precision), ctypes.byref(p))
+    if rc == FF_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"no gfx950 push-forward kernel for dim={dim}, cond_dim={cond_dim}, hidden={hidden}, "
+                                  f"activation={act[0]}: {PUSH_ENVELOPE}")
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_push_plan")
+    return p
+
+
+def is_push_plan(plan: PlanStruct) -> bool:
+    return int(plan.kernel_id) >= PUSH_KERNEL_BASE
 
 
 def row_width(plan: PlanStruct) -> int:
@@ -816,7 +851,7 @@ def f32_on(t: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
 # the caller's tensors among the ff_ode_args fields -> the name the ops' signatures (and so _chk's messages) give each
 _ARG_NAMES = {"x_in": "x", "cond": "cond", "probe": "probe", "noise": "noise", "wpack": "wpack", "etab": "etab",
               "in_shift": "in_shift", "in_scale": "in_scale", "out_scale": "out_scale", "out_shift": "out_shift",
-              "k1_in": "k1", "kl1_in": "kl1", "dlogp_in": "dlogp0", "jac_out": "jac"}
+              "k1_in": "k1", "kl1_in": "kl1", "dlogp_in": "dlogp0", "jac_out": "jac"}      # (mlp_ode_push: probe = its `tangents`)
 _AuxPtrs = ctypes.c_void_p * MAX_AUX
 
 
@@ -829,9 +864,10 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
     return _AuxPtrs(*range(t.data_ptr(), t.data_ptr() + t.shape[0] * step, step))
 
 
-def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, **fields) -> None:
-    """The one launch of the five ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch, or
-    ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer.  ``tensors``: the caller's
+def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, **fields) -> None:
+    """The one launch of the six ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
+    ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, or ff_mlp_ode_launch_push with
+    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``.  ``tensors``: the caller's
     tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
     of what the op allocated itself.  A field named in neither stays zero."""
     a = OdeArgs(**fields)
@@ -840,7 +876,11 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             setattr(a, field, _chk(t, _ARG_NAMES[field], dev))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if per_probe is None:
+        if push is not None:
+            what = "ff_mlp_ode_launch_push"
+            rc = lib().ff_mlp_ode_launch_push(ctypes.byref(p), ctypes.byref(a), _chk(push[0], "cond_tangents", dev),
+                                              _chk(push[1], "tangent_out", dev), ctypes.c_void_p(stream))
+        elif per_probe is None:
             what = "ff_mlp_ode_launch"
             rc = lib().ff_mlp_ode_launch(ctypes.byref(p), ctypes.byref(a), ctypes.c_void_p(stream))
         else:
@@ -935,6 +975,57 @@ def mlp_ode_probes(x: torch.Tensor, cond: Optional[torch.Tensor], probe: torch.T
 def _(x, cond, probe, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, tangent_count=0):
     B = x.shape[0]
     return (torch.empty_like(x), x.new_empty(B), x.new_empty(B, max(int(tangent_count), 1)),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_push", mutates_args=())
+def mlp_ode_push(x: torch.Tensor, cond: Optional[torch.Tensor], tangents: Optional[torch.Tensor],
+                 cond_tangents: Optional[torch.Tensor], wpack: torch.Tensor, etab: torch.Tensor,
+                 in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor],
+                 out_shift: Optional[torch.Tensor], plan: List[int], unit: bool, tangent_first: int,
+                 tangent_count: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused fixed-grid solve with K = ``tangent_count`` tangents per sample pushed through it
+    (ff_mlp_ode_launch_push): returns (final state [B, D], tangent_out [B, K, D], status [1]) with
+    ``tangent_out[b, k] = d x_out[b] / d (x[b], cond[b]) . (v_k, c_k)``, the derivative of the discrete solver map.
+    ``unit=False``: v = ``tangents`` [B, K, D] (None = zero), c = ``cond_tangents`` [B, K, C] (None = zero).
+    ``unit=True``: the unit vectors ``tangent_first .. tangent_first + K - 1`` of the combined space [0, D + C)."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_push needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    B, D = x.shape
+    K = int(tangent_count)
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    if K < 1:
+        raise RuntimeError(f"tangent_count={tangent_count}: at least one tangent per sample")
+    x_out = torch.empty_like(x)
+    t_out = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, t_out, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if unit and (tangents is not None or cond_tangents is not None):
+        raise RuntimeError("unit tangents take no tangent buffers")
+    if tangents is not None and tuple(tangents.shape) != (B, K, D):
+        raise RuntimeError(f"tangents has shape {tuple(tangents.shape)}, expected {(B, K, D)}")
+    if cond_tangents is not None and tuple(cond_tangents.shape) != (B, K, p.cond_dim):
+        raise RuntimeError(f"cond_tangents has shape {tuple(cond_tangents.shape)}, expected {(B, K, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": tangents, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                push=(cond_tangents, t_out), x_out=x_out.data_ptr(), status=status.data_ptr(), batch=B,
+                n_evals=etab.shape[0], mode=MODE_EXACT if unit else MODE_HUTCH, tangent_first=tangent_first if unit else 0,
+                tangent_count=K, stage_slots=_slots_hint(plan))
+    return x_out, t_out, status
+
+
+@mlp_ode_push.register_fake
+def _(x, cond, tangents, cond_tangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, unit, tangent_first,
+      tangent_count):
+    return (torch.empty_like(x), x.new_empty(x.shape[0], int(tangent_count), x.shape[1]),
             torch.empty(1, dtype=torch.int32, device=x.device))
 
 

@@ -118,6 +118,22 @@ def _pairsel_name(tile, h, d, c, wps, ring) -> str:
     return _pair_name(tile, h, d, c, wps, ring).replace("mlp_pair_", "mlp_pairsel_", 1)
 
 
+# Push-forward units (ff_mlp_ode.hpp PUSH; ff_mlp_push_plan): the tangent columns integrate the variational equation --
+# flow_jvp / flow_jacobian.  (TILE, H, DREGS, CREGS, WPS, RING): SiLU, fp32, one wavefront per tile; the shapes, occupancy
+# and rings of the Hutchinson units of the same widths.  Width <= 128 / 256 with dim <= 16, width <= 256 with dim <= 32;
+# cond_dim <= 16; up to 15 tangents per sample.  A family of its own: not in the ff_kernel_count / ff_kernel_name table, no
+# cooperative twins, no wide, split-precision or run-time-activation units.
+PUSH_INSTANCES = [
+    (16, 128, 4, 4, 3, 4),
+    (16, 256, 4, 4, 2, 8),
+    (16, 256, 8, 4, 2, 8),
+]
+
+
+def _push_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_push_m{tile}_h{h}_d{d}_c{c}_w{wps}"
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -214,7 +230,7 @@ def _write(path: Path, text: str) -> Path:
     return path
 
 
-def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None, select=None) -> list[Path]:
+def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None, select=None, push=None) -> list[Path]:
     """The translation units of a library: the product's (default arguments) or a test variant's instance lists."""
     GEN = gen if gen is not None else globals()["GEN"]
     INSTANCES = instances if instances is not None else globals()["INSTANCES"]
@@ -222,6 +238,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     SPLIT_INSTANCES = split if split is not None else globals()["SPLIT_INSTANCES"]
     PAIR_INSTANCES = pair if pair is not None else globals()["PAIR_INSTANCES"]
     SELECT = select if select is not None else globals()["PAIR_SELECT_INSTANCES"]       # (a subset of PAIR_INSTANCES)
+    PUSH_INSTANCES = push if push is not None else globals()["PUSH_INSTANCES"]
     GEN.mkdir(parents=True, exist_ok=True)
     tf = lambda t: "true" if t else "false"
     # every launcher of the library: (name, header, kernel expression) -> a translation unit, a declaration, a table cell
@@ -245,6 +262,9 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
             units.append((name, "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, {wps}, {ring}{one_wave}>"))
             if _has_coop(h):
                 units.append((f"{name}_coop", "ff_mlp_pair.hpp", f"mlp_pair_kernel<{tile}, {h}, {d}, {c}, 2, 4{coop}>"))
+    for tile, h, d, c, wps, ring in PUSH_INSTANCES:
+        units.append((_push_name(tile, h, d, c, wps, ring), "ff_mlp_ode.hpp",
+                      f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, true, {wps}, {ring}, 0, false, false, true>"))
     files = [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr)) for name, header, expr in units]
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
@@ -272,6 +292,9 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
         split_rows = '    {0, 0, 0, 0, 0, nullptr, ""}'
     if not PAIR_INSTANCES:           # (the test variants carry no pair kernels)
         pair_rows = '    {0, 0, 0, 0, 0, {nullptr, nullptr, ""}, {nullptr, nullptr, ""}}'
+    push_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_push_name(*i)}, "{_push_name(*i)}"}}' for i in PUSH_INSTANCES
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (the test variants carry no push kernels)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 namespace ff {{
@@ -288,6 +311,10 @@ const PairKernelEntry g_pair_kernels[] = {{
 {pair_rows}
 }};
 const int g_n_pair_kernels = {len(PAIR_INSTANCES)};
+const PushKernelEntry g_push_kernels[] = {{
+{push_rows}
+}};
+const int g_n_push_kernels = {len(PUSH_INSTANCES)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -315,6 +342,8 @@ def _cost(src: Path) -> float:
         return 95 if "_t1" in n else 55
     if "_h512_" in n:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
+    if n.startswith("mlp_push_"):
+        return 16 if "_h256_" in n else 6
     if n.startswith("mlp_pairsel_"):
         return (7 if "_h256_" in n else 3) if "_coop" in n else (16 if "_h256_" in n else 7)
     if n.startswith("mlp_pair_"):
@@ -401,7 +430,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
         for name, v in VARIANTS.items():
             gen, obj = PKG / "_build" / f"gen_{name}", PKG / "_build" / f"obj_{name}"
             obj.mkdir(parents=True, exist_ok=True)
-            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"], select=v.get("select", []))
+            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"], select=v.get("select", []), push=[])
             extra[name] = (vs, obj, tuple(v["defines"]))
             units += [(s, obj, tuple(v["defines"])) for s in vs]
     jobs = jobs or min(8, os.cpu_count() or 1)

@@ -12,7 +12,8 @@
 static_assert(FF_MAX_SLOTS == ff::kSlots, "slot count mismatch between header and kernel");
 static_assert(FF_MAX_AUX == ff::kAux, "aux count mismatch between header and kernel");
 static_assert(FF_ROW_HDR * 4 == sizeof(ff::RowHdr), "row header mismatch");
-static_assert(FF_STATUS_NAN == ff::kStatusNaN && FF_STATUS_BAD_SLOT == ff::kStatusBadSlot, "status bits mismatch");
+static_assert(FF_STATUS_NAN == ff::kStatusNaN && FF_STATUS_BAD_SLOT == ff::kStatusBadSlot && FF_STATUS_NOISE_ROW == ff::kStatusNoiseRow,
+              "status bits mismatch");
 static_assert(sizeof(ff_adapt_state) == 128, "controller state is 128 bytes");
 
 static thread_local int t_last_hip_error = 0;
@@ -156,7 +157,7 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
 // ---- what a plan launches, as data ------------------------------------------------------------------------------------
 // describe() validates a plan once and says everything the code below needs to know about its family: the launcher,
 // ff_mlp_launch_kind and the small queries read the description and never ask which family they serve.
-enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect };
+enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush };
 
 struct LaunchDesc {
     PlanFamily family;
@@ -224,6 +225,18 @@ static bool describe(const ff_mlp_plan_t* p, LaunchDesc* d)
         d->max_aux = FF_MAX_AUX; d->takes_k1 = true; d->empty_batch_first = true;
         return true;
     }
+    if (p->kernel_id >= FF_PUSH_KERNEL_BASE) {
+        // push-forward units: the Hutchinson kernels' shapes with the tangent columns integrated; one wavefront per tile, whole
+        // fixed-grid solves only (no first stage from the caller, no auxiliary outputs)
+        const int index = p->kernel_id - FF_PUSH_KERNEL_BASE;
+        if (index >= ff::g_n_push_kernels) return false;
+        const ff::PushKernelEntry& k = ff::g_push_kernels[index];
+        if (!k.launch || !shape_ok(p, k.tile, k.H, k.dregs, k.cregs) || p->activation != FF_ACT_SILU) return false;
+        d->family = kPush; d->name = k.name; d->one_wave = k.launch;
+        twin_line(d, k.wps);
+        d->tangents = 1; d->nets = 1; d->row_nets = 1; d->exchange = 2;
+        return true;
+    }
     const bool select = p->kernel_id >= FF_PAIR_SELECT_KERNEL_BASE;
     const int index = p->kernel_id - (select ? FF_PAIR_SELECT_KERNEL_BASE : FF_PAIR_KERNEL_BASE);
     if (index < 0 || index >= ff::g_n_pair_kernels) return false;
@@ -256,7 +269,7 @@ namespace ff {
 bool plan_steps_adaptively(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
-    return describe(plan, &d) && d.family != kSelect;
+    return describe(plan, &d) && d.family != kSelect && d.family != kPush;
 }
 }
 
@@ -272,6 +285,31 @@ extern "C" int ff_mlp_row_width(const ff_mlp_plan_t* plan)
     if (!plan) return -1;
     LaunchDesc d;
     return describe(plan, &d) ? d.row_nets * plan->width : plan->width;
+}
+
+extern "C" int ff_push_kernel_count(void) { return ff::g_n_push_kernels; }
+
+extern "C" const char* ff_push_kernel_name(int index)
+{
+    return index >= 0 && index < ff::g_n_push_kernels ? ff::g_push_kernels[index].name : NULL;
+}
+
+// the smallest push-forward unit that holds the network (best_entry's preference: narrowest width, then fewest first-layer
+// features): SiLU, fp32
+extern "C" int ff_mlp_push_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, int activation, int precision,
+                                ff_mlp_plan_t* plan)
+{
+    if (!plan || !hidden_widths || dim < 1 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
+    if (activation < 0 || activation >= FF_ACT_COUNT) return FF_ERR_BADARG;
+    if (precision != FF_PREC_F32 && precision != FF_PREC_BF16X3 && precision != FF_PREC_BF16X2) return FF_ERR_BADARG;
+    const int wmax = widest(n_hidden, hidden_widths);
+    if (wmax < 0) return FF_ERR_BADARG;
+    if (activation != FF_ACT_SILU || precision != FF_PREC_F32) return FF_ERR_UNSUPPORTED;
+    const int best = best_entry(ff::g_push_kernels, ff::g_n_push_kernels, dim, cond_dim, wmax,
+                                [](const ff::PushKernelEntry& k) { return k.launch != nullptr; });
+    if (best < 0) return FF_ERR_UNSUPPORTED;
+    const ff::PushKernelEntry& k = ff::g_push_kernels[best];
+    return fill_plan(plan, dim, cond_dim, n_hidden, k.H, k.dregs, k.cregs, FF_PUSH_KERNEL_BASE + best, k.tile, FF_ACT_SILU);
 }
 
 extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
@@ -719,9 +757,16 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
         if (t.cond) t.cond += row0 * C;
         if (t.probe) t.probe += row0 * D * (t.unit_tangents ? 1 : t.n_tangent);       // Hutchinson probes: [batch, n_tangent, dim]
         if (t.dlogp_probe_out) t.dlogp_probe_out += row0 * t.n_tangent;                // per-probe divergences: [batch, n_tangent]
-        if (t.dlogp_out) t.dlogp_out += row0;
+        if (d.family == kPush) {
+            // (push plans have no twin today, so they never get here; a cooperative push unit would.  Their two pointers share
+            // the places of dlogp_out and noise: ff_kernel_args.h)
+            if (t.cond_tangent) t.cond_tangent += row0 * t.n_tangent * C;              // [batch, n_tangent, cond_dim]
+            t.tangent_out += row0 * t.n_tangent * D;                                   // [batch, n_tangent, dim]
+        } else {
+            if (t.dlogp_out) t.dlogp_out += row0;
+            if (t.noise) t.noise += row0 * D;
+        }
         if (t.dlogp_in) t.dlogp_in += row0;
-        if (t.noise) t.noise += row0 * D;
         if (t.k1_in) t.k1_in += row0 * D;
         if (t.kl1_in) t.kl1_in += row0;
         for (int j = 0; j < FF_MAX_AUX; ++j) {
@@ -735,11 +780,25 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
     return FF_OK;
 }
 
-// ff_mlp_ode_launch (probe_out == NULL) and ff_mlp_ode_launch_probes: one argument check, one launch path
-static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream)
+// What ff_mlp_ode_launch_push adds to a launch (NULL: not a push launch).
+struct PushIo {
+    const float* cond_tangent;
+    float* tangent_out;
+};
+
+// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes and ff_mlp_ode_launch_push: one argument check, one launch path
+static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr)
 {
     LaunchDesc d;
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
+    if (push && d.family == kSplit) return FF_ERR_UNSUPPORTED;
+    if ((d.family == kPush) != (push != nullptr)) return FF_ERR_BADARG;      // push plans launch through their own entry, and only they
+    if (push) {
+        // whole fixed-grid solves of the state and its tangents: nothing of the divergence side, no attempt launches, no noise
+        if (!push->tangent_out || a->mode == FF_MODE_STATE || a->tangent_count < 0) return FF_ERR_BADARG;
+        if (a->dlogp_out || a->k1_in || a->kl1_in || a->dlogp_in || a->jac_out || a->n_aux > 0 || a->noise) return FF_ERR_BADARG;
+        if (push->cond_tangent && (plan->cond_dim == 0 || a->mode == FF_MODE_EXACT)) return FF_ERR_BADARG;
+    }
     if (probe_out) {
         // per-probe divergences: Hutchinson launches of the fp32 single-network family that are whole solves (an attempt
         // launch carries a sample's stage-0 divergence on ONE lane: kl1_in / dlogp_in / aux_lp_out have no per-probe form)
@@ -755,10 +814,13 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     if (rc) return rc;
     int tfirst = 0;
     if (a->mode == FF_MODE_EXACT) {
+        // (a push launch: the unit tangents run over the state's dimensions, then the conditional inputs)
+        const int span = push ? plan->dim + plan->cond_dim : plan->dim;
+        if (push) nt = span < plan->tile - 1 ? span : plan->tile - 1;
         tfirst = a->tangent_first;
         if (a->tangent_count > 0) nt = a->tangent_count;
-        else if (plan->dim > nt) return FF_ERR_BADARG;      // must be split by the caller
-        if (tfirst < 0 || tfirst + nt > plan->dim || nt + 1 > plan->tile) return FF_ERR_BADARG;
+        else if (span > nt) return FF_ERR_BADARG;           // must be split by the caller
+        if (tfirst < 0 || tfirst + nt > span || nt + 1 > plan->tile) return FF_ERR_BADARG;
     }
     if (a->mode == FF_MODE_HUTCH && a->tangent_count > 1) {      // K probes per sample: probe is [batch, K, dim]
         nt = a->tangent_count;
@@ -766,8 +828,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     }
     // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
     if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;
-    if (a->mode == FF_MODE_HUTCH && !a->probe) return FF_ERR_BADARG;
-    if (a->mode != FF_MODE_STATE && !a->dlogp_out) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && !a->probe && !push) return FF_ERR_BADARG;      // (push: no state tangents = zero)
+    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push) return FF_ERR_BADARG;
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->batch == 0 && d.empty_batch_first) return FF_OK;
     if (a->n_aux < 0 || a->n_aux > d.max_aux || (a->k1_in && !d.takes_k1)) return FF_ERR_BADARG;
@@ -782,6 +844,7 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
     ka.dlogp_probe_out = probe_out;
+    if (push) { ka.cond_tangent = push->cond_tangent; ka.tangent_out = push->tangent_out; }
     return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
 }
 
@@ -793,6 +856,13 @@ extern "C" int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* a
 extern "C" int ff_mlp_ode_launch_probes(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* dlogp_probe_out, void* hip_stream)
 {
     return launch_ode(plan, a, dlogp_probe_out, hip_stream);
+}
+
+extern "C" int ff_mlp_ode_launch_push(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* cond_tangent, float* tangent_out,
+                                      void* hip_stream)
+{
+    const PushIo io = {cond_tangent, tangent_out};
+    return launch_ode(plan, a, nullptr, hip_stream, &io);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

@@ -12,8 +12,18 @@ struct KernelArgs {
     float* x_out;
     const float* cond;
     const float* probe;
-    float* dlogp_out;
-    const float* noise;
+    // (the two unions: a push-forward launch -- mlp_ode_kernel PUSH, ff_mlp_ode_launch_push -- integrates no divergence and takes no
+    // noise, and the launcher refuses dlogp_out and noise for it; its two pointers take those places, so the block keeps its size:
+    // ANY growth, 8 bytes included, makes the compiler re-allocate the registers of five 32-column units and costs one of them
+    // 1.3 % -- profiles/pushforward_resources.txt)
+    union {
+        float* dlogp_out;
+        float* tangent_out;          // PUSH: [batch, n_tangent, dim] d x_out / d (x_in, cond) . tangent
+    };
+    union {
+        const float* noise;
+        const float* cond_tangent;   // PUSH: [batch, n_tangent, cond_dim] conditional part of every tangent (constant over the solve) or NULL = zero
+    };
     const float* wpack;
     const float* etab;
     const float* in_shift;
@@ -55,5 +65,6 @@ struct KernelArgs {
 // bits of the status word (ff_ode_args.status)
 constexpr unsigned kStatusNaN = 1u;        // a final state holds a NaN
 constexpr unsigned kStatusBadSlot = 2u;    // an evaluation row named a stage slot this kernel does not keep on chip
+constexpr unsigned kStatusNoiseRow = 4u;   // push-forward units: the table holds a noise row (no tangent form)
 
 } // namespace ff

@@ -436,11 +436,18 @@ namespace ff {
 // B operands are read from the LDS exchange buffer group by group (one ds_read_b128 per 4 operand registers, one group
 // ahead of the MFMAs that use it) instead of all at once after the exchange; one exchange buffer and a second barrier
 // per layer (everybody has finished reading before anybody overwrites).  Same packed layout and FMA chains.
+//
+// PUSH (with TANGENTS; the push-forward units of ff_mlp_ode_launch_push): the tangent columns take the stage algebra of the
+// value column -- their right-hand side a_e v + b_e J_net (v, c) is stored in their stage slots instead of zero -- so they
+// integrate the variational equation with the same tableau, and what leaves is the derivative of the discrete solver map,
+// d x_out / d (x_in, cond) . tangent, in tangent_out.  The divergence bookkeeping is compiled out.
 template <int TILE, int H, int DREGS, int CREGS, bool TANGENTS, int WPS, int RING, int ACT = 0, bool COOP = false,
-          bool WIDE = false>
+          bool WIDE = false, bool PUSH = false>
 __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args)
 {
     static_assert(!WIDE || COOP, "the wide variant is a cooperative kernel");
+    static_assert(!PUSH || TANGENTS, "the push-forward units carry tangent columns");
+    constexpr bool DIVERGENCE = TANGENTS && !PUSH;      // the tangent columns feed a divergence integral
     static_assert(kChunkPad % RING == 0, "ring must divide the chunk padding");
     static_assert(!COOP || (H / 32) % 4 == 0, "the cooperative twin splits the blocks of a layer four ways");
     typedef Tile<TILE> T;
@@ -497,9 +504,20 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
 #pragma unroll
         for (int r = 0; r < CREGS; ++r) cnd[r] = cond_reg<TILE>(args, sample, qd, is_tangent, r);
     }
+    // push-forward: a tangent column starts from its tangent's state part and keeps its conditional part
+    if constexpr (PUSH) {
+        if (is_tangent) {
+#pragma unroll
+            for (int r = 0; r < DREGS; ++r) x[r] = push_state_reg<TILE>(args, sample, qd, role, r);
+            if constexpr (CREGS > 0) {
+#pragma unroll
+                for (int r = 0; r < CREGS; ++r) cnd[r] = push_cond_reg<TILE>(args, sample, qd, role, r);
+            }
+        }
+    }
 
     // Hutchinson: a tangent column's vector is its probe (state_reg left it zero)
-    if constexpr (TANGENTS) {
+    if constexpr (DIVERGENCE) {
         if (is_tangent && !args.unit_tangents) {
 #pragma unroll
             for (int r = 0; r < DREGS; ++r) x[r] = probe_reg<TILE>(args, sample, qd, role, r);
@@ -507,7 +525,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     }
     // tangent lanes: e.e restricted to this lane's features
     float ee = 0.f;
-    if constexpr (TANGENTS) {
+    if constexpr (DIVERGENCE) {
 #pragma unroll
         for (int r = 0; r < DREGS; ++r) ee = __builtin_fmaf(x[r], x[r], ee);
     }
@@ -530,7 +548,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     for (int s = 0; s < kSlots; ++s) kl[s] = 0.f;
     float lp = 0.f;
     init_stage_slots<TILE, DREGS, COOP, FILL_BARRIER>(args, ks, sample, qd, is_tangent, wv == kSkewWave);
-    if constexpr (TANGENTS) {
+    if constexpr (DIVERGENCE) {
         // the per-sample divergence of stage 0 is carried by ONE lane of the sample (first tangent
         // column, lane group 0); all other lanes integrate their own partial sums from zero
         if (args.kl1_in && role == 1 && qd == 0) kl[0] = args.kl1_in[sample];
@@ -568,6 +586,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     }
 
     bool bad_slot = false;
+    [[maybe_unused]] bool bad_noise = false;
     // Cooperative twin: the exchange buffer of the NEXT activation hand-over.  It alternates over the whole launch, not per
     // evaluation: with an odd number of hidden layers a per-evaluation count would end one evaluation and start the next on
     // the same buffer, with a single barrier between a slow wavefront's reads of the old contents and a fast one's stores.
@@ -599,7 +618,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
 
         // noise for this row (requested early, consumed after the network)
         float nz[DREGS];
-        if ((flags & 2u) && args.noise) {
+        if (!PUSH && (flags & 2u) && args.noise) {        // (PUSH: the field holds cond_tangent, and noise rows are left out)
             const float* np = args.noise + (size_t)hdr->noise_idx * args.noise_stride + sample * D;
 #pragma unroll
             for (int r = 0; r < DREGS; ++r) {
@@ -784,7 +803,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
         // ---- RHS and stage bookkeeping -----------------------------------------------------
         float rhs[DREGS];
         float div = 0.f;
-        if constexpr (TANGENTS) {
+        if constexpr (DIVERGENCE) {
             float dot = 0.f;
 #pragma unroll
             for (int r = 0; r < DREGS; ++r) dot = __builtin_fmaf(x[r], net[r], dot);
@@ -804,7 +823,8 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
 #pragma unroll
         for (int r = 0; r < DREGS; ++r) {
             const float v = __builtin_fmaf(a_e, y[r], b_e * net[r]);
-            rhs[r] = is_tangent ? 0.f : v;
+            if constexpr (PUSH) rhs[r] = v;        // tangent columns: a_e v + b_e J_net (v, c), the variational equation
+            else rhs[r] = is_tangent ? 0.f : v;
         }
         // (a row naming a slot beyond the kSlots on chip is refused: nothing is stored, the status word says so)
         const bool slot_ok = (unsigned)slot < (unsigned)kSlots;
@@ -814,7 +834,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
             for (int j = 0; j < R4; ++j)
                 ks[(slot * R4 + j) * 64] = f32x4{rhs[4 * j], rhs[4 * j + 1], rhs[4 * j + 2], rhs[4 * j + 3]};
         }
-        if constexpr (TANGENTS) {
+        if constexpr (DIVERGENCE) {
 #pragma unroll
             for (int s = 0; s < kSlots; ++s) kl[s] = (slot == s) ? div : kl[s];
         }
@@ -827,12 +847,14 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
 #pragma unroll
                 for (int i = 0; i < 4; ++i) x[4 * j + i] = v[i];
             }
-            if constexpr (TANGENTS) {
+            if constexpr (DIVERGENCE) {
 #pragma unroll
                 for (int s = 0; s < kSlots; ++s) lp = __builtin_fmaf(hdr->cout[s], kl[s], lp);
             }
         }
-        if (flags & 2u) {
+        if constexpr (PUSH) {
+            bad_noise |= (flags & 2u) != 0;        // a noise row has no tangent form: left out, and reported
+        } else if (flags & 2u) {
             if constexpr (!TANGENTS) {
                 if (!args.noise) {
 #pragma unroll
@@ -864,7 +886,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
     };
     const bool writer = col_live && !is_tangent && (!COOP || wv == 0);
     float lp0 = 0.f;
-    if constexpr (TANGENTS) {
+    if constexpr (DIVERGENCE) {
         if (args.dlogp_in) lp0 = args.dlogp_in[sample];
         // per-probe output (ff_mlp_ode_launch_probes; a wave-uniform test): tangent column j's own integral, summed over its
         // lane groups in ascending order -- the order reduce_tangents takes them, so with one tangent column the value is
@@ -911,7 +933,7 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
                         if (writer && d < D && args.aux_out[j]) args.aux_out[j][sample * D + d] = v[i];
                     }
                 }
-                if constexpr (TANGENTS) {
+                if constexpr (DIVERGENCE) {
                     float part = 0.f;
 #pragma unroll
                     for (int s = 0; s < kSlots; ++s) part = __builtin_fmaf(c[s], kl[s], part);
@@ -936,11 +958,31 @@ __global__ __launch_bounds__(256, WPS) void mlp_ode_kernel(const KernelArgs args
             }
         }
     }
+    // push-forward: every live tangent column stores its own vector, through the linear part of the output map (no shift)
+    if constexpr (PUSH) {
+        if (col_live && is_tangent && (!COOP || wv == 0)) {
+            float* const tp = args.tangent_out + (sample * args.n_tangent + (role - 1)) * D;
+#pragma unroll
+            for (int r = 0; r < DREGS; ++r) {
+                const int d = feat_of_reg(TILE, r, qd);
+                if (d < D) {
+                    float v = x[r];
+                    if (args.out_scale) v = v * args.out_scale[d];
+                    tp[d] = v;
+                }
+            }
+        }
+    }
     if (args.status && __any(bad)) {
         if (lane == 0) atomicOr(args.status, kStatusNaN);
     }
     if (args.status && bad_slot) {
         if (lane == 0) atomicOr(args.status, kStatusBadSlot);
+    }
+    if constexpr (PUSH) {
+        if (args.status && bad_noise) {
+            if (lane == 0) atomicOr(args.status, kStatusNoiseRow);
+        }
     }
 }
 

@@ -51,6 +51,36 @@ __device__ __forceinline__ float cond_reg(const KernelArgs& args, long long samp
     const int d = feat_of_reg(TILE, r, qd);
     return (d < C && !is_tangent) ? args.cond[sample * C + d] : 0.f;
 }
+// Push-forward units (mlp_ode_kernel PUSH): one register of a tangent column's start vector, state part and conditional
+// part.  unit_tangents == 0: probe[sample, role - 1, :] / cond_tangent[sample, role - 1, :] (NULL = zero).  unit_tangents
+// == 1: the unit vector j = tangent_first + role - 1 of the combined space [0, D + C) -- j < D the state unit vector e_j,
+// j >= D a zero state part and the conditional unit vector e_{j - D}.  The state part goes through the linear part of the
+// input map, v / in_scale[d] (no shift: it is a derivative); the conditional part is taken as it is.
+template <int TILE>
+__device__ __forceinline__ float push_state_reg(const KernelArgs& args, long long sample, int qd, int role, int r)
+{
+    const int D = args.dim;
+    const int d = feat_of_reg(TILE, r, qd);
+    float v = 0.f;
+    if (d < D) {
+        if (args.unit_tangents) v = (d == args.tangent_first + role - 1) ? 1.0f : 0.0f;
+        else if (args.probe) v = args.probe[(sample * args.n_tangent + (role - 1)) * D + d];
+        if (args.in_scale) v = v / args.in_scale[d];
+    }
+    return v;
+}
+template <int TILE>
+__device__ __forceinline__ float push_cond_reg(const KernelArgs& args, long long sample, int qd, int role, int r)
+{
+    const int C = args.cond_dim;
+    const int d = feat_of_reg(TILE, r, qd);
+    float v = 0.f;
+    if (d < C) {
+        if (args.unit_tangents) v = (args.dim + d == args.tangent_first + role - 1) ? 1.0f : 0.0f;
+        else if (args.cond_tangent) v = args.cond_tangent[(sample * args.n_tangent + (role - 1)) * C + d];
+    }
+    return v;
+}
 // ---- stage slots ----------------------------------------------------------------------------------------------------------
 // Zero fill of the Runge-Kutta stage slots `ks` (LDS; each lane only ever touches its own words), then the caller's first
 // stage (k1_in: FSAL of the previous step) into slot 0.

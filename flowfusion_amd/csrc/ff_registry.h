@@ -64,4 +64,18 @@ struct PairKernelEntry {
 extern const PairKernelEntry g_pair_kernels[];
 extern const int g_n_pair_kernels;
 
+// push-forward family (mlp_ode_kernel PUSH, ff_mlp_push_plan): SiLU, fp32, one wavefront per tile, no twin; a push plan's
+// kernel_id is FF_PUSH_KERNEL_BASE + the index into this table
+struct PushKernelEntry {
+    int tile;       // MFMA columns per wavefront
+    int H;          // hidden width on chip
+    int dregs;      // state registers
+    int cregs;      // conditional registers
+    int wps;        // wavefronts per SIMD (launch bound)
+    LaunchFn launch;        // NULL: the library carries no push kernels (test variants)
+    const char* name;
+};
+extern const PushKernelEntry g_push_kernels[];
+extern const int g_n_push_kernels;
+
 } // namespace ff

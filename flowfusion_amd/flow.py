@@ -186,6 +186,47 @@ class _FlowBase(nn.Module):
             self.dlogp_probes = d
         return xT, logj.view(-1, 1), (trace_estimators.hutchinson_stderr(d).view(-1, 1) if stderr else None)
 
+    # -- flow-map sensitivities (extension) -------------------------------------------------------------------------------
+    def _push_args(self, x, conditional, direction):
+        """(t_span, keywords of ``odeint.solve_push``) of a sensitivity solve: ``to_data`` is ``sample``'s solve (base point
+        -> target space, ``* target_scale + target_shift`` in the kernel), ``to_base`` is ``log_prob``'s (target-space point
+        -> base, ``(x - target_shift) / target_scale`` in the kernel); the raw ``conditional`` is normalised as everywhere."""
+        if direction not in ("to_data", "to_base"):
+            raise ValueError(f"direction={direction!r}: 'to_data' (the solve of sample) or 'to_base' (the solve of log_prob)")
+        C = getattr(self, "conditional_dimension", 0)
+        kw = {}
+        if conditional is not None:
+            if C == 0:
+                raise ValueError("flow-map sensitivities: this flow has no conditional inputs")
+            if not torch.is_tensor(conditional) or conditional.dim() != 2 or conditional.shape[1] != C:
+                raise ValueError(f"flow-map sensitivities: conditional must be [batch, {C}]")
+            kw = {"cond": self._norm_cond(conditional), "cond_tangent_scale": self.conditional_scale}
+        if direction == "to_data":
+            return torch.tensor([1.0, 0.0], dtype=torch.float32), dict(kw, out_scale=self.target_scale, out_shift=self.target_shift)
+        return torch.tensor([0.0, 1.0], dtype=torch.float32), dict(kw, in_shift=self.target_shift, in_scale=self.target_scale)
+
+    @torch.no_grad()
+    def flow_jvp(self, x, tangents=None, conditional=None, conditional_tangents=None, *, direction="to_data", method="rk4",
+                 options=None):
+        """Extension: the solve of ``sample`` (``direction="to_data"``, ``x`` = base points) or of ``log_prob``
+        (``"to_base"``, ``x`` = target-space points) with K directions pushed through it, forward mode, in ONE launch:
+        returns ``(x_out [B, D], dx [B, K, D])`` with ``dx[b, k] = d x_out[b] / d (x[b], conditional[b]) . (tangents[b, k],
+        conditional_tangents[b, k])`` -- the exact derivative of the DISCRETE solver map (fixed grids only: ``method="rk4"``
+        / ``"dopri5_fixed"`` / ``"euler"`` ... with ``options={"step_size": h}``), in the units of ``x``, ``x_out`` and the
+        raw ``conditional``.  ``tangents`` [B, K, D] and ``conditional_tangents`` [B, K, C]: either may be None (zero);
+        K <= 15.  No parameter gradients, no torch.autograd integration (the call runs under ``no_grad``), no adaptive step
+        control: see ``odeint.solve_push``."""
+        t_span, kw = self._push_args(x, conditional, direction)
+        return odeint.solve_push(self, x, t_span, method, options, tangents=tangents, cond_tangents=conditional_tangents, **kw)
+
+    @torch.no_grad()
+    def flow_jacobian(self, x, conditional=None, *, direction="to_data", method="rk4", options=None):
+        """Extension: the whole Jacobian of the solver map of ``flow_jvp``: ``(x_out [B, D], J_x [B, D, D], J_c [B, D, C] or
+        None)``, ``J_x[b, i, j] = d x_out_i / d x_j``, ``J_c[b, i, j] = d x_out_i / d conditional_j``, from unit tangents
+        in ceil((D + C) / 15) launches."""
+        t_span, kw = self._push_args(x, conditional, direction)
+        return odeint.solve_push_jacobian(self, x, t_span, method, options, **kw)
+
     # -- the public methods' bodies, written once (``conditional=None``: the unconditional flow) -----------------------------
     def compute_linear_velocity_field(self, x0, xT, t):
         x0 = (x0 - self.target_shift) / self.target_scale

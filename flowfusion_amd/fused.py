@@ -152,8 +152,15 @@ class FusedNet:
         return _native.pack_weights(plan, [l.weight for l in self.linears], [l.bias for l in self.linears],
                                     self.hidden, self.x_col0, self.c_col0)
 
-    def wpack(self, device, mode: int) -> torch.Tensor:
-        plan = self.plan(mode)
+    def push_plan(self) -> _native.PlanStruct:
+        """The push-forward unit of this network (ff_mlp_push_plan); NotImplementedError with the envelope if none holds it."""
+        if "push" not in self._plans:
+            self._plans["push"] = _native.make_push_plan(self.dim, self.cond_dim, self.hidden, self.act,
+                                                         _native.PRECISIONS[self.precision])
+        return self._plans["push"]
+
+    def wpack(self, device, mode: int, plan=None) -> torch.Tensor:
+        plan = self.plan(mode) if plan is None else plan
         layout, vers = self._param_key(device, plan)
         hit = self._wpack.get(layout)
         if hit is None or hit[0] != vers:
@@ -212,6 +219,48 @@ class FusedNet:
             total = dl if total is None else total + dl
             status = st if status is None else (status | st)
         return y, total, status
+
+    def pushforward(self, x: torch.Tensor, etab: torch.Tensor, tangents: Optional[torch.Tensor] = None,
+                    cond: Optional[torch.Tensor] = None, cond_tangents: Optional[torch.Tensor] = None,
+                    unit: Optional[Tuple[int, int]] = None, in_shift=None, in_scale=None, out_scale=None, out_shift=None,
+                    stage_slots: int = 0):
+        """The fused fixed-grid solve of ``integrate`` with K tangents per sample pushed through it, on the push-forward
+        unit (``push_plan``; ``etab`` has ITS width).  Returns (y_final [B, D], dy [B, K, D], status [1]):
+        ``dy[b, k] = d y_final[b] / d (x[b], cond[b]) . (tangents[b, k], cond_tangents[b, k])``, the exact derivative of
+        the discrete solver map (either part may be None = zero), or with ``unit = (first, count)`` its columns for the
+        unit vectors ``first .. first + count - 1`` of the combined space [0, D + C).  The affine maps act on tangents
+        by their linear parts (``/ in_scale``, ``* out_scale``); ``cond`` and ``cond_tangents`` are taken as given.
+        ``y_final`` is bitwise the state of a ``num_probes=K`` Hutchinson ``integrate`` of the same rows."""
+        if not x.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {x.device}); there is no CPU fallback")
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(x.shape)}")
+        dev = x.device
+        plan = self.push_plan()
+        B = x.shape[0]
+        if self.cond_dim > 0:
+            if cond is None:
+                raise ValueError("this network has conditional inputs; `conditional` is required")
+            cond = f32_on(cond, dev)
+            if cond.dim() != 2 or cond.shape != (B, self.cond_dim):
+                raise ValueError(f"conditional must be [batch, {self.cond_dim}], got {tuple(cond.shape)}")
+        else:
+            cond = None
+        if unit is not None:
+            first, K = int(unit[0]), int(unit[1])
+            tangents = cond_tangents = None
+        else:
+            first = 0
+            given = tangents if tangents is not None else cond_tangents
+            if given is None or given.dim() != 3:
+                raise ValueError("pushforward: tangents [batch, K, dim] and / or cond_tangents [batch, K, cond_dim], or unit=(first, count)")
+            K = int(given.shape[1])
+        return torch.ops.flowfusion_amd.mlp_ode_push(
+            f32_on(x, dev), cond, f32_on(tangents, dev), f32_on(cond_tangents, dev), self.wpack(dev, MODE_HUTCH, plan),
+            f32_on(etab, dev), f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots), unit is not None, first, K)
 
     def cached_table(self, key, device, build):
         """Evaluation tables depend only on (time span, method, options, schedule parameters, first-layer

@@ -210,6 +210,133 @@ def _generic_per_probe(front, x, t_span, method, options, atol, rtol, e, p, keep
     return y, lp, torch.stack(cols, dim=1)
 
 
+def solve_push(front, x, t_span, method, options, tangents=None, cond=None, cond_tangents=None, unit=None, in_shift=None,
+               in_scale=None, out_scale=None, out_shift=None, tangent_gain=None, cond_tangent_scale=None):
+    """Flow-map sensitivities (extension): the fixed-grid solve of ``solve`` in MODE_STATE with K tangents per sample pushed
+    through it.  Returns ``(y [B, D], dy [B, K, D])`` with ``dy[b, k] = d y[b] / d (x[b], cond[b]) . (tangents[b, k],
+    cond_tangents[b, k])`` -- forward mode through the SAME discrete steps, so the exact derivative of the solver map, not
+    of the continuous flow (they agree to the order of the method).  ``tangents`` [B, K, D] / ``cond_tangents`` [B, K, C]:
+    either may be None (zero); ``unit = (first, count)`` instead of both: the unit vectors ``first .. first + count - 1`` of
+    the combined space [0, D + C), K = count.  ``cond`` and ``cond_tangents`` are the network's (normalised) conditional
+    inputs; the affine maps of ``solve`` act on the tangents by their linear parts, in the kernel.  What a front end did to
+    its inputs on the host follows here, after the checks: ``x * tangent_gain`` and ``tangents * tangent_gain`` (a VE
+    model's solve starts from the base samples times sigma_max; a tensor or None), ``cond_tangents / cond_tangent_scale``
+    (``cond`` is the caller's, normalised by that scale).
+
+    One launch of a push-forward unit per piece of rows (FusedNet.pushforward): the K tangents of a sample ride in K
+    columns of its tile beside its value column, as the probes of ``solve_hutchinson`` do, K <= 15.  Rows are cut by that
+    function's rule (a [rows, K, D] device buffer stays under ``PROBE_BUFFER_FLOATS`` floats); rows are independent, so the
+    result is bitwise the same for any cut.
+
+    Refused with ValueError before the device is touched: adaptive methods (the step control would have to be
+    differentiated too), ``grid_constructor`` / ``perturb``, K > 15, shapes that do not match, ``precision`` other than
+    f32.  NotImplementedError: a network outside the push-forward units, or a ``model=`` module (there is no module-path
+    fallback).  Out of scope: parameter gradients and torch.autograd integration, Euler-Maruyama, sharded entry points
+    (rows are independent: slice), split precision, activations other than SiLU."""
+    if method in solvers.ALL_ADAPTIVE or method in solvers.ADAPTIVE_METHODS:
+        raise ValueError(f"flow-map sensitivities with the adaptive method={method!r}: the tangents ride through the steps of a "
+                         "fixed grid (an adaptive solve would have to differentiate its step control); use method=\"rk4\" / "
+                         "\"dopri5_fixed\" with options={\"step_size\": h}")
+    solvers.resolve_method(method)
+    for name in ("grid_constructor", "perturb"):
+        if (options or {}).get(name) not in (None, False):
+            raise ValueError(f"flow-map sensitivities with options[{name!r}]: the grid is the uniform one of "
+                             "options={\"step_size\": h} (or the nodes of t_span)")
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError("flow-map sensitivities: x must be a [batch, dim] tensor")
+    B, D = int(x.shape[0]), int(x.shape[1])
+    prec = getattr(front, "precision", "f32")
+    if prec != "f32":
+        raise ValueError(f"flow-map sensitivities with precision={prec!r}: the push-forward kernels compute in f32; use "
+                         "precision='f32'")
+    try:
+        net = front._net()                  # (a ``model=`` module that is not the library's MLP raises here)
+        plan = net.push_plan()
+    except NotImplementedError as e:
+        msg = str(e)
+        raise NotImplementedError(msg if _native.PUSH_ENVELOPE in msg else
+                                  f"{msg} -- {_native.PUSH_ENVELOPE}; there is no module-path fallback") from None
+    if D != net.dim:
+        raise ValueError(f"flow-map sensitivities: x has {D} columns, the model has {net.dim} dimensions")
+    C = net.cond_dim
+    if C > 0 and (cond is None or cond.dim() != 2 or tuple(cond.shape) != (B, C)):
+        raise ValueError(f"flow-map sensitivities: conditional must be [{B}, {C}], got "
+                         f"{None if cond is None else tuple(cond.shape)}")
+    if C == 0 and (cond is not None or cond_tangents is not None):
+        raise ValueError("flow-map sensitivities: this model has no conditional inputs")
+    if unit is not None:
+        if tangents is not None or cond_tangents is not None:
+            raise ValueError("flow-map sensitivities: unit tangents take no tangent tensors")
+        first, K = int(unit[0]), int(unit[1])
+        if first < 0 or K < 1 or first + K > D + C:
+            raise ValueError(f"flow-map sensitivities: unit tangents [{first}, {first + K}) outside [0, {D + C})")
+    else:
+        if tangents is None and cond_tangents is None:
+            raise ValueError("flow-map sensitivities: tangents [batch, K, dim] and / or conditional_tangents [batch, K, cond_dim]")
+        given = tangents if tangents is not None else cond_tangents
+        if given.dim() != 3:
+            raise ValueError(f"flow-map sensitivities: tangents must be [batch, K, dim], got {tuple(given.shape)}")
+        K = int(given.shape[1])
+        if tangents is not None and tuple(tangents.shape) != (B, K, D):
+            raise ValueError(f"flow-map sensitivities: tangents has shape {tuple(tangents.shape)}, expected {(B, K, D)}")
+        if cond_tangents is not None and tuple(cond_tangents.shape) != (B, K, C):
+            raise ValueError(f"flow-map sensitivities: conditional_tangents has shape {tuple(cond_tangents.shape)}, "
+                             f"expected {(B, K, C)}")
+        if K < 1:
+            raise ValueError("flow-map sensitivities: at least one tangent per sample")
+    if K > _native.MAX_PUSH_TANGENTS or K + 1 > int(plan.tile):
+        raise ValueError(f"flow-map sensitivities: K={K} tangents per sample; a sample and its tangents share the "
+                         f"{int(plan.tile)} columns of one tile, so at most {_native.MAX_PUSH_TANGENTS} per call (flow_jacobian "
+                         "makes as many calls as it needs)")
+    require_fp32(front, x, cond, tangents, cond_tangents, what="a flow-map sensitivity solve")
+    _need_gpu(x)
+    if tangent_gain is not None:
+        x = x * tangent_gain
+        tangents = None if tangents is None else tangents * tangent_gain
+    if cond_tangent_scale is not None and cond_tangents is not None:
+        cond_tangents = cond_tangents / cond_tangent_scale
+    tab = solvers.plan_ode(t_span, method, options)          # (rows of a fixed-grid ODE method: none carries a noise flag)
+    width = int(plan.width)
+    key = ("push", tuple(float(v) for v in t_span), method, repr(sorted((options or {}).items()))) + front._schedule_key()
+    table = net.cached_table(key, x.device, lambda: solvers.build_table(tab, *front._host_schedule()(tab.t_eval), width))
+    rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D))
+    pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    ys, dys = [], []
+    for r0, r1 in pieces:
+        y, dy, _ = net.pushforward(cut(x, r0, r1), table, tangents=cut(tangents, r0, r1), cond=cut(cond, r0, r1),
+                                   cond_tangents=cut(cond_tangents, r0, r1), unit=None if unit is None else (first, K),
+                                   in_shift=in_shift, in_scale=in_scale, out_scale=out_scale, out_shift=out_shift,
+                                   stage_slots=solvers.resolve_method(method).stages)
+        ys.append(y)
+        dys.append(dy)
+    return (ys[0], dys[0]) if whole else (torch.cat(ys), torch.cat(dys))
+
+
+def solve_push_jacobian(front, x, t_span, method, options, cond=None, tangent_gain=None, cond_tangent_scale=None, **maps):
+    """The whole Jacobian of the flow map from ``solve_push`` with unit tangents: ``(y [B, D], J_x [B, D, D], J_c [B, D, C]
+    or None)``, ``J_x[b, i, j] = d y_i / d x_j``, ``J_c[b, i, j] = d y_i / d cond_j``, in ceil((D + C) / 15) launches per piece
+    of rows; ``y`` is the first launch's (every launch computes the same one, bit for bit).  ``tangent_gain`` /
+    ``cond_tangent_scale``: as in ``solve_push`` (the start is ``x * tangent_gain``), and applied to the columns of the
+    result (the chain rule's factors)."""
+    D = int(x.shape[1]) if torch.is_tensor(x) and x.dim() == 2 else 0
+    C = 0 if cond is None else int(cond.shape[-1])
+    y, cols = None, []
+    for first in range(0, max(D + C, 1), _native.MAX_PUSH_TANGENTS):
+        yk, dy = solve_push(front, x, t_span, method, options, cond=cond,
+                            unit=(first, min(_native.MAX_PUSH_TANGENTS, D + C - first)), **maps)
+        y = yk if y is None else y
+        cols.append(dy)
+    J = torch.cat(cols, dim=1).transpose(1, 2).contiguous()          # [B, D, D + C]: column j = the derivative along unit j
+    Jx, Jc = J[:, :, :D].contiguous(), (J[:, :, D:].contiguous() if C > 0 else None)
+    if tangent_gain is not None:
+        Jx = Jx * tangent_gain
+    if cond_tangent_scale is not None and Jc is not None:
+        Jc = Jc / cond_tangent_scale
+    return y, Jx, Jc
+
+
 def solve_leapfrog(front, x, grid, cond=None):
     """Kick-drift-kick leapfrog of a separable front end (symplectic.py) over the nodes ``grid``; returns the state
     [B, 2D] and sets ``front.last_solver_stats``.  Compiled shapes: ONE fused launch of the row-select kernel on the table

@@ -99,6 +99,13 @@ class SymplecticFlowModel(nn.Module):
         x = torch.randn(shape[0], shape[1] * 2, device=device)
         return self._sample_from(x, conditional, num_steps)
 
+    def flow_jvp(self, *args, **kwargs):
+        """Flow-map sensitivities (``ODEFlow.flow_jvp``) are not built for the two-network kernels."""
+        raise NotImplementedError("flow_jvp / flow_jacobian of a SymplecticFlowModel: the two-network kernels carry no tangent "
+                                  f"columns -- {_native.PUSH_ENVELOPE}, on ScoreModel, ODEFlow and ConditionalODEFlow")
+
+    flow_jacobian = flow_jvp
+
     @torch.no_grad()
     def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5):
         """``log N(z1) - log N(p0) - sum log scale`` with z1 the dopri5 solution over t: 0 -> 1 of [q0 | p0],

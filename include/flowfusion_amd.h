@@ -99,6 +99,8 @@ extern "C" {
                                    keep on chip (>= FF_MAX_SLOTS; >= 4 for the plans with four
                                    slots): that row's right-hand side was NOT stored,
                                    the results are invalid                                  */
+#define FF_STATUS_NOISE_ROW 4u  /* ff_mlp_ode_launch_push only: the table holds a row with
+                                   FF_ROW_NOISE, which has no tangent form: the results are invalid */
 
 /* evaluation-row flag bits (word 3 of the row header) */
 #define FF_ROW_STEP_END    1u   /* after this evaluation: y += sum_s cout[s] * k[s]        */
@@ -289,6 +291,49 @@ int ff_mlp_ode_launch(const ff_mlp_plan_t* plan, const ff_ode_args* args, void* 
 int ff_mlp_ode_launch_probes(const ff_mlp_plan_t* plan, const ff_ode_args* args,
                              float* dlogp_probe_out /* [batch, K], K = max(1, args->tangent_count) */,
                              void* hip_stream);
+
+/* ---- flow-map sensitivities: K tangents pushed through a fixed-grid solve ------------------------------------------------
+ * The push-forward units carry up to plan.tile - 1 tangent columns per sample like the Hutchinson kernels, but let them take
+ * the stage algebra of the value column: each integrates the variational equation  dv/ds = a_e v + b_e J_net(y, cond) (v, c)
+ * with the table's own tableau, c its constant conditional part.  What leaves is the exact derivative of the DISCRETE solver
+ * map,
+ *     tangent_out[b][k][:] = d x_out[b] / d (x_in[b], cond[b]) . (v_k, c_k)
+ * for K directions in one launch; with unit directions the whole Jacobian of the flow map.  x_out is bit for bit the x_out of
+ * an FF_MODE_HUTCH launch with tangent_count = K on the same rows.  The affine maps act on tangents by their linear parts:
+ * v / in_scale on the way in, * out_scale on the way out, no shift; the conditional part is taken as given.
+ *
+ * ff_mlp_push_plan: the smallest of the three compiled units that holds the network -- SiLU, fp32, hidden width <= 128
+ * with dim <= 16, width <= 256 with dim <= 16 or dim <= 32; cond_dim <= 16 -- else FF_ERR_UNSUPPORTED.  Its kernel_id is
+ * FF_PUSH_KERNEL_BASE + an index (kernel names mlp_push_...; not entries of ff_kernel_count).  The packed weights and the
+ * evaluation rows are those of any fp32 plan of the shape: ff_mlp_wpack[_floats], ff_mlp_row_width, ff_plan_kernel_name,
+ * ff_mlp_samples_per_workgroup accept the plan.  ff_mlp_ode_launch, ff_mlp_ode_launch_probes and ff_mlp_ode_adaptive refuse
+ * it (FF_ERR_BADARG).
+ *
+ * ff_mlp_ode_launch_push(plan, args, cond_tangent, tangent_out, stream): args as for ff_mlp_ode_launch with
+ *     args->mode == FF_MODE_HUTCH   tangents as given: K = max(1, args->tangent_count), state parts args->probe [batch, K, dim]
+ *                                   (NULL = zero), conditional parts cond_tangent [batch, K, cond_dim] (NULL = zero)
+ *     args->mode == FF_MODE_EXACT   unit tangents j = tangent_first .. tangent_first + K - 1 of the combined space
+ *                                   [0, dim + cond_dim): j < dim the state unit vector e_j, j >= dim the conditional unit
+ *                                   vector e_{j - dim}; K = tangent_count, 0 = all dim + cond_dim (which must then fit)
+ * and tangent_out DEVICE memory of batch * K * dim floats.  dlogp_out is not written.  Refused before anything is enqueued:
+ *     tangent_out NULL; K < 1 or K + 1 > plan->tile; mode FF_MODE_STATE                           FF_ERR_BADARG
+ *     dlogp_out, k1_in, kl1_in, dlogp_in or jac_out set, n_aux > 0                                FF_ERR_BADARG
+ *     `noise` set                                                                                 FF_ERR_BADARG
+ *     a unit range that reaches past dim + cond_dim; cond_tangent with cond_dim == 0, or with
+ *     unit tangents                                                                               FF_ERR_BADARG
+ *     a plan that is not a push plan                                                              FF_ERR_BADARG
+ *     a split-precision plan                                                                      FF_ERR_UNSUPPORTED
+ * Noise rows have no tangent form (Euler-Maruyama is out of scope).  The table lives in DEVICE memory, so the launcher cannot
+ * look for FF_ROW_NOISE flags before it enqueues: a push kernel that meets such a row leaves the noise out and ORs
+ * FF_STATUS_NOISE_ROW into args->status -- the results are invalid.  (The Python front ends take fixed-grid ODE methods only,
+ * whose tables hold no such row.) */
+#define FF_PUSH_KERNEL_BASE 0x40000
+int ff_push_kernel_count(void);
+const char* ff_push_kernel_name(int index);
+int ff_mlp_push_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, int activation, int precision,
+                     ff_mlp_plan_t* plan_out);
+int ff_mlp_ode_launch_push(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* cond_tangent /* [batch, K, cond_dim] or NULL */,
+                           float* tangent_out /* [batch, K, dim] */, void* hip_stream);
 
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
