@@ -94,6 +94,8 @@ PAIR_SELECT_KERNEL_BASE = 0x20000                           # FF_PAIR_SELECT_KER
 PUSH_KERNEL_BASE = 0x40000                                  # FF_PUSH_KERNEL_BASE
 STATUS_NOISE_ROW = 4                                        # FF_STATUS_NOISE_ROW
 MAX_PUSH_TANGENTS = 15                                      # tangent columns beside the value column of a 16-column tile
+PULL_KERNEL_BASE = 0x50000                                  # FF_PULL_KERNEL_BASE
+MAX_PULL_COTANGENTS = 15                                    # cotangent columns beside the value column of a 16-column tile
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -257,6 +259,19 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_ode_launch_push.restype = ctypes.c_int
     L.ff_mlp_ode_launch_push.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]
+    L.ff_pull_kernel_count.restype = ctypes.c_int
+    L.ff_pull_kernel_name.restype = ctypes.c_char_p
+    L.ff_pull_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_pull_plan.restype = ctypes.c_int
+    L.ff_mlp_pull_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
+                                   ctypes.c_int, ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pull_wpack_floats.restype = ctypes.c_size_t
+    L.ff_mlp_pull_wpack_floats.argtypes = [ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pull_wpack.restype = ctypes.c_int
+    L.ff_mlp_pull_wpack.argtypes = L.ff_mlp_wpack.argtypes
+    L.ff_mlp_ode_launch_pull.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_pull.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]
     L.ff_mlp_samples_per_workgroup.restype = ctypes.c_int
     L.ff_mlp_samples_per_workgroup.argtypes = [ctypes.POINTER(PlanStruct), ctypes.c_int]
     L.ff_last_hip_error.restype = ctypes.c_int
@@ -362,18 +377,21 @@ def make_plan(dim: int, cond_dim: int, hidden: List[int], mode: int,
 
 def pack_weights(plan: PlanStruct, weights: List[torch.Tensor], biases: List[Optional[torch.Tensor]],
                  hidden: List[int], x_col0: int, c_col0: int) -> torch.Tensor:
-    """ff_mlp_wpack on host copies of the nn.Linear parameters; returns the packed CPU tensor."""
+    """ff_mlp_wpack on host copies of the nn.Linear parameters; returns the packed CPU tensor.  A pull plan
+    (``make_pull_plan``): ff_mlp_pull_wpack, the forward network's pack followed by the transposed network's."""
     L = lib()
-    n = L.ff_mlp_wpack_floats(ctypes.byref(plan))
+    pull = is_pull_plan(plan)
+    n = (L.ff_mlp_pull_wpack_floats if pull else L.ff_mlp_wpack_floats)(ctypes.byref(plan))
     out = torch.empty(n, dtype=torch.float32)
     ws = [f32_on(w, "cpu") for w in weights]
     bs = [f32_on(b, "cpu") for b in biases]
     wp = (ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
     bp = (ctypes.c_void_p * len(bs))(*[0 if b is None else b.data_ptr() for b in bs])
     hw = (ctypes.c_int * len(hidden))(*hidden)
-    rc = L.ff_mlp_wpack(ctypes.byref(plan), wp, bp, hw, int(ws[0].shape[1]), x_col0, c_col0, out.data_ptr())
+    rc = (L.ff_mlp_pull_wpack if pull else L.ff_mlp_wpack)(ctypes.byref(plan), wp, bp, hw, int(ws[0].shape[1]), x_col0, c_col0,
+                                                           out.data_ptr())
     if rc != FF_OK:
-        raise _err(rc, "ff_mlp_wpack")
+        raise _err(rc, "ff_mlp_pull_wpack" if pull else "ff_mlp_wpack")
     return out
 
 
@@ -427,7 +445,32 @@ def make_push_plan(dim: int, cond_dim: int, hidden: List[int], act: Tuple[int, f
 
 
 def is_push_plan(plan: PlanStruct) -> bool:
-    return int(plan.kernel_id) >= PUSH_KERNEL_BASE
+    return PUSH_KERNEL_BASE <= int(plan.kernel_id) < PULL_KERNEL_BASE
+
+
+PULL_ENVELOPE = ("the pull-back kernels (flow_vjp) hold SiLU networks in f32 with hidden widths up to 256, up to 32 state "
+                 "dimensions and up to 16 conditional inputs, up to 15 cotangents per sample, and as many hidden layers as "
+                 "leave the stash of their slopes inside 160 KiB of LDS: 18 at width 256 (17 beyond 16 dimensions), 36 at "
+                 "width 128")
+
+
+def make_pull_plan(dim: int, cond_dim: int, hidden: List[int], act: Tuple[int, float, float] = (ACT_SILU, 0.0, 0.0),
+                   precision: int = PREC_F32) -> PlanStruct:
+    """ff_mlp_pull_plan: the smallest pull-back unit that holds the network (NotImplementedError with the envelope if
+    none does, or if its depth overflows the stash)."""
+    p = PlanStruct()
+    arr = (ctypes.c_int * len(hidden))(*hidden)
+    rc = lib().ff_mlp_pull_plan(dim, cond_dim, len(hidden), arr, int(act[0]), int(precision), ctypes.byref(p))
+    if rc == FF_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"no gfx950 pull-back kernel for dim={dim}, cond_dim={cond_dim}, hidden={hidden}, "
+                                  f"activation={act[0]}: {PULL_ENVELOPE}")
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_pull_plan")
+    return p
+
+
+def is_pull_plan(plan: PlanStruct) -> bool:
+    return int(plan.kernel_id) >= PULL_KERNEL_BASE
 
 
 def row_width(plan: PlanStruct) -> int:
@@ -864,10 +907,11 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
     return _AuxPtrs(*range(t.data_ptr(), t.data_ptr() + t.shape[0] * step, step))
 
 
-def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, **fields) -> None:
-    """The one launch of the six ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
-    ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, or ff_mlp_ode_launch_push with
-    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``.  ``tensors``: the caller's
+def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, **fields) -> None:
+    """The one launch of the seven ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
+    ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, ff_mlp_ode_launch_push with
+    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, or ff_mlp_ode_launch_pull with
+    ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``.  ``tensors``: the caller's
     tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
     of what the op allocated itself.  A field named in neither stays zero."""
     a = OdeArgs(**fields)
@@ -876,7 +920,12 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             setattr(a, field, _chk(t, _ARG_NAMES[field], dev))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if push is not None:
+        if pull is not None:
+            what = "ff_mlp_ode_launch_pull"
+            rc = lib().ff_mlp_ode_launch_pull(ctypes.byref(p), ctypes.byref(a), _chk(pull[0], "cotangents", dev),
+                                              _chk(pull[1], "cot_x_out", dev), _chk(pull[2], "cot_cond_out", dev),
+                                              ctypes.c_void_p(stream))
+        elif push is not None:
             what = "ff_mlp_ode_launch_push"
             rc = lib().ff_mlp_ode_launch_push(ctypes.byref(p), ctypes.byref(a), _chk(push[0], "cond_tangents", dev),
                                               _chk(push[1], "tangent_out", dev), ctypes.c_void_p(stream))
@@ -1026,6 +1075,53 @@ def mlp_ode_push(x: torch.Tensor, cond: Optional[torch.Tensor], tangents: Option
 def _(x, cond, tangents, cond_tangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, unit, tangent_first,
       tangent_count):
     return (torch.empty_like(x), x.new_empty(x.shape[0], int(tangent_count), x.shape[1]),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_pull", mutates_args=())
+def mlp_ode_pull(x: torch.Tensor, cond: Optional[torch.Tensor], cotangents: torch.Tensor, wpack: torch.Tensor, etab: torch.Tensor,
+                 in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor],
+                 out_shift: Optional[torch.Tensor], plan: List[int], want_cond: bool
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused continuous-adjoint solve (ff_mlp_ode_launch_pull) over the rows ``etab`` of the REVERSED span, from
+    ``x`` = the forward solve's result: returns (retraced state [B, D], cot_x [B, K, D], cot_cond [B, K, C] -- [B, K, 0]
+    unless ``want_cond`` --, status [1]) with ``cot_x[b, k] = cotangents[b, k]^T d x[b] / d (retraced state[b])`` and
+    ``cot_cond[b, k]`` likewise for ``cond[b]``.  ``wpack``: the pull plan's two packs (``pack_weights``)."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_pull needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    B, D = x.shape
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    if cotangents.dim() != 3 or cotangents.shape[0] != B or cotangents.shape[2] != D or cotangents.shape[1] < 1:
+        raise RuntimeError(f"cotangents has shape {tuple(cotangents.shape)}, expected [{B}, K >= 1, {D}]")
+    K = int(cotangents.shape[1])
+    C = int(p.cond_dim) if want_cond else 0
+    if want_cond and p.cond_dim == 0:
+        raise RuntimeError("want_cond on a plan without conditional inputs")
+    x_out = torch.empty_like(x)
+    gx = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+    gc = torch.empty(B, K, C, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, gx, gc, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                pull=(cotangents, gx, gc if want_cond else None), x_out=x_out.data_ptr(), status=status.data_ptr(), batch=B,
+                n_evals=etab.shape[0], mode=MODE_HUTCH, tangent_count=K, stage_slots=_slots_hint(plan))
+    return x_out, gx, gc, status
+
+
+@mlp_ode_pull.register_fake
+def _(x, cond, cotangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, want_cond):
+    B, K = x.shape[0], cotangents.shape[1]
+    C = _plan_from_words(plan).cond_dim if want_cond else 0
+    return (torch.empty_like(x), x.new_empty(B, K, x.shape[1]), x.new_empty(B, K, C),
             torch.empty(1, dtype=torch.int32, device=x.device))
 
 

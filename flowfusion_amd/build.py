@@ -134,6 +134,22 @@ def _push_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_push_m{tile}_h{h}_d{d}_c{c}_w{wps}"
 
 
+# Pull-back units (ff_mlp_pull.hpp; ff_mlp_pull_plan): the continuous adjoint of a fixed-grid solve on cotangent columns --
+# flow_vjp.  (TILE, H, DREGS, CREGS, WPS, RING): the three push-forward shapes, SiLU, fp32.  ONE wavefront per workgroup (the
+# slope stash of a tile takes up to 32 KiB of LDS at 4 x 256, four tiles do not share 64 KiB), so WPS is 1 and the occupancy is
+# what the stash and the registers leave.  A family of its own (g_pull_kernels, FF_PULL_KERNEL_BASE): not in the ff_kernel_count /
+# ff_kernel_name table, no twins, no wide, split-precision or run-time-activation units; the test variants carry none.
+PULL_INSTANCES = [
+    (16, 128, 4, 4, 1, 4),
+    (16, 256, 4, 4, 1, 8),
+    (16, 256, 8, 4, 1, 8),
+]
+
+
+def _pull_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_pull_m{tile}_h{h}_d{d}_c{c}"
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -197,11 +213,12 @@ def _inst_name(tile, h, d, c, t, wps, ring, act) -> str:
     return f"mlp_ode_m{tile}_h{h}_d{d}_c{c}_t{t}" + (f"_w{wps}" if (wps != 1 and act == 0) else "") + (f"_a{act}" if act else "")
 
 
-def _launcher_unit(name: str, header: str, kernel_expr: str) -> str:
-    """One translation unit: the instantiation `kernel_expr` behind `int launch_<name>(args, grid, lds, stream)`."""
+def _launcher_unit(name: str, header: str, kernel_expr: str, block: int = 256, registry: str = "ff_registry.h") -> str:
+    """One translation unit: the instantiation `kernel_expr` behind `int launch_<name>(args, grid, lds, stream)`, launched
+    with `block` threads per workgroup."""
     return f"""// generated by flowfusion_amd/build.py -- do not edit
 #include <atomic>
-#include "ff_registry.h"
+#include "{registry}"
 #include "{header}"
 namespace ff {{
 int launch_{name}(const KernelArgs* a, unsigned grid, unsigned lds, hipStream_t s)
@@ -218,7 +235,7 @@ int launch_{name}(const KernelArgs* a, unsigned grid, unsigned lds, hipStream_t 
         if (dev >= 0 && dev < kMaxDevices) ready[dev].store(1, std::memory_order_release);
     }}
     void* params[] = {{(void*)a}};
-    return (int)hipLaunchKernel((const void*)kern, dim3(grid), dim3(256), params, lds, s);
+    return (int)hipLaunchKernel((const void*)kern, dim3(grid), dim3({block}), params, lds, s);
 }}
 }}
 """
@@ -230,7 +247,7 @@ def _write(path: Path, text: str) -> Path:
     return path
 
 
-def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None, select=None, push=None) -> list[Path]:
+def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None, pair=None, select=None, push=None, pull=None) -> list[Path]:
     """The translation units of a library: the product's (default arguments) or a test variant's instance lists."""
     GEN = gen if gen is not None else globals()["GEN"]
     INSTANCES = instances if instances is not None else globals()["INSTANCES"]
@@ -239,6 +256,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     PAIR_INSTANCES = pair if pair is not None else globals()["PAIR_INSTANCES"]
     SELECT = select if select is not None else globals()["PAIR_SELECT_INSTANCES"]       # (a subset of PAIR_INSTANCES)
     PUSH_INSTANCES = push if push is not None else globals()["PUSH_INSTANCES"]
+    PULL_INSTANCES = pull if pull is not None else globals()["PULL_INSTANCES"]
     GEN.mkdir(parents=True, exist_ok=True)
     tf = lambda t: "true" if t else "false"
     # every launcher of the library: (name, header, kernel expression) -> a translation unit, a declaration, a table cell
@@ -266,6 +284,10 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
         units.append((_push_name(tile, h, d, c, wps, ring), "ff_mlp_ode.hpp",
                       f"mlp_ode_kernel<{tile}, {h}, {d}, {c}, true, {wps}, {ring}, 0, false, false, true>"))
     files = [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr)) for name, header, expr in units]
+    # the pull-back units: one wavefront per workgroup, a registry header of their own
+    pulls = [(_pull_name(*i), "ff_mlp_pull.hpp", f"mlp_pull_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
+    files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_pull_registry.h")) for name, header, expr in pulls]
+    units = units + pulls
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
     fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
@@ -295,8 +317,12 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     push_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_push_name(*i)}, "{_push_name(*i)}"}}' for i in PUSH_INSTANCES
     ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (the test variants carry no push kernels)
+    pull_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pull_name(*i)}, "{_pull_name(*i)}"}}' for i in PULL_INSTANCES
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor pull kernels)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
+#include "ff_pull_registry.h"
 namespace ff {{
 {decls}
 const KernelEntry g_kernels[] = {{
@@ -315,6 +341,10 @@ const PushKernelEntry g_push_kernels[] = {{
 {push_rows}
 }};
 const int g_n_push_kernels = {len(PUSH_INSTANCES)};
+const PullKernelEntry g_pull_kernels[] = {{
+{pull_rows}
+}};
+const int g_n_pull_kernels = {len(PULL_INSTANCES)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -344,6 +374,8 @@ def _cost(src: Path) -> float:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
     if n.startswith("mlp_push_"):
         return 16 if "_h256_" in n else 6
+    if n.startswith("mlp_pull_"):
+        return 40 if "_h256_" in n else 15
     if n.startswith("mlp_pairsel_"):
         return (7 if "_h256_" in n else 3) if "_coop" in n else (16 if "_h256_" in n else 7)
     if n.startswith("mlp_pair_"):
@@ -430,7 +462,7 @@ def build(verbose: bool = False, jobs: int | None = None, variants: bool = True)
         for name, v in VARIANTS.items():
             gen, obj = PKG / "_build" / f"gen_{name}", PKG / "_build" / f"obj_{name}"
             obj.mkdir(parents=True, exist_ok=True)
-            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"], select=v.get("select", []), push=[])
+            vs = _gen_sources(gen, v["instances"], v["wide"], v["split"], pair=v["pair"], select=v.get("select", []), push=[], pull=[])
             extra[name] = (vs, obj, tuple(v["defines"]))
             units += [(s, obj, tuple(v["defines"])) for s in vs]
     jobs = jobs or min(8, os.cpu_count() or 1)

@@ -7,6 +7,7 @@
 #include "ff_layout.h"
 #include "ff_split_layout.h"
 #include "ff_registry.h"
+#include "ff_pull_registry.h"
 #include "ff_adapt_logic.h"
 
 static_assert(FF_MAX_SLOTS == ff::kSlots, "slot count mismatch between header and kernel");
@@ -157,7 +158,7 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
 // ---- what a plan launches, as data ------------------------------------------------------------------------------------
 // describe() validates a plan once and says everything the code below needs to know about its family: the launcher,
 // ff_mlp_launch_kind and the small queries read the description and never ask which family they serve.
-enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush };
+enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush, kPull };
 
 struct LaunchDesc {
     PlanFamily family;
@@ -225,6 +226,18 @@ static bool describe(const ff_mlp_plan_t* p, LaunchDesc* d)
         d->max_aux = FF_MAX_AUX; d->takes_k1 = true; d->empty_batch_first = true;
         return true;
     }
+    if (p->kernel_id >= FF_PULL_KERNEL_BASE) {
+        // pull-back units (ff_mlp_pull.hpp): a wavefront per workgroup and per tile, whole fixed-grid solves only; the packed
+        // weights are the forward network's and the transposed network's (pull_layout), back to back
+        const int index = p->kernel_id - FF_PULL_KERNEL_BASE;
+        if (index >= ff::g_n_pull_kernels) return false;
+        const ff::PullKernelEntry& k = ff::g_pull_kernels[index];
+        if (!k.launch || !shape_ok(p, k.tile, k.H, k.dregs, k.cregs) || p->activation != FF_ACT_SILU) return false;
+        d->family = kPull; d->name = k.name; d->one_wave = k.launch;
+        twin_line(d, k.wps);
+        d->tangents = 1; d->nets = 1; d->row_nets = 1; d->exchange = 2;
+        return true;
+    }
     if (p->kernel_id >= FF_PUSH_KERNEL_BASE) {
         // push-forward units: the Hutchinson kernels' shapes with the tangent columns integrated; one wavefront per tile, whole
         // fixed-grid solves only (no first stage from the caller, no auxiliary outputs)
@@ -258,6 +271,22 @@ static ff::Layout plan_layout(const ff_mlp_plan_t* p)
     return ff::make_layout(p->tile, p->width, p->dregs, p->cregs, p->n_hidden);
 }
 
+// The transposed network of a pull plan (ff_mlp_pull.hpp, net B): an ordinary network whose state registers are the forward
+// network's state AND conditional registers, without conditional inputs of its own.
+static ff::Layout pull_layout(const ff_mlp_plan_t* p)
+{
+    return ff::make_layout(p->tile, p->width, p->dregs + p->cregs, 0, p->n_hidden);
+}
+
+// Dynamic LDS of one pull tile with K cotangent columns per sample: `slots` stage slots (dregs + cregs words per slot and
+// lane), then the slope stash, n_hidden x width words for each of its tile / (1 + K) samples.
+static size_t pull_lds_bytes(const ff_mlp_plan_t* p, int K, int n_slots = ff::kSlots)
+{
+    const size_t slots = (size_t)n_slots * ((p->dregs + p->cregs) / 4) * 64 * 16;
+    return slots + (size_t)(p->tile / (1 + K)) * p->n_hidden * p->width * 4;
+}
+constexpr size_t kPullLdsLimit = 160u * 1024u;      // LDS of a compute unit = the most a workgroup can ask for
+
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
@@ -269,7 +298,7 @@ namespace ff {
 bool plan_steps_adaptively(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
-    return describe(plan, &d) && d.family != kSelect && d.family != kPush;
+    return describe(plan, &d) && d.family != kSelect && d.family != kPush && d.family != kPull;
 }
 }
 
@@ -312,6 +341,39 @@ extern "C" int ff_mlp_push_plan(int dim, int cond_dim, int n_hidden, const int* 
     return fill_plan(plan, dim, cond_dim, n_hidden, k.H, k.dregs, k.cregs, FF_PUSH_KERNEL_BASE + best, k.tile, FF_ACT_SILU);
 }
 
+extern "C" int ff_pull_kernel_count(void) { return ff::g_n_pull_kernels; }
+
+extern "C" const char* ff_pull_kernel_name(int index)
+{
+    return index >= 0 && index < ff::g_n_pull_kernels ? ff::g_pull_kernels[index].name : NULL;
+}
+
+// the smallest pull-back unit that holds the network (best_entry's preference), SiLU, fp32 -- and whose slope stash fits the
+// LDS at its largest, one cotangent per sample
+extern "C" int ff_mlp_pull_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, int activation, int precision,
+                                ff_mlp_plan_t* plan)
+{
+    if (!plan || !hidden_widths || dim < 1 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
+    if (activation < 0 || activation >= FF_ACT_COUNT) return FF_ERR_BADARG;
+    if (precision != FF_PREC_F32 && precision != FF_PREC_BF16X3 && precision != FF_PREC_BF16X2) return FF_ERR_BADARG;
+    const int wmax = widest(n_hidden, hidden_widths);
+    if (wmax < 0) return FF_ERR_BADARG;
+    if (activation != FF_ACT_SILU || precision != FF_PREC_F32) return FF_ERR_UNSUPPORTED;
+    const int best = best_entry(ff::g_pull_kernels, ff::g_n_pull_kernels, dim, cond_dim, wmax,
+                                [](const ff::PullKernelEntry& k) { return k.launch != nullptr; });
+    if (best < 0) return FF_ERR_UNSUPPORTED;
+    const ff::PullKernelEntry& k = ff::g_pull_kernels[best];
+    fill_plan(plan, dim, cond_dim, n_hidden, k.H, k.dregs, k.cregs, FF_PULL_KERNEL_BASE + best, k.tile, FF_ACT_SILU);
+    if (pull_lds_bytes(plan, 1) > kPullLdsLimit) { memset(plan, 0, sizeof(*plan)); return FF_ERR_UNSUPPORTED; }
+    return FF_OK;
+}
+
+extern "C" size_t ff_mlp_pull_wpack_floats(const ff_mlp_plan_t* plan)
+{
+    LaunchDesc d;
+    return describe(plan, &d) && d.family == kPull ? plan_layout(plan).total_floats + pull_layout(plan).total_floats : 0;
+}
+
 extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
 {
     const int rc = ff_mlp_pair_plan(dim, cond_dim, n_hidden, hidden_widths, plan);      // one envelope, one preference
@@ -344,6 +406,7 @@ extern "C" size_t ff_mlp_wpack_floats(const ff_mlp_plan_t* plan)
     LaunchDesc d;
     if (!describe(plan, &d)) return 0;
     if (d.family == kSplit) return ff::split::total_words(plan->n_hidden, split_parts(plan->precision), plan->dregs / 8, plan->width);
+    if (d.family == kPull) return 0;                     // (two packs: ff_mlp_pull_wpack_floats)
     return d.nets == 1 ? plan_layout(plan).total_floats : 0;
 }
 
@@ -447,7 +510,7 @@ extern "C" int ff_mlp_wpack(const ff_mlp_plan_t* plan, const float* const* W, co
                             const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out)
 {
     LaunchDesc d;
-    if (!describe(plan, &d) || d.nets == 2) return FF_ERR_BADARG;
+    if (!describe(plan, &d) || d.nets == 2 || d.family == kPull) return FF_ERR_BADARG;
     if (d.family == kSplit) {
         if (!W || !b || !hidden_widths || !out) return FF_ERR_BADARG;
         const int D = plan->dim, C = plan->cond_dim, NH = plan->n_hidden;
@@ -526,6 +589,78 @@ static int wpack_f32(const ff::Layout& L, int D, int C, const float* const* W, c
     return FF_OK;
 }
 
+// Pull packing (ff_mlp_pull.hpp): the forward network as ff_mlp_wpack packs it, then the transposed network as an ordinary
+// network of pull_layout -- first layer W_out^T (D -> h_L), hidden layers W_L^T .. W_2^T, output layer the x and c columns of
+// W_1 as rows -- with zero biases.  Its "state" is the combined feature space of the forward network's first-layer registers:
+// feature F sits on register R, lane group q with feat_of_reg(R, q) == F; R < dregs is state dimension F, R >= dregs the
+// conditional input feat_of_reg(R - dregs, q).
+extern "C" int ff_mlp_pull_wpack(const ff_mlp_plan_t* plan, const float* const* W, const float* const* b, const int* hidden_widths,
+                                 int in_features0, int x_col0, int c_col0, float* out)
+{
+    LaunchDesc d;
+    if (!describe(plan, &d) || d.family != kPull || !W || !b || !hidden_widths || !out) return FF_ERR_BADARG;
+    const int D = plan->dim, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
+    if (x_col0 < 0 || x_col0 + D > in_features0) return FF_ERR_BADARG;
+    if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
+    for (int i = 0; i < NH; ++i)
+        if (hidden_widths[i] < 1 || hidden_widths[i] > H) return FF_ERR_BADARG;
+    for (int i = 0; i <= NH; ++i)
+        if (!W[i] || (i > 0 && !b[i])) return FF_ERR_BADARG;
+    const ff::Layout L = plan_layout(plan), LT = pull_layout(plan);
+    int rc = wpack_f32(L, D, C, W, b, hidden_widths, in_features0, x_col0, c_col0, out);
+    if (rc != FF_OK) return rc;
+    const int NQ = ff::tile_nq(plan->tile), K1 = plan->dregs + plan->cregs, FB = NQ * K1;      // combined features
+    const int h0 = hidden_widths[0], hl = hidden_widths[NH - 1];
+    // combined feature -> column of W_1 (>= 0), and -> row of W_out (>= 0), or -1
+    int* const col1 = (int*)malloc((size_t)FB * sizeof(int));
+    int* const rowo = (int*)malloc((size_t)FB * sizeof(int));
+    float* const wf = (float*)calloc((size_t)hl * FB, sizeof(float));              // first layer  [h_L x FB] = W_out^T
+    float* const wl = (float*)calloc((size_t)FB * h0, sizeof(float));              // output layer [FB x h_1] = W_1^T
+    float* const zb = (float*)calloc((size_t)(H > FB ? H : FB), sizeof(float));    // zero biases
+    float* const wt = (float*)calloc((size_t)(NH > 1 ? NH - 1 : 1) * H * H, sizeof(float));      // hidden layers, transposed
+    const float** const Wl = (const float**)calloc((size_t)NH + 1, sizeof(float*));
+    const float** const bl = (const float**)calloc((size_t)NH + 1, sizeof(float*));
+    int* const hw = (int*)calloc((size_t)NH, sizeof(int));
+    rc = (col1 && rowo && wf && wl && zb && wt && Wl && bl && hw) ? FF_OK : FF_ERR_BADARG;
+    if (rc == FF_OK) {
+        for (int F = 0; F < FB; ++F) col1[F] = rowo[F] = -1;
+        for (int R = 0; R < K1; ++R)
+            for (int q = 0; q < NQ; ++q) {
+                const int F = ff::feat_of_reg(plan->tile, R, q);
+                if (F < 0 || F >= FB) { rc = FF_ERR_BADARG; continue; }
+                if (R < plan->dregs) {
+                    if (F < D) { col1[F] = x_col0 + F; rowo[F] = F; }
+                } else {
+                    const int c = ff::feat_of_reg(plan->tile, R - plan->dregs, q);
+                    if (c < C) col1[F] = c_col0 + c;
+                }
+            }
+    }
+    if (rc == FF_OK) {
+        for (int F = 0; F < FB; ++F) {
+            if (rowo[F] >= 0)
+                for (int k = 0; k < hl; ++k) wf[(size_t)k * FB + F] = W[NH][(size_t)rowo[F] * hl + k];
+            if (col1[F] >= 0)
+                for (int k = 0; k < h0; ++k) wl[(size_t)F * h0 + k] = W[0][(size_t)k * in_features0 + col1[F]];
+        }
+        // transposed hidden layer j = 1 .. NH - 1 is W[NH - j]^T: hidden_widths[NH - j] -> hidden_widths[NH - j - 1]
+        for (int j = 0; j < NH; ++j) hw[j] = hidden_widths[NH - 1 - j];
+        Wl[0] = wf; bl[0] = nullptr;
+        for (int j = 1; j < NH; ++j) {
+            const float* const src = W[NH - j];
+            const int win = hidden_widths[NH - j], wout = hidden_widths[NH - j - 1];      // of the TRANSPOSED layer
+            float* const dst = wt + (size_t)(j - 1) * H * H;
+            for (int r = 0; r < wout; ++r)
+                for (int k = 0; k < win; ++k) dst[(size_t)r * win + k] = src[(size_t)k * wout + r];
+            Wl[j] = dst; bl[j] = zb;
+        }
+        Wl[NH] = wl; bl[NH] = zb;
+        rc = wpack_f32(LT, FB, 0, Wl, bl, hw, FB, 0, 0, out + L.total_floats);
+    }
+    free(col1); free(rowo); free(wf); free(wl); free(zb); free(wt); free(Wl); free(bl); free(hw);
+    return rc;
+}
+
 // Pair packing: each reference network becomes an ordinary network over the whole state [q | p] (its first layer reads
 // its own half -- p for mlp_q, q for mlp_p -- and has zero columns on the other; its output layer writes its own half,
 // negated for mlp_p, and zero rows on the other), packed by wpack_f32; net A's pack, then net B's.
@@ -591,6 +726,7 @@ extern "C" int ff_mlp_samples_per_workgroup(const ff_mlp_plan_t* plan, int mode)
     int nt, unit;
     int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
     if (rc) return rc;
+    if (d.family == kPull) return plan->tile / (1 + nt);      // a tile per workgroup
     return (d.one_wave ? 4 : 1) * (plan->tile / (1 + nt));      // (the wide catch-all: a tile per workgroup)
 }
 
@@ -736,6 +872,15 @@ extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int3
 static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArgs ka, long long spt, bool jac_out, hipStream_t stream)
 {
     const long long batch = ka.batch;
+    if (d.family == kPull) {
+        // a wavefront per workgroup and per tile; LDS = stage slots + the slope stash of the tile's samples
+        const long long tiles = (batch + spt - 1) / spt;
+        const size_t lds = pull_lds_bytes(plan, ka.n_tangent, ka.tangent_first);
+        if (lds > kPullLdsLimit || tiles > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
+        const int herr = d.one_wave(&ka, (unsigned)tiles, (unsigned)lds, stream);
+        if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
+        return FF_OK;
+    }
     const LaunchChoice ch = choose_launch(d, (batch + spt - 1) / spt, jac_out);
     const bool coop = ch.coop;
     const long long main_tiles = ch.main_tiles, tail_tiles = ch.tail_tiles;
@@ -786,11 +931,31 @@ struct PushIo {
     float* tangent_out;
 };
 
-// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes and ff_mlp_ode_launch_push: one argument check, one launch path
-static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr)
+// What ff_mlp_ode_launch_pull adds to a launch (NULL: not a pull launch).
+struct PullIo {
+    const float* cotangent_in;
+    float* cot_x_out;
+    float* cot_cond_out;
+};
+
+// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push and ff_mlp_ode_launch_pull: one
+// argument check, one launch path
+static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr,
+                      const PullIo* pull = nullptr)
 {
     LaunchDesc d;
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
+    if (pull && d.family == kSplit) return FF_ERR_UNSUPPORTED;
+    if ((d.family == kPull) != (pull != nullptr)) return FF_ERR_BADARG;      // pull plans launch through their own entry, and only they
+    if (pull) {
+        // whole fixed-grid adjoint solves: K cotangents as given, nothing of the divergence side, no attempt launches, no noise
+        if (!pull->cotangent_in || !pull->cot_x_out || a->mode != FF_MODE_HUTCH) return FF_ERR_BADARG;
+        if (a->tangent_count < 1 || a->tangent_count + 1 > plan->tile) return FF_ERR_BADARG;
+        if (a->probe || a->dlogp_out || a->k1_in || a->kl1_in || a->dlogp_in || a->jac_out || a->n_aux > 0 || a->noise) return FF_ERR_BADARG;
+        if (pull->cot_cond_out && plan->cond_dim == 0) return FF_ERR_BADARG;
+        const int ns = a->stage_slots > 0 && a->stage_slots <= FF_MAX_SLOTS ? a->stage_slots : FF_MAX_SLOTS;
+        if (pull_lds_bytes(plan, a->tangent_count, ns) > kPullLdsLimit) return FF_ERR_UNSUPPORTED;      // the stash does not fit
+    }
     if (push && d.family == kSplit) return FF_ERR_UNSUPPORTED;
     if ((d.family == kPush) != (push != nullptr)) return FF_ERR_BADARG;      // push plans launch through their own entry, and only they
     if (push) {
@@ -822,14 +987,14 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
         else if (span > nt) return FF_ERR_BADARG;           // must be split by the caller
         if (tfirst < 0 || tfirst + nt > span || nt + 1 > plan->tile) return FF_ERR_BADARG;
     }
-    if (a->mode == FF_MODE_HUTCH && a->tangent_count > 1) {      // K probes per sample: probe is [batch, K, dim]
+    if (a->mode == FF_MODE_HUTCH && a->tangent_count > 1) {      // K probes (tangents, cotangents) per sample: [batch, K, dim]
         nt = a->tangent_count;
         if (nt + 1 > plan->tile) return FF_ERR_BADARG;
     }
     // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
     if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;
-    if (a->mode == FF_MODE_HUTCH && !a->probe && !push) return FF_ERR_BADARG;      // (push: no state tangents = zero)
-    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull) return FF_ERR_BADARG;      // (push: no state tangents = zero)
+    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull) return FF_ERR_BADARG;
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->batch == 0 && d.empty_batch_first) return FF_OK;
     if (a->n_aux < 0 || a->n_aux > d.max_aux || (a->k1_in && !d.takes_k1)) return FF_ERR_BADARG;
@@ -839,12 +1004,17 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
 
     ff::KernelArgs ka = fill_args(plan, a, !d.state_only, nt, unit, tfirst);
     ka.etab_stride = FF_ROW_HDR + d.row_nets * plan->width;
-    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats;
+    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull ? pull_layout(plan).total_floats : 0);
     if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
     ka.dlogp_probe_out = probe_out;
     if (push) { ka.cond_tangent = push->cond_tangent; ka.tangent_out = push->tangent_out; }
+    // (a pull launch takes none of the three, so they carry its own pointers: ff_mlp_pull.hpp)
+    if (pull) {
+        ka.probe = pull->cotangent_in; ka.dlogp_out = pull->cot_x_out; ka.jac_out = pull->cot_cond_out;
+        ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;      // the stage slots the kernel keeps in LDS
+    }
     return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
 }
 
@@ -863,6 +1033,13 @@ extern "C" int ff_mlp_ode_launch_push(const ff_mlp_plan_t* plan, const ff_ode_ar
 {
     const PushIo io = {cond_tangent, tangent_out};
     return launch_ode(plan, a, nullptr, hip_stream, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_pull(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* cotangent_in, float* cot_x_out,
+                                      float* cot_cond_out, void* hip_stream)
+{
+    const PullIo io = {cotangent_in, cot_x_out, cot_cond_out};
+    return launch_ode(plan, a, nullptr, hip_stream, nullptr, &io);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

@@ -611,6 +611,31 @@ class ScoreModel(nn.Module):
         in ceil((D + C) / 15) launches (``x_out`` is the first launch's)."""
         return self._flow_jacobian(x, conditional, direction, method, options)
 
+    @torch.no_grad()
+    def flow_vjp(self, x, cotangents, conditional=None, *, direction="to_data", method="rk4", options=None,
+                 return_retrace=False):
+        """Extension: K cotangents pulled back through the probability-flow solve of ``flow_jvp``, reverse mode: returns
+        ``(x_out [B, D], gx [B, K, D], gc [B, K, C] or None)`` -- plus ``retrace [B]`` with ``return_retrace`` -- with
+        ``gx[b, k] = cotangents[b, k]^T d x_out[b] / d x[b]`` and ``gc`` likewise for ``conditional``; ``cotangents`` is
+        [B, K, D], K <= 15; ``x_out`` is bitwise the fixed-grid state-only solve (for a VE model ``to_data`` starts from
+        ``x * sigma_max``, and ``gx`` carries the factor).
+
+        It integrates the CONTINUOUS adjoint over the reversed grid, as the reference's ``odeint_adjoint`` does -- not the
+        transpose of the discrete map ``flow_jvp`` differentiates.  The two differ by the discretisation error, and the
+        backward sweep retraces the state instead of storing it.  A score model's Fourier time features (sigma = 16) are
+        under-resolved below about 100 steps: use rk4 or better, read ``retrace[b] = max_d |y_back - x|``, and raise the step
+        count until it is small.  (Measured in float64 on a VP model: gap to ``w^T flow_jacobian`` 4e-4 with 32 rk4 steps,
+        4e-6 with 128; with 128 EULER steps ``to_base`` the gap is 0.7 and the retrace 0.4.)
+
+        No parameter gradients, no torch.autograd integration, no adaptive step control, no exact discrete adjoint: see
+        ``odeint.solve_pull``."""
+        return self._flow_vjp(x, cotangents, conditional, direction, method, options, return_retrace)
+
+    def _flow_vjp(self, x, cotangents, conditional, direction, method, options, return_retrace, **maps):
+        t_span, gain = self._push_args(x, direction)
+        return odeint.solve_pull(self, x, t_span, method, options, cotangents, cond=conditional, tangent_gain=gain,
+                                 return_retrace=return_retrace, **maps)
+
     def _flow_jacobian(self, x, conditional, direction, method, options, **maps):
         t_span, gain = self._push_args(x, direction)
         return odeint.solve_push_jacobian(self, x, t_span, method, options, cond=conditional, tangent_gain=gain, **maps)
@@ -843,6 +868,13 @@ class _PopulationModel(nn.Module):
         return self.score_model._flow_jacobian(x, cond, direction, method, options, **maps)
 
     @torch.no_grad()
+    def _flow_vjp(self, x, cotangents, conditional, direction, method, options, return_retrace):
+        """``flow_vjp`` of the two wrappers: ``ScoreModel.flow_vjp`` of the inner score model between the wrappers' affine
+        maps, so that ``x``, ``x_out``, ``conditional`` and every cotangent are in the user's units."""
+        cond, maps = self._push_maps(conditional, direction)
+        return self.score_model._flow_vjp(x, cotangents, cond, direction, method, options, return_retrace, **maps)
+
+    @torch.no_grad()
     def _log_prob_noisy(self, x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
                         return_ess, num_probes):
         """``log_prob_noisy`` of the two wrappers: ``ScoreModel.log_prob_noisy`` around this wrapper's own ``log_prob`` --
@@ -901,6 +933,12 @@ class PopulationModelDiffusion(_PopulationModel):
         """Extension: ``ScoreModel.flow_jacobian`` in the units of this wrapper: ``(x_out [B, D], J_x [B, D, D], None)``."""
         return self._flow_jacobian(x, None, direction, method, options)
 
+    def flow_vjp(self, x, cotangents, *, direction="to_data", method="rk4", options=None, return_retrace=False):
+        """Extension: ``ScoreModel.flow_vjp`` in the units of this wrapper: ``(x_out [B, D], gx [B, K, D], None)`` (and
+        ``retrace [B]``), ``gx[b, k] = cotangents[b, k]^T d x_out[b] / d x[b]`` -- the continuous adjoint: use rk4 or
+        better, read ``retrace``, raise the step count (``options={"step_size": h}``; the default grid is ONE step)."""
+        return self._flow_vjp(x, cotangents, None, direction, method, options, return_retrace)
+
     def log_prob_noisy(self, x, noise_std, num_draws=16, atol=1e-5, rtol=1e-5, *, seed=None, sample_offset=0,
                        chunk_points=None, return_ess=False, num_probes=1):
         """Extension: ``log_prob`` of observations ``x`` measured with Gaussian errors ``noise_std`` (in the units of ``x``),
@@ -957,6 +995,14 @@ class PopulationModelDiffusionConditional(_PopulationModel):
         """Extension: ``ScoreModel.flow_jacobian`` in the units of this wrapper: ``(x_out [B, D], J_x [B, D, D],
         J_c [B, D, C])``, ``J_c`` with respect to the RAW conditional."""
         return self._flow_jacobian(x, conditional, direction, method, options)
+
+    def flow_vjp(self, x, cotangents, conditional=None, *, direction="to_data", method="rk4", options=None,
+                 return_retrace=False):
+        """Extension: ``ScoreModel.flow_vjp`` in the units of this wrapper: ``(x_out [B, D], gx [B, K, D], gc [B, K, C])``
+        (and ``retrace [B]``), ``gc`` with respect to the RAW conditional (the population hyper-parameters) -- the
+        continuous adjoint: use rk4 or better, read ``retrace``, raise the step count (``options={"step_size": h}``; the
+        default grid is ONE step)."""
+        return self._flow_vjp(x, cotangents, conditional, direction, method, options, return_retrace)
 
     def log_prob_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-5, rtol=1e-5, *, seed=None,
                        sample_offset=0, chunk_points=None, return_ess=False, num_probes=1):

@@ -227,6 +227,28 @@ class _FlowBase(nn.Module):
         t_span, kw = self._push_args(x, conditional, direction)
         return odeint.solve_push_jacobian(self, x, t_span, method, options, **kw)
 
+    @torch.no_grad()
+    def flow_vjp(self, x, cotangents, conditional=None, *, direction="to_data", method="rk4", options=None,
+                 return_retrace=False):
+        """Extension: K cotangents pulled back through the solve of ``sample`` (``direction="to_data"``, ``x`` = base points)
+        or of ``log_prob`` (``"to_base"``, ``x`` = target-space points), reverse mode: returns ``(x_out [B, D], gx [B, K, D],
+        gc [B, K, C] or None)`` -- plus ``retrace [B]`` with ``return_retrace`` -- with ``gx[b, k] = cotangents[b, k]^T
+        d x_out[b] / d x[b]`` and ``gc`` likewise for the raw ``conditional``, in the units of ``x``, ``x_out`` and the raw
+        ``conditional`` (``flow_jvp``'s conventions).  ``cotangents`` is [B, K, D], K <= 15.  ``x_out`` is bitwise the
+        fixed-grid ``sample`` / forward solve.
+
+        It integrates the CONTINUOUS adjoint over the reversed grid, as the reference's ``odeint_adjoint`` does
+        (``sample(gradients=True)``, ``adjoint=True``) -- not the transpose of the discrete map ``flow_jvp``
+        differentiates.  The two differ by the discretisation error, and the backward sweep retraces the state instead of
+        storing it: use rk4 or better, read ``retrace[b] = max_d |y_back - x|`` (how far the retraced trajectory ended
+        from ``x``, in its units), and raise the step count until it is small.  (Measured in float64 on a small flow: gap to
+        ``w^T flow_jacobian`` 6e-11 with 16 rk4 steps, 9e-3 with 128 euler steps.)
+
+        No parameter gradients, no torch.autograd integration (the call runs under ``no_grad``), no adaptive step
+        control, no exact discrete adjoint: see ``odeint.solve_pull``."""
+        t_span, kw = self._push_args(x, conditional, direction)
+        return odeint.solve_pull(self, x, t_span, method, options, cotangents, return_retrace=return_retrace, **kw)
+
     # -- the public methods' bodies, written once (``conditional=None``: the unconditional flow) -----------------------------
     def compute_linear_velocity_field(self, x0, xT, t):
         x0 = (x0 - self.target_shift) / self.target_scale
@@ -236,7 +258,8 @@ class _FlowBase(nn.Module):
         if gradients:
             raise NotImplementedError("sample(gradients=True) uses odeint_adjoint in the reference "
                                       f"(flow.py:{'286-295' if conditional is None else '779-788'}); differentiable solves are "
-                                      "out of scope")
+                                      "out of scope (flow_vjp pulls cotangents back through a fixed-grid solve, for x and "
+                                      "the conditional; parameter gradients are not built)")
         cond, norm_only = self._cond_args(conditional)
         return self._fused_sample(xT, cond, method, options, atol, rtol, norm_only=norm_only)
 
@@ -244,7 +267,8 @@ class _FlowBase(nn.Module):
                            num_probes, return_stderr):
         """``(xT, log_jacobian [B,1], stderr [B,1] or None)`` of the normalised points ``x``."""
         if adjoint:
-            raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path")
+            raise NotImplementedError("adjoint=True (odeint_adjoint) is out of scope for the fused path (flow_vjp is the "
+                                      "continuous adjoint of a fixed-grid solve with respect to x and the conditional)")
         cond, norm_only = self._cond_args(conditional)
         return self._fused_forward(x, cond, method, options, hutchinson, atol, rtol, norm_only=norm_only,
                                    probe_rng=self._probe_rng(probe, seed, sample_offset, hutchinson), num_probes=num_probes,

@@ -146,7 +146,9 @@ class FusedNet:
         n_hidden) -- ff_layout.h make_layout -- and not of the kernel instantiation: the state-only and the
         divergence-capable kernels of one shape share a buffer."""
         vers = tuple((p.data_ptr(), p._version) for l in self.linears for p in (l.weight, l.bias))
-        return (str(device), plan.precision, plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden), vers
+        # (a pull plan's buffer holds the transposed network too: a key of its own)
+        return (str(device), plan.precision, plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden) + \
+            (("pull",) if _native.is_pull_plan(plan) else ()), vers
 
     def _pack(self, plan) -> torch.Tensor:
         return _native.pack_weights(plan, [l.weight for l in self.linears], [l.bias for l in self.linears],
@@ -158,6 +160,13 @@ class FusedNet:
             self._plans["push"] = _native.make_push_plan(self.dim, self.cond_dim, self.hidden, self.act,
                                                          _native.PRECISIONS[self.precision])
         return self._plans["push"]
+
+    def pull_plan(self) -> _native.PlanStruct:
+        """The pull-back unit of this network (ff_mlp_pull_plan); NotImplementedError with the envelope if none holds it."""
+        if "pull" not in self._plans:
+            self._plans["pull"] = _native.make_pull_plan(self.dim, self.cond_dim, self.hidden, self.act,
+                                                         _native.PRECISIONS[self.precision])
+        return self._plans["pull"]
 
     def wpack(self, device, mode: int, plan=None) -> torch.Tensor:
         plan = self.plan(mode) if plan is None else plan
@@ -261,6 +270,41 @@ class FusedNet:
             f32_on(x, dev), cond, f32_on(tangents, dev), f32_on(cond_tangents, dev), self.wpack(dev, MODE_HUTCH, plan),
             f32_on(etab, dev), f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
             _native.plan_words(plan, stage_slots), unit is not None, first, K)
+
+    def pullback(self, x: torch.Tensor, etab: torch.Tensor, cotangents: torch.Tensor, cond: Optional[torch.Tensor] = None,
+                 want_cond: bool = False, in_shift=None, in_scale=None, out_scale=None, out_shift=None, stage_slots: int = 0):
+        """The fused continuous-adjoint solve on the pull-back unit (``pull_plan``; ``etab`` has ITS width and holds the
+        rows of the REVERSED span of the solve that produced ``x``).  Returns (retraced state [B, D], gx [B, K, D],
+        gc [B, K, C] or None, status [1]): ``gx[b, k] = cotangents[b, k]^T d x[b] / d (retraced state)[b]`` and ``gc``
+        likewise for ``cond`` as given -- the continuous adjoint integrated with the table's method, not the transpose of
+        ``pushforward``'s discrete derivative.  The affine maps are this launch's own: ``in_*`` undo the output map of the
+        forward solve, ``out_*`` redo its input map; cotangents come in the units of ``x`` and leave in those of the
+        retraced state."""
+        if not x.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {x.device}); there is no CPU fallback")
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(x.shape)}")
+        dev = x.device
+        plan = self.pull_plan()
+        B = x.shape[0]
+        if self.cond_dim > 0:
+            if cond is None:
+                raise ValueError("this network has conditional inputs; `conditional` is required")
+            cond = f32_on(cond, dev)
+            if cond.dim() != 2 or cond.shape != (B, self.cond_dim):
+                raise ValueError(f"conditional must be [batch, {self.cond_dim}], got {tuple(cond.shape)}")
+        else:
+            cond = None
+        if cotangents is None or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, self.dim):
+            raise ValueError(f"pullback: cotangents [batch, K, {self.dim}]")
+        want = bool(want_cond and self.cond_dim > 0)
+        y, gx, gc, status = torch.ops.flowfusion_amd.mlp_ode_pull(
+            f32_on(x, dev), cond, f32_on(cotangents, dev).contiguous(), self.wpack(dev, MODE_HUTCH, plan), f32_on(etab, dev),
+            f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots), want)
+        return y, gx, (gc if want else None), status
 
     def cached_table(self, key, device, build):
         """Evaluation tables depend only on (time span, method, options, schedule parameters, first-layer

@@ -337,6 +337,103 @@ def solve_push_jacobian(front, x, t_span, method, options, cond=None, tangent_ga
     return y, Jx, Jc
 
 
+def solve_pull(front, x, t_span, method, options, cotangents, cond=None, in_shift=None, in_scale=None, out_scale=None,
+               out_shift=None, tangent_gain=None, cond_tangent_scale=None, return_retrace=False):
+    """Flow-map pull-backs (extension): K cotangents per sample pulled back through the fixed-grid solve of ``solve`` in
+    MODE_STATE, by the CONTINUOUS adjoint, as torchdiffeq's ``odeint_adjoint`` does.  Returns ``(y [B, D], gx [B, K, D],
+    gc [B, K, C] or None)`` -- and ``retrace [B]`` with ``return_retrace`` -- where ``gx[b, k] = cotangents[b, k]^T d y[b] /
+    d x[b]`` and ``gc`` likewise for ``cond`` (times ``1 / cond_tangent_scale``: the caller's raw conditional).
+
+    Two launches per piece of rows: the ordinary state-only solve ``x -> y`` (``y`` is bitwise what ``solve`` returns), then
+    ONE launch of a pull-back unit (FusedNet.pullback) over the REVERSED span, same method and step, on the augmented state
+    ``[y | alpha_k | gamma_k]`` from ``[y, w_k, 0]``: ``dalpha/dt = -(df/dy)^T alpha``, ``dgamma/dt = -(df/dc)^T alpha``.
+    This is NOT the transpose of the discrete map ``solve_push`` differentiates: the two differ by the discretisation
+    error of the method (order p in the step), and the backward sweep retraces ``y`` instead of storing it.
+    ``retrace[b] = max_d |y_back - x|`` in the units of ``x`` says how far the retraced trajectory ended from where the
+    forward one began: read it, use rk4 or better, and raise the step count until it is small.  (An Euler sweep of a VP
+    score model with 128 steps retraces to 0.4 and its gradient is off by 0.7; rk4 with 128 steps is off by 4e-6.)
+
+    The affine maps are those of the forward solve, as in ``solve_push``; ``tangent_gain``: the solve starts from
+    ``x * tangent_gain`` (a VE model's sigma_max), and ``gx`` carries the factor.  Rows are cut so that a [rows, K, D]
+    device buffer stays under ``PROBE_BUFFER_FLOATS`` floats; rows are independent, so any cut gives bitwise the same.
+
+    Refused with ValueError before the device is touched: adaptive methods, ``grid_constructor`` / ``perturb``, K > 15,
+    shapes that do not match, ``precision`` other than f32.  NotImplementedError: a network outside the pull-back units
+    (``_native.PULL_ENVELOPE``), or a ``model=`` module.  Out of scope: parameter gradients and torch.autograd
+    integration, the exact discrete adjoint (checkpointed states), adaptive control, sharded entry points."""
+    if method in solvers.ALL_ADAPTIVE or method in solvers.ADAPTIVE_METHODS:
+        raise ValueError(f"flow-map pull-backs with the adaptive method={method!r}: the adjoint sweep runs over the reversed "
+                         "fixed grid of the forward solve; use method=\"rk4\" / \"dopri5_fixed\" with "
+                         "options={\"step_size\": h}")
+    solvers.resolve_method(method)
+    for name in ("grid_constructor", "perturb"):
+        if (options or {}).get(name) not in (None, False):
+            raise ValueError(f"flow-map pull-backs with options[{name!r}]: the grid is the uniform one of "
+                             "options={\"step_size\": h} (or the nodes of t_span)")
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError("flow-map pull-backs: x must be a [batch, dim] tensor")
+    B, D = int(x.shape[0]), int(x.shape[1])
+    prec = getattr(front, "precision", "f32")
+    if prec != "f32":
+        raise ValueError(f"flow-map pull-backs with precision={prec!r}: the pull-back kernels compute in f32; use "
+                         "precision='f32'")
+    if not torch.is_tensor(cotangents) or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, D) or cotangents.shape[1] < 1:
+        raise ValueError(f"flow-map pull-backs: cotangents must be [{B}, K >= 1, {D}], got "
+                         f"{tuple(cotangents.shape) if torch.is_tensor(cotangents) else type(cotangents).__name__}")
+    K = int(cotangents.shape[1])
+    if K > _native.MAX_PULL_COTANGENTS:
+        raise ValueError(f"flow-map pull-backs: K={K} cotangents per sample; a sample and its cotangents share the 16 columns "
+                         f"of one tile, so at most {_native.MAX_PULL_COTANGENTS} per call")
+    try:
+        net = front._net()                  # (a ``model=`` module that is not the library's MLP raises here)
+        plan = net.pull_plan()
+    except NotImplementedError as e:
+        msg = str(e)
+        raise NotImplementedError(msg if _native.PULL_ENVELOPE in msg else
+                                  f"{msg} -- {_native.PULL_ENVELOPE}; there is no module-path fallback") from None
+    if D != net.dim:
+        raise ValueError(f"flow-map pull-backs: x has {D} columns, the model has {net.dim} dimensions")
+    C = net.cond_dim
+    if C > 0 and (cond is None or cond.dim() != 2 or tuple(cond.shape) != (B, C)):
+        raise ValueError(f"flow-map pull-backs: conditional must be [{B}, {C}], got "
+                         f"{None if cond is None else tuple(cond.shape)}")
+    if C == 0 and cond is not None:
+        raise ValueError("flow-map pull-backs: this model has no conditional inputs")
+    require_fp32(front, x, cond, cotangents, what="a flow-map pull-back solve")
+    _need_gpu(x)
+    x0 = x if tangent_gain is None else x * tangent_gain
+    y, _ = solve(front, x0, t_span, method, options, MODE_STATE, 0.0, 0.0, cond=cond, in_shift=in_shift, in_scale=in_scale,
+                 out_scale=out_scale, out_shift=out_shift)
+    t_back = torch.flip(torch.as_tensor(t_span), dims=(0,))
+    tab = solvers.plan_ode(t_back, method, options)           # (rows of a fixed-grid ODE method: none carries a noise flag)
+    width = int(plan.width)
+    key = ("pull", tuple(float(v) for v in t_back), method, repr(sorted((options or {}).items()))) + front._schedule_key()
+    table = net.cached_table(key, x.device, lambda: solvers.build_table(tab, *front._host_schedule()(tab.t_eval), width))
+    rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D))
+    pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    backs, gxs, gcs = [], [], []
+    for r0, r1 in pieces:
+        # the backward launch's maps: undo the forward solve's output map on the way in, redo its input map on the way out
+        yb, gx, gc, _ = net.pullback(cut(y, r0, r1), table, cut(cotangents, r0, r1), cond=cut(cond, r0, r1), want_cond=C > 0,
+                                     in_shift=out_shift, in_scale=out_scale, out_scale=in_scale, out_shift=in_shift,
+                                     stage_slots=solvers.resolve_method(method).stages)
+        backs.append(yb)
+        gxs.append(gx)
+        gcs.append(gc)
+    yb, gx = (backs[0], gxs[0]) if whole else (torch.cat(backs), torch.cat(gxs))
+    gc = None if C == 0 else (gcs[0] if whole else torch.cat(gcs))
+    if tangent_gain is not None:
+        gx = gx * tangent_gain
+        yb = yb / tangent_gain
+    if cond_tangent_scale is not None and gc is not None:
+        gc = gc / cond_tangent_scale
+    if not return_retrace:
+        return y, gx, gc
+    return y, gx, gc, (yb - x).abs().amax(dim=1)
+
+
 def solve_leapfrog(front, x, grid, cond=None):
     """Kick-drift-kick leapfrog of a separable front end (symplectic.py) over the nodes ``grid``; returns the state
     [B, 2D] and sets ``front.last_solver_stats``.  Compiled shapes: ONE fused launch of the row-select kernel on the table

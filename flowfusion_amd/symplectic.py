@@ -106,6 +106,11 @@ class SymplecticFlowModel(nn.Module):
 
     flow_jacobian = flow_jvp
 
+    def flow_vjp(self, *args, **kwargs):
+        """Flow-map pull-backs (``ODEFlow.flow_vjp``) are not built for the two-network kernels."""
+        raise NotImplementedError("flow_vjp of a SymplecticFlowModel: the two-network kernels carry no cotangent columns -- "
+                                  f"{_native.PULL_ENVELOPE}, on ScoreModel, ODEFlow and ConditionalODEFlow")
+
     @torch.no_grad()
     def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5):
         """``log N(z1) - log N(p0) - sum log scale`` with z1 the dopri5 solution over t: 0 -> 1 of [q0 | p0],

@@ -99,7 +99,7 @@ extern "C" {
                                    keep on chip (>= FF_MAX_SLOTS; >= 4 for the plans with four
                                    slots): that row's right-hand side was NOT stored,
                                    the results are invalid                                  */
-#define FF_STATUS_NOISE_ROW 4u  /* ff_mlp_ode_launch_push only: the table holds a row with
+#define FF_STATUS_NOISE_ROW 4u  /* ff_mlp_ode_launch_push / _pull only: the table holds a row with
                                    FF_ROW_NOISE, which has no tangent form: the results are invalid */
 
 /* evaluation-row flag bits (word 3 of the row header) */
@@ -334,6 +334,60 @@ int ff_mlp_push_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widt
                      ff_mlp_plan_t* plan_out);
 int ff_mlp_ode_launch_push(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* cond_tangent /* [batch, K, cond_dim] or NULL */,
                            float* tangent_out /* [batch, K, dim] */, void* hip_stream);
+
+/* ---- flow-map pull-backs: K cotangents through a fixed-grid adjoint solve --------------------------------------------------
+ * The pull-back units (csrc/ff_mlp_pull.hpp) integrate the CONTINUOUS adjoint, as torchdiffeq's odeint_adjoint does, for the
+ * inputs of a solve (no parameter gradients).  Run the ordinary state-only solve x -> x_out first; then ONE pull launch over a
+ * table built on the REVERSED span (same method, same step; the ordinary row format) integrates the augmented state
+ * [y | alpha_k | gamma_k], k < K, from [x_out, w_k, 0]:
+ *     dy/dt = a_e y + b_e NET(y, c)      dalpha/dt = -(a_e alpha + b_e J_net^T alpha)      dgamma/dt = -b_e (dNET/dc)^T alpha
+ * (the signs are the kernel's) and returns
+ *     args->x_out          the retraced state (compare it with x: the retrace error)
+ *     cot_x_out[b][k][:]   w_k^T d x_out[b] / d x[b]
+ *     cot_cond_out[b][k][:] w_k^T d x_out[b] / d cond[b]                      (NULL: not wanted)
+ * This is NOT the transpose of the discrete map ff_mlp_ode_launch_push differentiates: the two differ by the discretisation
+ * error of the method, and y is retraced, not stored.  The affine maps are the launch's own (args->x_in = the forward solve's
+ * x_out in ITS output units: in_shift / in_scale undo the forward solve's output map, out_scale / out_shift redo its input
+ * map); cotangent_in is taken in the units of x_in (alpha = w * in_scale) and cot_x_out handed back in those of x_out
+ * (alpha / out_scale); cot_cond_out is with respect to `cond` as given.
+ *
+ * An evaluation runs two networks: the forward network, whose value columns park act'(z) of every hidden layer in LDS, and
+ * the transposed network W_out^T, W_L^T .. W_2^T, W_1^T (no biases) on the cotangent columns.  ff_mlp_pull_wpack packs both
+ * (ff_mlp_pull_wpack_floats floats; arguments as ff_mlp_wpack).  A workgroup is ONE wavefront; its LDS holds
+ * slots * (dregs + cregs) * 256 bytes of stage slots, slots = args->stage_slots (0 = FF_MAX_SLOTS; a row naming a slot
+ * beyond them sets FF_STATUS_BAD_SLOT), and the stash, (tile / (1 + K)) * n_hidden * width * 4 bytes.  A 4 x 256 network
+ * at K = 1 with the four slots of rk4 takes 40 KiB: four wavefronts per compute unit.
+ *
+ * ff_mlp_pull_plan: the smallest of the three compiled units that holds the network -- SiLU, fp32, hidden width <= 128 with
+ * dim <= 16, width <= 256 with dim <= 16 or dim <= 32; cond_dim <= 16 -- whose K = 1 stash fits 160 KiB of LDS beside all
+ * FF_MAX_SLOTS stage slots (18 hidden
+ * layers at width 256 with dim <= 16, 17 with dim <= 32, 36 at width 128), else FF_ERR_UNSUPPORTED.  Its kernel_id is
+ * FF_PULL_KERNEL_BASE + an index (kernel names mlp_pull_...; not entries of ff_kernel_count).  ff_mlp_row_width,
+ * ff_plan_kernel_name and ff_mlp_samples_per_workgroup accept the plan; ff_mlp_wpack refuses it (FF_ERR_BADARG) and
+ * ff_mlp_wpack_floats returns 0.
+ *
+ * ff_mlp_ode_launch_pull(plan, args, cotangent_in, cot_x_out, cot_cond_out, stream): args as for ff_mlp_ode_launch with
+ * args->mode == FF_MODE_HUTCH and K = args->tangent_count; cotangent_in [batch, K, dim], cot_x_out [batch, K, dim] and
+ * cot_cond_out [batch, K, cond_dim] DEVICE memory.  Refused before anything is enqueued:
+ *     a plan that is not a pull plan (and a pull plan handed to ff_mlp_ode_launch, ff_mlp_ode_launch_probes,
+ *     ff_mlp_ode_launch_push or ff_mlp_ode_adaptive)                                              FF_ERR_BADARG
+ *     K < 1 or K > plan->tile - 1; a mode other than FF_MODE_HUTCH                                FF_ERR_BADARG
+ *     cotangent_in or cot_x_out NULL; cot_cond_out with cond_dim == 0                             FF_ERR_BADARG
+ *     noise, k1_in, kl1_in, dlogp_in, jac_out, dlogp_out or probe set, n_aux > 0                  FF_ERR_BADARG
+ *     a depth whose stash does not fit the LDS at this K                                          FF_ERR_UNSUPPORTED
+ * A table row with FF_ROW_NOISE has no adjoint form; the table is device memory, so the kernel leaves the noise out and ORs
+ * FF_STATUS_NOISE_ROW into args->status -- the results are invalid. */
+#define FF_PULL_KERNEL_BASE 0x50000
+int ff_pull_kernel_count(void);
+const char* ff_pull_kernel_name(int index);
+int ff_mlp_pull_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, int activation, int precision,
+                     ff_mlp_plan_t* plan_out);
+size_t ff_mlp_pull_wpack_floats(const ff_mlp_plan_t* plan);
+int ff_mlp_pull_wpack(const ff_mlp_plan_t* plan, const float* const* W, const float* const* b, const int* hidden_widths,
+                      int in_features0, int x_col0, int c_col0, float* out);
+int ff_mlp_ode_launch_pull(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* cotangent_in /* [batch, K, dim] */,
+                           float* cot_x_out /* [batch, K, dim] */, float* cot_cond_out /* [batch, K, cond_dim] or NULL */,
+                           void* hip_stream);
 
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
