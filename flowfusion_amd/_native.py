@@ -96,6 +96,8 @@ STATUS_NOISE_ROW = 4                                        # FF_STATUS_NOISE_RO
 MAX_PUSH_TANGENTS = 15                                      # tangent columns beside the value column of a 16-column tile
 PULL_KERNEL_BASE = 0x50000                                  # FF_PULL_KERNEL_BASE
 MAX_PULL_COTANGENTS = 15                                    # cotangent columns beside the value column of a 16-column tile
+VJP_KERNEL_BASE = 0x60000                                   # FF_VJP_KERNEL_BASE
+MAX_VJP_SEEDS = 15                                          # seed columns beside the value column of a 16-column tile
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -151,6 +153,16 @@ class TraceArgs(ctypes.Structure):        # ff_trace_args
         ("m", ctypes.c_int32), ("reserved", ctypes.c_int32), ("batch", ctypes.c_int64),
         ("jac", ctypes.c_void_p), ("probes0", ctypes.c_void_p), ("probes1", ctypes.c_void_p), ("out", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("gate", ctypes.c_void_p),
+    ]
+
+
+class TraceProdArgs(ctypes.Structure):    # ff_trace_prod_args
+    _fields_ = [
+        ("kind", ctypes.c_int32), ("dim", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("r", ctypes.c_int32),
+        ("m", ctypes.c_int32), ("reserved", ctypes.c_int32), ("batch", ctypes.c_int64),
+        ("probes0", ctypes.c_void_p), ("probes1", ctypes.c_void_p), ("y", ctypes.c_void_p), ("basis", ctypes.c_void_p),
+        ("rfac", ctypes.c_void_p), ("prod", ctypes.c_void_p), ("out", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("gate", ctypes.c_void_p),
     ]
 
 
@@ -272,6 +284,12 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_ode_launch_pull.restype = ctypes.c_int
     L.ff_mlp_ode_launch_pull.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_vjp_kernel_count.restype = ctypes.c_int
+    L.ff_vjp_kernel_name.restype = ctypes.c_char_p
+    L.ff_vjp_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_ode_launch_vjp.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_vjp.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_void_p]
     L.ff_mlp_samples_per_workgroup.restype = ctypes.c_int
     L.ff_mlp_samples_per_workgroup.argtypes = [ctypes.POINTER(PlanStruct), ctypes.c_int]
     L.ff_last_hip_error.restype = ctypes.c_int
@@ -318,6 +336,14 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_trace_estimate.argtypes = [ctypes.POINTER(TraceArgs), ctypes.c_void_p]
     L.ff_trace_estimate_host.restype = ctypes.c_int
     L.ff_trace_estimate_host.argtypes = [ctypes.POINTER(TraceArgs)]
+    L.ff_trace_prod_workspace_floats.restype = ctypes.c_size_t
+    L.ff_trace_prod_workspace_floats.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+    for fn in (L.ff_trace_basis, L.ff_trace_combine):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(TraceProdArgs), ctypes.c_void_p]
+    for fn in (L.ff_trace_basis_host, L.ff_trace_combine_host):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(TraceProdArgs)]
     L.ff_adapt_host_row.restype = ctypes.c_int
     L.ff_adapt_host_row.argtypes = [ctypes.POINTER(AdaptConfig), ctypes.c_float, ctypes.POINTER(ctypes.c_float),
                                     ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -796,6 +822,69 @@ def trace_estimate(jac: torch.Tensor, kind: str, probes, host: bool = False) -> 
     return out
 
 
+def _trace_prod(second: bool, kind: str, probes, y, basis, rfac, prod, host: bool):
+    """The one call behind ``trace_basis`` / ``trace_combine``: checks the layouts of ff_trace_prod_args, allocates what the
+    launch writes, runs it on torch's current stream (``host``: the _host twin on CPU tensors)."""
+    code, p0, p1, r, m = trace_kind_and_probes(kind, probes)
+    K2 = r + m if code == TRACE_HUTCHPP else r
+    lead = y if not second else prod
+    what = "ff_trace_combine" if second else "ff_trace_basis"
+    if lead.dim() != 4:
+        raise RuntimeError(f"{what}: products [n_rows, B, K, D], got {tuple(lead.shape)}")
+    n_rows, B, _, D = lead.shape
+    if tuple(lead.shape) != (n_rows, B, K2 if second else r, D) or tuple(p0.shape) != (r, B, D) or \
+            (p1 is not None and tuple(p1.shape) != (m, B, D)):
+        raise RuntimeError(f"{what}: products {tuple(lead.shape)} and probes {tuple(p0.shape)} do not match")
+    dev = lead.device
+    if host != (dev.type == "cpu"):
+        raise RuntimeError(f"flowfusion_amd: {what} works on device memory (host=True: CPU tensors, tests only)")
+    lead, p0, p1 = f32_on(lead, dev), f32_on(p0, dev), f32_on(p1, dev)
+    if second:
+        basis, rfac = f32_on(basis, dev), f32_on(rfac, dev)
+        if tuple(basis.shape) != (n_rows, B, K2, D) or (code == TRACE_XTRACE and (rfac is None or tuple(rfac.shape) != (n_rows, B, r, r))):
+            raise RuntimeError(f"{what}: basis {tuple(basis.shape)} does not match products {tuple(lead.shape)}")
+        out = torch.empty(n_rows, B, dtype=torch.float32, device=dev)
+    else:
+        basis = torch.empty(n_rows, B, K2, D, dtype=torch.float32, device=dev)
+        rfac = torch.empty(n_rows, B, r, r, dtype=torch.float32, device=dev) if code == TRACE_XTRACE else None
+        out = None
+    items = 1 if host else n_rows * B
+    ws = torch.empty(max(1, int(lib().ff_trace_prod_workspace_floats(code, D, r, items))), dtype=torch.float32, device=dev)
+    a = TraceProdArgs()
+    a.kind, a.dim, a.n_rows, a.r, a.m, a.batch = code, D, n_rows, r, m, B
+    a.probes0, a.probes1 = p0.data_ptr(), (0 if p1 is None else p1.data_ptr())
+    a.basis, a.rfac, a.workspace = basis.data_ptr(), (0 if rfac is None else rfac.data_ptr()), ws.data_ptr()
+    if second:
+        a.prod, a.out = lead.data_ptr(), out.data_ptr()
+    else:
+        a.y = lead.data_ptr()
+    if host:
+        rc = (lib().ff_trace_combine_host if second else lib().ff_trace_basis_host)(ctypes.byref(a))
+    else:
+        with torch.cuda.device(dev):
+            rc = (lib().ff_trace_combine if second else lib().ff_trace_basis)(
+                ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != FF_OK:
+        raise _err(rc, what)
+    return out if second else (basis, rfac)
+
+
+def trace_basis(y: torch.Tensor, kind: str, probes, host: bool = False):
+    """ff_trace_basis: from the first sweep's products ``y`` [n_rows, B, r, D] (``A p_c`` for the sketch probes S / O of
+    ``probes``, laid out as for ``trace_estimate``) the second sweep's seeds ``basis`` [n_rows, B, K2, D] -- Hutch++:
+    ``q_0 .. q_{r-1}, u_0 .. u_{m-1}``, K2 = r + m; XTrace: ``q_0 .. q_{r-1}``, K2 = r -- and ``rfac`` [n_rows, B, r, r]
+    (XTrace; else None).  ``host=True``: CPU tensors through ff_trace_basis_host (tests without a GPU)."""
+    return _trace_prod(False, kind, probes, y, None, None, None, host)
+
+
+def trace_combine(basis: torch.Tensor, rfac: Optional[torch.Tensor], prod: torch.Tensor, kind: str, probes,
+                  host: bool = False) -> torch.Tensor:
+    """ff_trace_combine: the Hutch++ / XTrace estimates [n_rows, B] from ``trace_basis``'s output and the second sweep's
+    products ``prod`` [n_rows, B, K2, D] = ``A basis``: ``trace_estimate``'s arithmetic with every matrix-vector product
+    read instead of summed.  ``host=True``: ff_trace_combine_host."""
+    return _trace_prod(True, kind, probes, None, basis, rfac, prod, host)
+
+
 _norm_ws = {}     # (device index, stream) -> (workspace, out) of ff_scaled_rms
 
 
@@ -907,11 +996,13 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
     return _AuxPtrs(*range(t.data_ptr(), t.data_ptr() + t.shape[0] * step, step))
 
 
-def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, **fields) -> None:
-    """The one launch of the seven ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
+def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, vjp=None,
+                **fields) -> None:
+    """The one launch of the eight ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
     ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, ff_mlp_ode_launch_push with
-    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, or ff_mlp_ode_launch_pull with
-    ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``.  ``tensors``: the caller's
+    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, ff_mlp_ode_launch_pull with
+    ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``, or ff_mlp_ode_launch_vjp with
+    ``vjp = (seeds, seed_row_stride, prod_out [n_evals, B, K, D])``.  ``tensors``: the caller's
     tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
     of what the op allocated itself.  A field named in neither stays zero."""
     a = OdeArgs(**fields)
@@ -920,7 +1011,11 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             setattr(a, field, _chk(t, _ARG_NAMES[field], dev))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if pull is not None:
+        if vjp is not None:
+            what = "ff_mlp_ode_launch_vjp"
+            rc = lib().ff_mlp_ode_launch_vjp(ctypes.byref(p), ctypes.byref(a), _chk(vjp[0], "seeds", dev), int(vjp[1]),
+                                             _chk(vjp[2], "prod_out", dev), ctypes.c_void_p(stream))
+        elif pull is not None:
             what = "ff_mlp_ode_launch_pull"
             rc = lib().ff_mlp_ode_launch_pull(ctypes.byref(p), ctypes.byref(a), _chk(pull[0], "cotangents", dev),
                                               _chk(pull[1], "cot_x_out", dev), _chk(pull[2], "cot_cond_out", dev),
@@ -1122,6 +1217,48 @@ def _(x, cond, cotangents, wpack, etab, in_shift, in_scale, out_scale, out_shift
     B, K = x.shape[0], cotangents.shape[1]
     C = _plan_from_words(plan).cond_dim if want_cond else 0
     return (torch.empty_like(x), x.new_empty(B, K, x.shape[1]), x.new_empty(B, K, C),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_vjp_products", mutates_args=())
+def mlp_ode_vjp_products(x: torch.Tensor, cond: Optional[torch.Tensor], seeds: torch.Tensor, wpack: torch.Tensor, etab: torch.Tensor,
+                         in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor],
+                         out_shift: Optional[torch.Tensor], plan: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused fixed-grid solve of the state over the (forward) rows ``etab`` with K products per evaluation row
+    (ff_mlp_ode_launch_vjp): returns (x_out [B, D], prod [n_evals, B, K, D], status [1]) with
+    ``prod[e, b, k] = a_e seed + b_e J_net(y_e)^T seed`` at the stage state ``y_e`` of row e.  ``seeds`` [B, K, D]: the same
+    seeds on every row; [n_evals, B, K, D]: seeds per row.  ``plan`` / ``wpack``: the PULL plan and its two packs."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_vjp_products needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    B, D = x.shape
+    n = int(etab.shape[0])
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    per_row = seeds.dim() == 4
+    if seeds.dim() not in (3, 4) or tuple(seeds.shape[-3::2]) != (B, D) or seeds.shape[-2] < 1 or (per_row and seeds.shape[0] != n):
+        raise RuntimeError(f"seeds has shape {tuple(seeds.shape)}, expected [{B}, K >= 1, {D}] or [{n}, {B}, K >= 1, {D}]")
+    K = int(seeds.shape[-2])
+    x_out = torch.empty_like(x)
+    prod = torch.empty(n, B, K, D, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, prod, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                vjp=(seeds, B * K * D if per_row else 0, prod), x_out=x_out.data_ptr(), status=status.data_ptr(), batch=B,
+                n_evals=n, mode=MODE_HUTCH, tangent_count=K, stage_slots=_slots_hint(plan))
+    return x_out, prod, status
+
+
+@mlp_ode_vjp_products.register_fake
+def _(x, cond, seeds, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan):
+    return (torch.empty_like(x), x.new_empty(etab.shape[0], x.shape[0], seeds.shape[-2], x.shape[1]),
             torch.empty(1, dtype=torch.int32, device=x.device))
 
 

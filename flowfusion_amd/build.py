@@ -150,6 +150,13 @@ def _pull_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_pull_m{tile}_h{h}_d{d}_c{c}"
 
 
+# Products units (ff_mlp_vjp.hpp; ff_mlp_ode_launch_vjp): the pull-back evaluation body run on a forward table, J^T seed of every
+# evaluation row written out -- the Hutch++ / XTrace route products="vjp".  One sibling per pull-back unit, same shape and the
+# same two weight packs: a pull plan launches entry i of g_vjp_kernels (FF_VJP_KERNEL_BASE names them, no plan carries it).
+def _vjp_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_vjp_m{tile}_h{h}_d{d}_c{c}"
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -287,7 +294,10 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     # the pull-back units: one wavefront per workgroup, a registry header of their own
     pulls = [(_pull_name(*i), "ff_mlp_pull.hpp", f"mlp_pull_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
     files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_pull_registry.h")) for name, header, expr in pulls]
-    units = units + pulls
+    # their products siblings
+    vjps = [(_vjp_name(*i), "ff_mlp_vjp.hpp", f"mlp_vjp_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
+    files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_vjp_registry.h")) for name, header, expr in vjps]
+    units = units + pulls + vjps
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
     fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
@@ -320,9 +330,13 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     pull_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pull_name(*i)}, "{_pull_name(*i)}"}}' for i in PULL_INSTANCES
     ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor pull kernels)
+    vjp_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_vjp_name(*i)}, "{_vjp_name(*i)}"}}' for i in PULL_INSTANCES
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor their products siblings)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
+#include "ff_vjp_registry.h"
 namespace ff {{
 {decls}
 const KernelEntry g_kernels[] = {{
@@ -345,6 +359,10 @@ const PullKernelEntry g_pull_kernels[] = {{
 {pull_rows}
 }};
 const int g_n_pull_kernels = {len(PULL_INSTANCES)};
+const PullKernelEntry g_vjp_kernels[] = {{
+{vjp_rows}
+}};
+const int g_n_vjp_kernels = {len(PULL_INSTANCES)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -352,6 +370,7 @@ const int g_n_pull_kernels = {len(PULL_INSTANCES)};
     files.append(CSRC / "ff_aux.hip")
     files.append(CSRC / "ff_adaptive.hip")
     files.append(CSRC / "ff_trace.hip")
+    files.append(CSRC / "ff_trace_prod.hip")
     files.append(CSRC / "ff_marginal.hip")
     files.append(CSRC / "ff_probe.hip")
     files.append(CSRC / "ff_observe.hip")
@@ -374,7 +393,7 @@ def _cost(src: Path) -> float:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
     if n.startswith("mlp_push_"):
         return 16 if "_h256_" in n else 6
-    if n.startswith("mlp_pull_"):
+    if n.startswith("mlp_pull_") or n.startswith("mlp_vjp_"):
         return 40 if "_h256_" in n else 15
     if n.startswith("mlp_pairsel_"):
         return (7 if "_h256_" in n else 3) if "_coop" in n else (16 if "_h256_" in n else 7)

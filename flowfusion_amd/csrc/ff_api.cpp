@@ -8,6 +8,7 @@
 #include "ff_split_layout.h"
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
+#include "ff_vjp_registry.h"
 #include "ff_adapt_logic.h"
 
 static_assert(FF_MAX_SLOTS == ff::kSlots, "slot count mismatch between header and kernel");
@@ -179,6 +180,7 @@ struct LaunchDesc {
     bool checks_noise_stride;  // noise_stride >= batch * dim where `noise` is set
     bool empty_batch_first;    // an empty batch is FF_OK before n_aux, k1_in, noise_stride and jac_out are looked at
     const ff::SplitKernelEntry* split;      // kSplit: the entry (that family keeps its own launch geometry, launch_split)
+    bool products;             // kPull: the launch runs the plan's products sibling (ff_mlp_ode_launch_vjp sets it: ff_mlp_vjp.hpp)
 };
 
 static bool shape_ok(const ff_mlp_plan_t* p, int tile, int H, int dregs, int cregs)
@@ -287,6 +289,14 @@ static size_t pull_lds_bytes(const ff_mlp_plan_t* p, int K, int n_slots = ff::kS
 }
 constexpr size_t kPullLdsLimit = 160u * 1024u;      // LDS of a compute unit = the most a workgroup can ask for
 
+// The same of a products tile (ff_mlp_vjp.hpp): the stash is the pull tile's, a stage slot holds dregs words per lane -- the
+// seed columns integrate nothing and no conditional part is carried.
+static size_t vjp_lds_bytes(const ff_mlp_plan_t* p, int K, int n_slots = ff::kSlots)
+{
+    const size_t slots = (size_t)n_slots * (p->dregs / 4) * 64 * 16;
+    return slots + (size_t)(p->tile / (1 + K)) * p->n_hidden * p->width * 4;
+}
+
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
@@ -346,6 +356,21 @@ extern "C" int ff_pull_kernel_count(void) { return ff::g_n_pull_kernels; }
 extern "C" const char* ff_pull_kernel_name(int index)
 {
     return index >= 0 && index < ff::g_n_pull_kernels ? ff::g_pull_kernels[index].name : NULL;
+}
+
+// The products table is a WEAK reference here: a program that links this file with kernel tables of its own from before the
+// products units (tests/sanitize/pull_wpack_main.cpp) still links, and sees a library without products units.
+namespace ff {
+extern const PullKernelEntry g_vjp_kernels[] __attribute__((weak));
+extern const int g_n_vjp_kernels __attribute__((weak));
+}
+static int n_vjp_kernels() { return &ff::g_n_vjp_kernels ? ff::g_n_vjp_kernels : 0; }
+
+extern "C" int ff_vjp_kernel_count(void) { return n_vjp_kernels(); }
+
+extern "C" const char* ff_vjp_kernel_name(int index)
+{
+    return index >= 0 && index < n_vjp_kernels() ? ff::g_vjp_kernels[index].name : NULL;
 }
 
 // the smallest pull-back unit that holds the network (best_entry's preference), SiLU, fp32 -- and whose slope stash fits the
@@ -875,7 +900,7 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
     if (d.family == kPull) {
         // a wavefront per workgroup and per tile; LDS = stage slots + the slope stash of the tile's samples
         const long long tiles = (batch + spt - 1) / spt;
-        const size_t lds = pull_lds_bytes(plan, ka.n_tangent, ka.tangent_first);
+        const size_t lds = (d.products ? vjp_lds_bytes : pull_lds_bytes)(plan, ka.n_tangent, ka.tangent_first);
         if (lds > kPullLdsLimit || tiles > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
         const int herr = d.one_wave(&ka, (unsigned)tiles, (unsigned)lds, stream);
         if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
@@ -938,15 +963,35 @@ struct PullIo {
     float* cot_cond_out;
 };
 
-// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push and ff_mlp_ode_launch_pull: one
-// argument check, one launch path
+// What ff_mlp_ode_launch_vjp adds to a launch (NULL: not a products launch).
+struct VjpIo {
+    const float* seed_in;
+    int64_t seed_row_stride;
+    float* prod_out;
+};
+
+// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push, ff_mlp_ode_launch_pull and
+// ff_mlp_ode_launch_vjp: one argument check, one launch path
 static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr,
-                      const PullIo* pull = nullptr)
+                      const PullIo* pull = nullptr, const VjpIo* vjp = nullptr)
 {
     LaunchDesc d;
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
-    if (pull && d.family == kSplit) return FF_ERR_UNSUPPORTED;
-    if ((d.family == kPull) != (pull != nullptr)) return FF_ERR_BADARG;      // pull plans launch through their own entry, and only they
+    if ((pull || vjp) && d.family == kSplit) return FF_ERR_UNSUPPORTED;
+    // pull plans launch through their own two entries, and only they
+    if ((d.family == kPull) != (pull != nullptr || vjp != nullptr)) return FF_ERR_BADARG;
+    if (vjp) {
+        // whole fixed-grid solves of the state with K products per evaluation row: the pull launch's refusals, its own buffers
+        const int index = plan->kernel_id - FF_PULL_KERNEL_BASE;
+        if (index < 0 || index >= n_vjp_kernels() || !ff::g_vjp_kernels[index].launch) return FF_ERR_BADARG;
+        if (!vjp->seed_in || !vjp->prod_out || a->mode != FF_MODE_HUTCH) return FF_ERR_BADARG;
+        if (a->tangent_count < 1 || a->tangent_count + 1 > plan->tile) return FF_ERR_BADARG;
+        if (a->probe || a->dlogp_out || a->k1_in || a->kl1_in || a->dlogp_in || a->jac_out || a->n_aux > 0 || a->noise) return FF_ERR_BADARG;
+        if (vjp->seed_row_stride != 0 && vjp->seed_row_stride != a->batch * (int64_t)a->tangent_count * plan->dim) return FF_ERR_BADARG;
+        const int ns = a->stage_slots > 0 && a->stage_slots <= FF_MAX_SLOTS ? a->stage_slots : FF_MAX_SLOTS;
+        if (vjp_lds_bytes(plan, a->tangent_count, ns) > kPullLdsLimit) return FF_ERR_UNSUPPORTED;      // the stash does not fit
+        d.products = true; d.one_wave = ff::g_vjp_kernels[index].launch; d.name = ff::g_vjp_kernels[index].name;
+    }
     if (pull) {
         // whole fixed-grid adjoint solves: K cotangents as given, nothing of the divergence side, no attempt launches, no noise
         if (!pull->cotangent_in || !pull->cot_x_out || a->mode != FF_MODE_HUTCH) return FF_ERR_BADARG;
@@ -993,8 +1038,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     }
     // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
     if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;
-    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull) return FF_ERR_BADARG;      // (push: no state tangents = zero)
-    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull && !vjp) return FF_ERR_BADARG;      // (push: no state tangents = zero)
+    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull && !vjp) return FF_ERR_BADARG;
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->batch == 0 && d.empty_batch_first) return FF_OK;
     if (a->n_aux < 0 || a->n_aux > d.max_aux || (a->k1_in && !d.takes_k1)) return FF_ERR_BADARG;
@@ -1004,7 +1049,7 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
 
     ff::KernelArgs ka = fill_args(plan, a, !d.state_only, nt, unit, tfirst);
     ka.etab_stride = FF_ROW_HDR + d.row_nets * plan->width;
-    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull ? pull_layout(plan).total_floats : 0);
+    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull || vjp ? pull_layout(plan).total_floats : 0);
     if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
@@ -1014,6 +1059,11 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     if (pull) {
         ka.probe = pull->cotangent_in; ka.dlogp_out = pull->cot_x_out; ka.jac_out = pull->cot_cond_out;
         ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;      // the stage slots the kernel keeps in LDS
+    }
+    // (nor does a products launch, which takes no noise either: ff_mlp_vjp.hpp)
+    if (vjp) {
+        ka.probe = vjp->seed_in; ka.dlogp_out = vjp->prod_out; ka.noise_stride = vjp->seed_row_stride;
+        ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;
     }
     return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
 }
@@ -1040,6 +1090,13 @@ extern "C" int ff_mlp_ode_launch_pull(const ff_mlp_plan_t* plan, const ff_ode_ar
 {
     const PullIo io = {cotangent_in, cot_x_out, cot_cond_out};
     return launch_ode(plan, a, nullptr, hip_stream, nullptr, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_vjp(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* seed_in, int64_t seed_row_stride,
+                                     float* prod_out, void* hip_stream)
+{
+    const VjpIo io = {seed_in, seed_row_stride, prod_out};
+    return launch_ode(plan, a, nullptr, hip_stream, nullptr, nullptr, &io);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

@@ -643,7 +643,7 @@ class ScoreModel(nn.Module):
     @torch.no_grad()
     def solve_odes_forward(self, x0_samples, conditional=None, atol=1e-5, rtol=1e-5,
                            method="dopri5", options=None, *, probe="torch", seed=None, sample_offset=0, num_probes=1,
-                           return_stderr=False):
+                           return_stderr=False, products="jacobian"):
         """Probability-flow ODE from epsilon up to t=1 with the divergence integrated alongside;
         returns ``(xT, delta_logp[B,1])`` (reference: diffusion.py:642-754).
 
@@ -669,21 +669,47 @@ class ScoreModel(nn.Module):
         probes as [B, K, D]; probe 0 of ``probe="philox"`` is the single-probe stream's, probe k >= 1 lives under the noise
         index FF_HUTCH_PROBE_NOISE_BASE + k.  On fixed grids the rows are cut so that a probe buffer on the device stays
         under 1 GiB (``odeint.solve_hutchinson``; ``probe="torch"`` still draws the whole [B, K, D] set on the host, and
-        ``self.e`` holds it whole).  f32 kernels only."""
+        ``self.e`` holds it whole).  f32 kernels only.
+
+        ``products`` (keyword only, extension; ``hutchpp=True`` / ``xtrace=True`` models): how a Hutch++ / XTrace solve gets
+        its matrix-vector products.  ``"jacobian"`` (default): today's route, bit for bit -- the Jacobian of every
+        evaluation row is recorded in forward mode (D + 1 tile columns per sample, ``n_evals B D D`` floats through memory)
+        and ``ff_trace_estimate`` reads it.  ``"vjp"`` (opt-in): the reference's own route (diffusion.py:356-398,
+        :419-455), J^T v products in reverse mode -- two sweeps of the products unit over the fixed grid
+        (``ff_mlp_ode_launch_vjp``; r, then r + m seed columns per sample for Hutch++, m and m for XTrace) with
+        ``ff_trace_basis`` between and ``ff_trace_combine`` after them; ``(2r + m) D`` or ``2m D`` floats per evaluation and
+        sample, no Jacobian.  Same probes (``probe="torch"`` / ``"philox"``), same ``self.S`` / ``self.G`` / ``self.O``, same
+        shapes.  The two routes agree to rounding, not bitwise.  When the Jacobian route is the cheaper one: at small D,
+        where D + 1 columns undercut two sweeps that each run two networks, and at many seed columns (a tile holds
+        16 // (1 + K) samples).  Measured (one MI355X, 100-step rk4, 2^16 rows, 4x256, whole calls against the parent
+        commit's in the same run; profiles/estimator_products.txt): 16-d 0.62x at r = m = 1, 0.75x at XTrace m = 2, 2.36x
+        (slower) at r = m = 4; 32-d 0.30x, 0.39x, 1.17x (slower).  ``"vjp"`` refuses, with ValueError before the device is touched:
+        adaptive methods -- the default here: pass ``method="rk4"`` / ``"dopri5_fixed"`` with
+        ``options={"step_size": h}``, or stay with ``"jacobian"`` --, ``grid_constructor`` / ``perturb``, a model without
+        ``hutchpp=True`` / ``xtrace=True``, ``hpp_rank + hpp_vecs > 15`` or ``xt_vecs > 15``, ``precision`` other than f32;
+        with NotImplementedError naming ``_native.PULL_ENVELOPE``: a network outside the pull-back units, a ``model=``
+        module.  Out of scope: the adaptive / device-controller hook-up (adaptive solves, the reference's defaults, still
+        take the Jacobian route), a single-sweep kernel with the QR in it, sharded entry points (rows are independent:
+        slice), the flows (no estimators), split precision and non-SiLU activations, a module-path fallback,
+        ``num_probes``; ``log_prob_noisy`` / ``posterior_noisy`` keep their signatures and the Jacobian route."""
         philox_ok = self.hutch or self.hutchpp or self.xtrace
         out = self._solve_forward(x0_samples, conditional, atol, rtol, method, options, probe_rng=trace_estimators.probe_rng(
             probe, seed, sample_offset, philox_ok, "probe='philox' draws the probes of a Hutchinson / Hutch++ / XTrace model: "
-            "construct it with hutchinson=True, hutchpp=True or xtrace=True"), num_probes=num_probes, return_stderr=return_stderr)
+            "construct it with hutchinson=True, hutchpp=True or xtrace=True"), num_probes=num_probes, return_stderr=return_stderr,
+            products=products)
         return out if return_stderr else out[:2]
 
     @torch.no_grad()
     def _solve_forward(self, x0_samples, conditional, atol, rtol, method, options, in_shift=None, in_scale=None,
-                       probe_rng=None, num_probes=1, return_stderr=False):
+                       probe_rng=None, num_probes=1, return_stderr=False, products="jacobian"):
         """solve_odes_forward proper; returns ``(xT, delta_logp [B,1], stderr [B,1] or None)``.  ``(x - in_shift) / in_scale``
         (PopulationModel*.log_prob, diffusion.py:1633, 1837) is applied by the kernel's prologue."""
         K = trace_estimators.check_num_probes(num_probes, bool(self.hutch), "construct the model with hutchinson=True",
                                               estimator=bool((self.hutchpp or self.xtrace) and not self.hutch))
         stderr = trace_estimators.check_stderr(return_stderr, K, method)
+        estimator = bool((self.hutchpp or self.xtrace) and not self.hutch)
+        if products != "jacobian" and not estimator:
+            odeint.check_products(self, products, method, options)      # (raises: no estimator, or no such route)
         fused = self._fusable()
         if fused:
             self._net()
@@ -692,7 +718,8 @@ class ScoreModel(nn.Module):
         if (self.hutchpp or self.xtrace) and not self.hutch:
             if in_shift is not None:
                 x0_samples = (x0_samples - in_shift) / in_scale
-            return self._solve_with_estimator(x0_samples, conditional, atol, rtol, method, options, fused, probe_rng) + (None,)
+            return self._solve_with_estimator(x0_samples, conditional, atol, rtol, method, options, fused, probe_rng,
+                                              products) + (None,)
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
         if not self.hutch:
             xT, dlogp = odeint.solve(self, x0_samples, t_span, method, options, MODE_EXACT, atol, rtol, cond=conditional,
@@ -707,12 +734,16 @@ class ScoreModel(nn.Module):
             self.dlogp_probes = d
         return xT, dlogp.view(-1, 1), (trace_estimators.hutchinson_stderr(d).view(-1, 1) if stderr else None)
 
-    def _solve_with_estimator(self, x0, conditional, atol, rtol, method, options, fused, probe_rng=None):
+    def _solve_with_estimator(self, x0, conditional, atol, rtol, method, options, fused, probe_rng=None, products="jacobian"):
         """Hutch++ / XTrace log-density solve.  The state never depends on the divergence, so the fused launches are those
         of the exact trace with the Jacobian of every evaluation row recorded (ff_ode_args.jac_all); the estimates of all
         rows come from ONE launch (ff_trace_estimate, csrc/ff_trace.hip) and are combined with the tableau's weights
         (odeint.py picks the route).  Any other module: forward() runs the estimator itself (reverse mode, like the
-        reference).  Probes are drawn once per solve on the state's device, as the reference does (:703-719)."""
+        reference).  Probes are drawn once per solve on the state's device, as the reference does (:703-719).
+        ``products="vjp"``: the same estimates from J^T v products (``solve_odes_forward``; odeint.check_products)."""
+        if products != "jacobian":
+            (r, m), mx = self._probe_counts(x0.shape[1])
+            odeint.check_products(self, products, method, options, *(("hutchpp", r, m) if self.hutchpp else ("xtrace", mx, 0)))
         if fused:
             net = self._net()
             if net.precision != "f32":
@@ -736,18 +767,20 @@ class ScoreModel(nn.Module):
             kind, probes = "xtrace", (self.O,)
         t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
         y, lp = odeint.solve(self, x0, t_span, method, options, MODE_EXACT, atol, rtol, cond=conditional,
-                             estimator=(kind, probes), div_fn=lambda A: self._estimate_divergence(A, x0))
+                             estimator=(kind, probes), div_fn=lambda A: self._estimate_divergence(A, x0), products=products)
         return y, lp.view(-1, 1)
 
     @torch.no_grad()
     def log_prob(self, x0_samples, conditional=None, atol=1e-4, rtol=1e-4, method="dopri5",
-                 options={"min_step": 1e-6}, *, probe="torch", seed=None, sample_offset=0, num_probes=1, return_stderr=False):
+                 options={"min_step": 1e-6}, *, probe="torch", seed=None, sample_offset=0, num_probes=1, return_stderr=False,
+                 products="jacobian"):
         """log p(x0) = delta_logp + log prior(xT), shape [B,1] (reference: diffusion.py:756-815).  ``probe`` / ``seed`` /
-        ``sample_offset`` / ``num_probes`` / ``return_stderr``: see ``solve_odes_forward``; with ``return_stderr=True``
+        ``sample_offset`` / ``num_probes`` / ``return_stderr`` / ``products``: see ``solve_odes_forward``; with ``return_stderr=True``
         returns ``(log_p [B,1], stderr [B,1])`` (the prior term is exact, so the standard error is ``delta_logp``'s)."""
         out = self.solve_odes_forward(x0_samples, conditional=conditional, atol=atol, rtol=rtol,
                                       method=method, options=options, probe=probe, seed=seed,
-                                      sample_offset=sample_offset, num_probes=num_probes, return_stderr=return_stderr)
+                                      sample_offset=sample_offset, num_probes=num_probes, return_stderr=return_stderr,
+                                      products=products)
         xT, lp = out[0], out[1]
         logp = lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
         return (logp, out[2]) if return_stderr else logp

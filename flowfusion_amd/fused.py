@@ -306,6 +306,43 @@ class FusedNet:
             _native.plan_words(plan, stage_slots), want)
         return y, gx, (gc if want else None), status
 
+    def vjp_products(self, x: torch.Tensor, etab: torch.Tensor, seeds: torch.Tensor, per_row: bool = False,
+                     cond: Optional[torch.Tensor] = None, stage_slots: int = 0, in_shift=None, in_scale=None, out_scale=None,
+                     out_shift=None):
+        """The fused fixed-grid solve of the state on the products unit (the sibling of ``pull_plan``'s; ``etab`` has ITS
+        width and holds the rows of the FORWARD span) with K products per evaluation row.  ``seeds`` [B, K, D] (the same on
+        every row) or, with ``per_row``, [n_evals, B, K, D].  Returns (x_out [B, D], prod [n_evals, B, K, D], status [1]):
+        ``prod[e, b, k] = a_e seed + b_e J_net(y_e)^T seed`` at the stage state of row e -- row e of
+        ``mlp_ode_jacobians``' record applied to the seed, without the record.  Seeds and products are in the units of the
+        integrated state; the state never depends on them."""
+        if not x.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {x.device}); there is no CPU fallback")
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(x.shape)}")
+        dev = x.device
+        plan = self.pull_plan()
+        B, n = x.shape[0], int(etab.shape[0])
+        if self.cond_dim > 0:
+            if cond is None:
+                raise ValueError("this network has conditional inputs; `conditional` is required")
+            cond = f32_on(cond, dev)
+            if cond.dim() != 2 or cond.shape != (B, self.cond_dim):
+                raise ValueError(f"conditional must be [batch, {self.cond_dim}], got {tuple(cond.shape)}")
+        else:
+            cond = None
+        want = ((n, B) if per_row else (B,))
+        if seeds is None or seeds.dim() != len(want) + 2 or tuple(seeds.shape[:-2]) != want or seeds.shape[-1] != self.dim:
+            raise ValueError(f"vjp_products: seeds {list(want) + ['K', self.dim]}, got {None if seeds is None else tuple(seeds.shape)}")
+        K = int(seeds.shape[-2])
+        if not 1 <= K <= _native.MAX_VJP_SEEDS:
+            raise ValueError(f"vjp_products: 1 <= K <= {_native.MAX_VJP_SEEDS} seed columns beside the value column, got {K}")
+        return torch.ops.flowfusion_amd.mlp_ode_vjp_products(
+            f32_on(x, dev), cond, f32_on(seeds, dev), self.wpack(dev, MODE_HUTCH, plan), f32_on(etab, dev),
+            f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots))
+
     def cached_table(self, key, device, build):
         """Evaluation tables depend only on (time span, method, options, schedule parameters, first-layer
         weights): keep the last few on the device so repeated solves skip the host work."""

@@ -34,8 +34,50 @@ def _fixed_grid(front, net, x, t_span, method, options, mode, **launch):
     return net.integrate(x, table, mode, stage_slots=solvers.resolve_method(method).stages, **launch)
 
 
+ESTIMATOR_MIN_BYTES = 1 << 30      # a fixed-grid estimator solve cuts its batch no finer than this many bytes per chunk
+PRODUCTS = ("jacobian", "vjp")
+MAX_PRODUCT_SEEDS = _native.MAX_VJP_SEEDS      # seed columns of the second sweep: r + m (Hutch++) or m (XTrace)
+
+
+def check_products(front, products, method, options, kind=None, r=0, m=0):
+    """The refusals of ``products="vjp"`` (``solve``), raised before the device is touched; each names the way out.
+    ``kind`` None: the front end is not an estimator model."""
+    if products not in PRODUCTS:
+        raise ValueError(f"products={products!r}: expected 'jacobian' (the recorded-Jacobian route, the default) or 'vjp'")
+    if products == "jacobian":
+        return
+    if kind is None:
+        raise ValueError("products='vjp' is a route of the Hutch++ / XTrace estimators: construct the model with hutchpp=True "
+                         "or xtrace=True (hutchinson=True and the exact trace have their own fused launches)")
+    if method in solvers.ALL_ADAPTIVE or method in solvers.ADAPTIVE_METHODS:
+        raise ValueError(f"products='vjp' with the adaptive method={method!r}: the two sweeps run over a fixed grid; use "
+                         "method=\"rk4\" / \"dopri5_fixed\" with options={\"step_size\": h}, or products=\"jacobian\"")
+    solvers.resolve_method(method)
+    for name in ("grid_constructor", "perturb"):
+        if (options or {}).get(name) not in (None, False):
+            raise ValueError(f"products='vjp' with options[{name!r}]: the grid is the uniform one of "
+                             "options={\"step_size\": h} (or the nodes of t_span); or use products=\"jacobian\"")
+    prec = getattr(front, "precision", "f32")
+    if prec != "f32":
+        raise ValueError(f"products='vjp' with precision={prec!r}: the products kernels compute in f32; use precision='f32'")
+    seeds = r + m if kind == "hutchpp" else r
+    if seeds > MAX_PRODUCT_SEEDS:
+        what = f"hpp_rank + hpp_vecs = {r} + {m}" if kind == "hutchpp" else f"xt_vecs = {r}"
+        raise ValueError(f"products='vjp' with {what} > {MAX_PRODUCT_SEEDS}: a sample and the second sweep's seeds share the "
+                         "16 columns of one tile; use products=\"jacobian\"")
+    try:
+        if not front._fusable():
+            raise NotImplementedError("products='vjp' needs the library's MLP (a ``model=`` module has no products kernel)")
+        front._net().pull_plan()
+    except NotImplementedError as e:
+        msg = str(e)
+        raise NotImplementedError(msg if _native.PULL_ENVELOPE in msg else
+                                  f"{msg} -- {_native.PULL_ENVELOPE}; there is no module-path fallback: use "
+                                  "products=\"jacobian\"") from None
+
+
 def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=None, norm_only=(), estimator=None,
-          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None):
+          div_fn=None, in_shift=None, in_scale=None, out_scale=None, out_shift=None, products="jacobian"):
     """``odeint(front, x, t_span, method=, atol=, rtol=, options=)``; returns (y [B, D], dlogp [B] or None) and sets
     ``front.last_solver_stats`` (fused fixed-grid solves leave it alone).
 
@@ -43,7 +85,20 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
     adaptive error norm only.  ``estimator = (kind, probes)``: a Hutch++ / XTrace solve in MODE_EXACT (``div_fn(A)`` is its
     estimate on the host controller; on the generic route the front end's module estimates by itself).  The affine maps
     (PopulationModel*, flow sampling): ``(x - in_shift) / in_scale`` before the solve, ``y * out_scale + out_shift`` after
-    it -- on the host around the adaptive and generic routes, in the kernel's prologue / epilogue on fixed grids."""
+    it -- on the host around the adaptive and generic routes, in the kernel's prologue / epilogue on fixed grids.
+
+    ``products`` (estimator solves): ``"jacobian"`` (default) records the Jacobian of every evaluation row
+    (``RowStepper.run_table_recorded``, ``n_evals * B * D * D`` floats through memory, D + 1 tile columns per sample);
+    ``"vjp"`` (opt-in, fixed grids, the pull-back units' networks) computes the estimators as the reference does, from
+    J^T v products: two sweeps of the products unit and two streaming launches (``RowStepper.run_table_products``),
+    ``(2r + m) D`` or ``2m D`` floats per evaluation and sample.  The two agree to rounding, not bitwise.  At small D the
+    Jacobian route is the cheaper one (D + 1 columns undercut two sweeps of two networks).  ``check_products`` lists what
+    ``"vjp"`` refuses; adaptive solves -- the reference's defaults -- always take the Jacobian route."""
+    if products != "jacobian":
+        if estimator is None:
+            check_products(front, products, method, options)
+        else:
+            check_products(front, products, method, options, estimator[0], *_native.trace_kind_and_probes(*estimator)[3:])
     if estimator is None:           # (the estimator solves have never refused other dtypes: they cast the state to fp32)
         require_fp32(front, x, cond, probe, what="an ODE solve")
     fused = front._fusable()
@@ -76,10 +131,18 @@ def solve(front, x, t_span, method, options, mode, atol, rtol, cond=None, probe=
         # all of them (the recorded Jacobians of a chunk of samples may take a quarter of the free device memory: cutting a
         # batch into many small launches leaves their last rounds of tiles mostly empty)
         kind, probes = estimator
-        div_rows = lambda A, lo, hi: _native.trace_estimate(A, kind, tuple(P[:, lo:hi] for P in probes))
-        y, lp = RowStepper(net, x.device, cond, None).run_table_recorded(
-            x, front._ode_table(t_span, method, options, MODE_EXACT), div_rows, cond=cond,
-            max_bytes=max(1 << 30, _estimator_budget(x.device) // 2))
+        budget = max(ESTIMATOR_MIN_BYTES, _estimator_budget(x.device) // 2)
+        if products == "vjp":
+            # the same estimates from J^T v products: two sweeps of the products unit over the pull plan's table, the basis
+            # between them and the combination after them (no Jacobian leaves the chip)
+            grid = solvers.plan_ode(t_span, method, options)
+            table = solvers.build_table(grid, *front._host_schedule()(grid.t_eval), int(net.pull_plan().width))
+            y, lp = RowStepper(net, x.device, cond, None).run_table_products(
+                x, table, kind, probes, cond=cond, max_bytes=budget, stage_slots=solvers.resolve_method(method).stages)
+        else:
+            div_rows = lambda A, lo, hi: _native.trace_estimate(A, kind, tuple(P[:, lo:hi] for P in probes))
+            y, lp = RowStepper(net, x.device, cond, None).run_table_recorded(
+                x, front._ode_table(t_span, method, options, MODE_EXACT), div_rows, cond=cond, max_bytes=budget)
     else:
         spec = front._device_schedule(x.device) if (x.is_cuda and method in solvers.NATIVE_ADAPTIVE) else None
         if device_adaptive.supported(spec, x, net, mode, options) and (estimator is None or device_adaptive.estimator_bytes(

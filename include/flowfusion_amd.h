@@ -389,6 +389,33 @@ int ff_mlp_ode_launch_pull(const ff_mlp_plan_t* plan, const ff_ode_args* args, c
                            float* cot_x_out /* [batch, K, dim] */, float* cot_cond_out /* [batch, K, cond_dim] or NULL */,
                            void* hip_stream);
 
+/* ---- per-row J^T v products along a fixed-grid solve: what Hutch++ / XTrace consume instead of a recorded Jacobian --------
+ * The products units (csrc/ff_mlp_vjp.hpp), one sibling per pull-back unit, run the pull-back evaluation body on an ordinary
+ * FORWARD table: the value column integrates the state exactly as a state-only solve does (stage slots, the affine maps,
+ * args->x_out), and at every evaluation row e the K seed columns of a sample write
+ *     prod_out[e][b][k][:] = a_e seed + b_e J_net(y_e, c)^T seed  =  A(y_e) seed,    A = (d rhs / d y)^T at the stage state y_e
+ * -- row e of ff_ode_args.jac_all applied to a vector, without the matrix.  seed = seed_in[b][k][:] on every row
+ * (seed_row_stride == 0) or seed_in[e][b][k][:] (seed_row_stride == batch * K * dim).  Seeds and products are in the units
+ * of the integrated state (after the input map); the state never depends on them.
+ *
+ * ff_mlp_ode_launch_vjp(plan, args, seed_in, seed_row_stride, prod_out, stream): `plan` is a PULL plan (ff_mlp_pull_plan)
+ * and args->wpack its two packs (ff_mlp_pull_wpack); the launch runs the sibling of the plan's unit (ff_vjp_kernel_name
+ * (plan->kernel_id - FF_PULL_KERNEL_BASE); FF_VJP_KERNEL_BASE + index names it, no plan carries that id).  args as for
+ * ff_mlp_ode_launch with args->mode == FF_MODE_HUTCH and K = args->tangent_count; DEVICE memory.  A tile holds
+ * tile / (1 + K) samples; LDS = stage_slots * dregs * 256 bytes of stage slots and the stash of ff_mlp_ode_launch_pull.
+ * Refused before anything is enqueued:
+ *     a plan that is not a pull plan; K < 1 or K > plan->tile - 1; a mode other than FF_MODE_HUTCH     FF_ERR_BADARG
+ *     seed_in or prod_out NULL; a seed_row_stride other than 0 or batch * K * dim                      FF_ERR_BADARG
+ *     noise, k1_in, kl1_in, dlogp_in, jac_out, dlogp_out or probe set, n_aux > 0                       FF_ERR_BADARG
+ *     a depth whose stash does not fit the LDS at this K                                               FF_ERR_UNSUPPORTED
+ * A table row with FF_ROW_NOISE has no product form: the kernel leaves the noise out and ORs FF_STATUS_NOISE_ROW into
+ * args->status; FF_STATUS_BAD_SLOT and FF_STATUS_NAN (a NaN in the final state) as in ff_mlp_ode_launch_pull. */
+#define FF_VJP_KERNEL_BASE 0x60000
+int ff_vjp_kernel_count(void);
+const char* ff_vjp_kernel_name(int index);
+int ff_mlp_ode_launch_vjp(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* seed_in, int64_t seed_row_stride,
+                          float* prod_out /* [n_evals, batch, K, dim] */, void* hip_stream);
+
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
  * query, so that callers, benchmarks and tests can name the kernel that ran without timing it.  Honours FF_COOP /
@@ -696,6 +723,46 @@ int ff_trace_estimate(const ff_trace_args* args, void* hip_stream);
 /* The same arithmetic on the HOST (tests without a GPU): HOST pointers; `workspace` holds
  * ff_trace_workspace_floats(kind, dim, r, 1) floats; `gate` is ignored. */
 int ff_trace_estimate_host(const ff_trace_args* args);
+
+/* ---- the same estimates from J^T v PRODUCTS (csrc/ff_trace_prod.hip, csrc/ff_trace_prod.h) -------------------------------
+ *
+ * The reference computes both estimators from 2r + m (Hutch++) or 2m (XTrace) reverse-mode products per right-hand side
+ * (diffusion.py:356-398, :419-455).  With ff_mlp_ode_launch_vjp supplying the products A v = a v + b J_net^T v of every
+ * evaluation row, an estimate takes two sweeps and two streaming launches, and no Jacobian is recorded:
+ *     sweep 1           y[e][b][c][:]    = A(y_e) p_c                     p = S (Hutch++, r columns) or O (XTrace, r columns)
+ *     ff_trace_basis    Q = thin_qr(y[e][b]) -- the QR of ff_trace_estimate -- and
+ *                       basis[e][b] = [q_0 .. q_{r-1} | u_0 .. u_{m-1}],  u_g = g - Q (Q^T g)      Hutch++, K2 = r + m
+ *                       basis[e][b] = [q_0 .. q_{r-1}],  rfac[e][b] = R                             XTrace,  K2 = r
+ *     sweep 2           prod[e][b][c][:] = A(y_e) basis[e][b][c]
+ *     ff_trace_combine  out[e][b] = the estimate of :381-400 from (Q, U, AQ, AU), or of :451-481 from (Q, R, O, AQ)
+ * in the fp32 operation order of ff_trace_estimate with every product read instead of summed.  One work item per
+ * (row, sample); plain global-memory kernels (an item moves K2 * D floats, not D * D).  All pointers are DEVICE pointers
+ * (HOST pointers for the _host twins, tests without a GPU: `workspace` then holds one item's floats, `gate` is ignored).
+ * FF_ERR_BADARG: a kind other than FF_TRACE_*, dim < 1, r < 1 or r > dim, Hutch++ with m < 1 or no probes1, XTrace without
+ * rfac, a NULL probes0 / basis / workspace, ff_trace_basis without y, ff_trace_combine without prod or out. */
+typedef struct ff_trace_prod_args {
+    int32_t kind;            /* FF_TRACE_*                                                                     */
+    int32_t dim;             /* D                                                                               */
+    int32_t n_rows;          /* evaluation rows                                                                 */
+    int32_t r;               /* Hutch++: sketch probes S (`hpp_rank`, <= D); XTrace: probes O (`xt_vecs`, <= D)  */
+    int32_t m;               /* Hutch++: residual probes G (`hpp_vecs`, >= 1); XTrace: unused                   */
+    int32_t reserved;
+    int64_t batch;
+    const float* probes0;    /* S or O: [r][batch][D]                                                           */
+    const float* probes1;    /* G: [m][batch][D], or NULL (XTrace)                                              */
+    const float* y;          /* [n_rows][batch][r][D]   sweep 1's products          (ff_trace_basis)            */
+    float*       basis;      /* [n_rows][batch][K2][D]  written by ff_trace_basis, read by ff_trace_combine     */
+    float*       rfac;       /* [n_rows][batch][r][r]   XTrace: R, likewise; Hutch++: NULL                      */
+    const float* prod;       /* [n_rows][batch][K2][D]  sweep 2's products          (ff_trace_combine)          */
+    float*       out;        /* [n_rows][batch]                                     (ff_trace_combine)          */
+    float*       workspace;  /* ff_trace_prod_workspace_floats(kind, dim, r, n_rows * batch) floats              */
+    const int32_t* gate;     /* optional DEVICE word: 0 = the launch does nothing (see ff_ode_args.gate)         */
+} ff_trace_prod_args;
+size_t ff_trace_prod_workspace_floats(int32_t kind, int32_t dim, int32_t r, int64_t items);
+int ff_trace_basis(const ff_trace_prod_args* args, void* hip_stream);
+int ff_trace_combine(const ff_trace_prod_args* args, void* hip_stream);
+int ff_trace_basis_host(const ff_trace_prod_args* args);
+int ff_trace_combine_host(const ff_trace_prod_args* args);
 
 /* ---- adaptive embedded Runge-Kutta solves with the step control ON THE DEVICE (csrc/ff_adaptive.hip) ---------
  *
