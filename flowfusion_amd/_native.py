@@ -98,6 +98,8 @@ PULL_KERNEL_BASE = 0x50000                                  # FF_PULL_KERNEL_BAS
 MAX_PULL_COTANGENTS = 15                                    # cotangent columns beside the value column of a 16-column tile
 VJP_KERNEL_BASE = 0x60000                                   # FF_VJP_KERNEL_BASE
 MAX_VJP_SEEDS = 15                                          # seed columns beside the value column of a 16-column tile
+REC_KERNEL_BASE = 0x70000                                   # FF_REC_KERNEL_BASE
+DADJ_KERNEL_BASE = 0x80000                                  # FF_DADJ_KERNEL_BASE
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -290,6 +292,17 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_ode_launch_vjp.restype = ctypes.c_int
     L.ff_mlp_ode_launch_vjp.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_void_p, ctypes.c_void_p]
+    for fam in ("rec", "dadj"):
+        getattr(L, f"ff_{fam}_kernel_count").restype = ctypes.c_int
+        getattr(L, f"ff_{fam}_kernel_name").restype = ctypes.c_char_p
+        getattr(L, f"ff_{fam}_kernel_name").argtypes = [ctypes.c_int]
+    L.ff_mlp_record_floats.restype = ctypes.c_size_t
+    L.ff_mlp_record_floats.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
+    L.ff_mlp_ode_launch_record.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_record.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_mlp_ode_launch_pull_discrete.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_pull_discrete.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.ff_mlp_samples_per_workgroup.restype = ctypes.c_int
     L.ff_mlp_samples_per_workgroup.argtypes = [ctypes.POINTER(PlanStruct), ctypes.c_int]
     L.ff_last_hip_error.restype = ctypes.c_int
@@ -997,12 +1010,14 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
 
 
 def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, vjp=None,
-                **fields) -> None:
-    """The one launch of the eight ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
+                record=None, discrete=None, **fields) -> None:
+    """The one launch of the ten ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
     ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, ff_mlp_ode_launch_push with
     ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, ff_mlp_ode_launch_pull with
     ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``, or ff_mlp_ode_launch_vjp with
-    ``vjp = (seeds, seed_row_stride, prod_out [n_evals, B, K, D])``.  ``tensors``: the caller's
+    ``vjp = (seeds, seed_row_stride, prod_out [n_evals, B, K, D])``, ff_mlp_ode_launch_record with ``record = record_out
+    [n_evals, B, D]``, or ff_mlp_ode_launch_pull_discrete with ``discrete = (record [n_evals, B, D], cotangents [B, K, D],
+    cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``.  ``tensors``: the caller's
     tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
     of what the op allocated itself.  A field named in neither stays zero."""
     a = OdeArgs(**fields)
@@ -1011,7 +1026,16 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             setattr(a, field, _chk(t, _ARG_NAMES[field], dev))
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if vjp is not None:
+        if record is not None:
+            what = "ff_mlp_ode_launch_record"
+            rc = lib().ff_mlp_ode_launch_record(ctypes.byref(p), ctypes.byref(a), _chk(record, "record_out", dev),
+                                                ctypes.c_void_p(stream))
+        elif discrete is not None:
+            what = "ff_mlp_ode_launch_pull_discrete"
+            rc = lib().ff_mlp_ode_launch_pull_discrete(ctypes.byref(p), ctypes.byref(a), _chk(discrete[0], "record", dev),
+                                                       _chk(discrete[1], "cotangents", dev), _chk(discrete[2], "cot_x_out", dev),
+                                                       _chk(discrete[3], "cot_cond_out", dev), ctypes.c_void_p(stream))
+        elif vjp is not None:
             what = "ff_mlp_ode_launch_vjp"
             rc = lib().ff_mlp_ode_launch_vjp(ctypes.byref(p), ctypes.byref(a), _chk(vjp[0], "seeds", dev), int(vjp[1]),
                                              _chk(vjp[2], "prod_out", dev), ctypes.c_void_p(stream))
@@ -1260,6 +1284,91 @@ def mlp_ode_vjp_products(x: torch.Tensor, cond: Optional[torch.Tensor], seeds: t
 def _(x, cond, seeds, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan):
     return (torch.empty_like(x), x.new_empty(etab.shape[0], x.shape[0], seeds.shape[-2], x.shape[1]),
             torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_record", mutates_args=())
+def mlp_ode_record(x: torch.Tensor, cond: Optional[torch.Tensor], wpack: torch.Tensor, etab: torch.Tensor,
+                   in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor],
+                   out_shift: Optional[torch.Tensor], plan: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused fixed-grid solve of the state over the (forward) rows ``etab`` that writes every stage state down
+    (ff_mlp_ode_launch_record): returns (x_out [B, D], record [n_evals, B, D], status [1]) with ``record[e, b]`` = the stage
+    state y_e of row e in the integrated state's units (after the input map).  ``plan`` / ``wpack``: the PULL plan and its
+    two packs."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_record needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    B, D = x.shape
+    n = int(etab.shape[0])
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    x_out = torch.empty_like(x)
+    rec = torch.empty(n, B, D, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, rec, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                record=rec, x_out=x_out.data_ptr(), status=status.data_ptr(), batch=B, n_evals=n, mode=MODE_STATE,
+                stage_slots=_slots_hint(plan))
+    return x_out, rec, status
+
+
+@mlp_ode_record.register_fake
+def _(x, cond, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan):
+    return (torch.empty_like(x), x.new_empty(etab.shape[0], x.shape[0], x.shape[1]),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_pull_discrete", mutates_args=())
+def mlp_ode_pull_discrete(record: torch.Tensor, cond: Optional[torch.Tensor], cotangents: torch.Tensor, wpack: torch.Tensor,
+                          etab: torch.Tensor, in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor],
+                          out_scale: Optional[torch.Tensor], out_shift: Optional[torch.Tensor], plan: List[int], want_cond: bool
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The exact discrete adjoint (ff_mlp_ode_launch_pull_discrete): the transposed row program of the FORWARD rows ``etab``,
+    run backwards over ``record`` [n_evals, B, D] (``mlp_ode_record`` of the same table, cond and maps).  Returns (cot_x
+    [B, K, D], cot_cond [B, K, C] -- [B, K, 0] unless ``want_cond`` --, status [1]) with ``cot_x[b, k] = cotangents[b, k]^T
+    d x_out[b] / d x[b]`` of the discrete solver map and ``cot_cond[b, k]`` likewise for ``cond[b]``."""
+    if not record.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_pull_discrete needs tensors on the GPU (there is no CPU path)")
+    dev = record.device
+    p = _plan_from_words(plan)
+    n = int(etab.shape[0])
+    if record.dim() != 3 or record.shape[0] != n or record.shape[2] != p.dim:
+        raise RuntimeError(f"record has shape {tuple(record.shape)}, expected [{n}, B, {p.dim}]")
+    B, D = int(record.shape[1]), int(record.shape[2])
+    if cotangents.dim() != 3 or cotangents.shape[0] != B or cotangents.shape[2] != D or cotangents.shape[1] < 1:
+        raise RuntimeError(f"cotangents has shape {tuple(cotangents.shape)}, expected [{B}, K >= 1, {D}]")
+    K = int(cotangents.shape[1])
+    C = int(p.cond_dim) if want_cond else 0
+    if want_cond and p.cond_dim == 0:
+        raise RuntimeError("want_cond on a plan without conditional inputs")
+    gx = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+    gc = torch.empty(B, K, C, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return gx, gc, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"cond": cond, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                discrete=(record, cotangents, gx, gc if want_cond else None), status=status.data_ptr(), batch=B,
+                n_evals=n, mode=MODE_HUTCH, tangent_count=K, stage_slots=_slots_hint(plan))
+    return gx, gc, status
+
+
+@mlp_ode_pull_discrete.register_fake
+def _(record, cond, cotangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, want_cond):
+    B, K = record.shape[1], cotangents.shape[1]
+    C = _plan_from_words(plan).cond_dim if want_cond else 0
+    return (record.new_empty(B, K, record.shape[2]), record.new_empty(B, K, C),
+            torch.empty(1, dtype=torch.int32, device=record.device))
 
 
 @torch.library.custom_op("flowfusion_amd::mlp_ode_step", mutates_args=())

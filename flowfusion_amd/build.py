@@ -157,6 +157,18 @@ def _vjp_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_vjp_m{tile}_h{h}_d{d}_c{c}"
 
 
+# Record and discrete-adjoint units (ff_mlp_dadj.hpp; ff_mlp_ode_launch_record, ff_mlp_ode_launch_pull_discrete): a forward solve
+# that writes every stage state down, and the transposed row program run backwards over that record -- flow_vjp(adjoint=
+# "discrete").  One sibling of each per pull-back unit, same shape and the same two weight packs: a pull plan launches entry i of
+# g_rec_kernels / g_dadj_kernels (FF_REC_KERNEL_BASE / FF_DADJ_KERNEL_BASE name them, no plan carries them).
+def _rec_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_rec_m{tile}_h{h}_d{d}_c{c}"
+
+
+def _dadj_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_dadj_m{tile}_h{h}_d{d}_c{c}"
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -297,7 +309,11 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     # their products siblings
     vjps = [(_vjp_name(*i), "ff_mlp_vjp.hpp", f"mlp_vjp_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
     files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_vjp_registry.h")) for name, header, expr in vjps]
-    units = units + pulls + vjps
+    # the record and discrete-adjoint siblings
+    dadjs = [(_rec_name(*i), "ff_mlp_dadj.hpp", f"mlp_rec_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES] + \
+            [(_dadj_name(*i), "ff_mlp_dadj.hpp", f"mlp_dadj_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
+    files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_dadj_registry.h")) for name, header, expr in dadjs]
+    units = units + pulls + vjps + dadjs
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
     fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
@@ -333,10 +349,17 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     vjp_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_vjp_name(*i)}, "{_vjp_name(*i)}"}}' for i in PULL_INSTANCES
     ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor their products siblings)
+    rec_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_rec_name(*i)}, "{_rec_name(*i)}"}}' for i in PULL_INSTANCES
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the record units)
+    dadj_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_dadj_name(*i)}, "{_dadj_name(*i)}"}}' for i in PULL_INSTANCES
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the discrete-adjoint units)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
 #include "ff_vjp_registry.h"
+#include "ff_dadj_registry.h"
 namespace ff {{
 {decls}
 const KernelEntry g_kernels[] = {{
@@ -363,6 +386,14 @@ const PullKernelEntry g_vjp_kernels[] = {{
 {vjp_rows}
 }};
 const int g_n_vjp_kernels = {len(PULL_INSTANCES)};
+const PullKernelEntry g_rec_kernels[] = {{
+{rec_rows}
+}};
+const int g_n_rec_kernels = {len(PULL_INSTANCES)};
+const PullKernelEntry g_dadj_kernels[] = {{
+{dadj_rows}
+}};
+const int g_n_dadj_kernels = {len(PULL_INSTANCES)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -393,8 +424,10 @@ def _cost(src: Path) -> float:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
     if n.startswith("mlp_push_"):
         return 16 if "_h256_" in n else 6
-    if n.startswith("mlp_pull_") or n.startswith("mlp_vjp_"):
+    if n.startswith("mlp_pull_") or n.startswith("mlp_vjp_") or n.startswith("mlp_dadj_"):
         return 40 if "_h256_" in n else 15
+    if n.startswith("mlp_rec_"):
+        return 16 if "_h256_" in n else 6
     if n.startswith("mlp_pairsel_"):
         return (7 if "_h256_" in n else 3) if "_coop" in n else (16 if "_h256_" in n else 7)
     if n.startswith("mlp_pair_"):

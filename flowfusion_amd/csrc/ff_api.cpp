@@ -9,6 +9,7 @@
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
 #include "ff_vjp_registry.h"
+#include "ff_dadj_registry.h"
 #include "ff_adapt_logic.h"
 
 static_assert(FF_MAX_SLOTS == ff::kSlots, "slot count mismatch between header and kernel");
@@ -181,6 +182,7 @@ struct LaunchDesc {
     bool empty_batch_first;    // an empty batch is FF_OK before n_aux, k1_in, noise_stride and jac_out are looked at
     const ff::SplitKernelEntry* split;      // kSplit: the entry (that family keeps its own launch geometry, launch_split)
     bool products;             // kPull: the launch runs the plan's products sibling (ff_mlp_ode_launch_vjp sets it: ff_mlp_vjp.hpp)
+    bool record, discrete;     // kPull: the plan's record / discrete-adjoint sibling (ff_mlp_ode_launch_record, _pull_discrete: ff_mlp_dadj.hpp)
 };
 
 static bool shape_ok(const ff_mlp_plan_t* p, int tile, int H, int dregs, int cregs)
@@ -297,6 +299,13 @@ static size_t vjp_lds_bytes(const ff_mlp_plan_t* p, int K, int n_slots = ff::kSl
     return slots + (size_t)(p->tile / (1 + K)) * p->n_hidden * p->width * 4;
 }
 
+// The same of a record tile (ff_mlp_dadj.hpp): stage slots of dregs words per lane and nothing else.  A discrete-adjoint tile
+// takes vjp_lds_bytes: adjoint slots of dregs words per lane and the pull tile's stash.
+static size_t rec_lds_bytes(const ff_mlp_plan_t* p, int n_slots = ff::kSlots)
+{
+    return (size_t)n_slots * (p->dregs / 4) * 64 * 16;
+}
+
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
@@ -371,6 +380,37 @@ extern "C" int ff_vjp_kernel_count(void) { return n_vjp_kernels(); }
 extern "C" const char* ff_vjp_kernel_name(int index)
 {
     return index >= 0 && index < n_vjp_kernels() ? ff::g_vjp_kernels[index].name : NULL;
+}
+
+// The record and discrete-adjoint tables: weak for the same reason.
+namespace ff {
+extern const PullKernelEntry g_rec_kernels[] __attribute__((weak));
+extern const int g_n_rec_kernels __attribute__((weak));
+extern const PullKernelEntry g_dadj_kernels[] __attribute__((weak));
+extern const int g_n_dadj_kernels __attribute__((weak));
+}
+static int n_rec_kernels() { return &ff::g_n_rec_kernels ? ff::g_n_rec_kernels : 0; }
+static int n_dadj_kernels() { return &ff::g_n_dadj_kernels ? ff::g_n_dadj_kernels : 0; }
+
+extern "C" int ff_rec_kernel_count(void) { return n_rec_kernels(); }
+
+extern "C" const char* ff_rec_kernel_name(int index)
+{
+    return index >= 0 && index < n_rec_kernels() ? ff::g_rec_kernels[index].name : NULL;
+}
+
+extern "C" int ff_dadj_kernel_count(void) { return n_dadj_kernels(); }
+
+extern "C" const char* ff_dadj_kernel_name(int index)
+{
+    return index >= 0 && index < n_dadj_kernels() ? ff::g_dadj_kernels[index].name : NULL;
+}
+
+// floats of the record of a solve: one stage state per evaluation row and sample; 0 for arguments that describe none
+extern "C" size_t ff_mlp_record_floats(int64_t batch, int32_t n_evals, int32_t dim)
+{
+    if (batch < 0 || n_evals < 0 || dim < 0) return 0;
+    return (size_t)batch * (size_t)n_evals * (size_t)dim;
 }
 
 // the smallest pull-back unit that holds the network (best_entry's preference), SiLU, fp32 -- and whose slope stash fits the
@@ -900,7 +940,8 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
     if (d.family == kPull) {
         // a wavefront per workgroup and per tile; LDS = stage slots + the slope stash of the tile's samples
         const long long tiles = (batch + spt - 1) / spt;
-        const size_t lds = (d.products ? vjp_lds_bytes : pull_lds_bytes)(plan, ka.n_tangent, ka.tangent_first);
+        const size_t lds = d.record ? rec_lds_bytes(plan, ka.tangent_first)
+                                    : (d.products || d.discrete ? vjp_lds_bytes : pull_lds_bytes)(plan, ka.n_tangent, ka.tangent_first);
         if (lds > kPullLdsLimit || tiles > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
         const int herr = d.one_wave(&ka, (unsigned)tiles, (unsigned)lds, stream);
         if (herr != 0) { t_last_hip_error = herr; return FF_ERR_HIP; }
@@ -970,16 +1011,50 @@ struct VjpIo {
     float* prod_out;
 };
 
-// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push, ff_mlp_ode_launch_pull and
-// ff_mlp_ode_launch_vjp: one argument check, one launch path
+// What ff_mlp_ode_launch_record adds to a launch (NULL: not a record launch).
+struct RecIo {
+    float* record_out;
+};
+
+// What ff_mlp_ode_launch_pull_discrete adds to a launch (NULL: not a discrete-adjoint launch).
+struct DadjIo {
+    const float* record_in;
+    const float* cotangent_in;
+    float* cot_x_out;
+    float* cot_cond_out;
+};
+
+// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push, ff_mlp_ode_launch_pull,
+// ff_mlp_ode_launch_vjp, ff_mlp_ode_launch_record and ff_mlp_ode_launch_pull_discrete: one argument check, one launch path
 static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr,
-                      const PullIo* pull = nullptr, const VjpIo* vjp = nullptr)
+                      const PullIo* pull = nullptr, const VjpIo* vjp = nullptr, const RecIo* rec = nullptr, const DadjIo* dadj = nullptr)
 {
     LaunchDesc d;
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
-    if ((pull || vjp) && d.family == kSplit) return FF_ERR_UNSUPPORTED;
-    // pull plans launch through their own two entries, and only they
-    if ((d.family == kPull) != (pull != nullptr || vjp != nullptr)) return FF_ERR_BADARG;
+    if ((pull || vjp || rec || dadj) && d.family == kSplit) return FF_ERR_UNSUPPORTED;
+    // pull plans launch through their own entries, and only they
+    if ((d.family == kPull) != (pull != nullptr || vjp != nullptr || rec != nullptr || dadj != nullptr)) return FF_ERR_BADARG;
+    if (rec) {
+        // a whole fixed-grid solve of the state that writes every stage state down: a state-only launch's arguments, the pull
+        // launch's refusals.  No cotangent columns: no stash, and the tile's columns are all samples
+        const int index = plan->kernel_id - FF_PULL_KERNEL_BASE;
+        if (index < 0 || index >= n_rec_kernels() || !ff::g_rec_kernels[index].launch) return FF_ERR_BADARG;
+        if (!rec->record_out || a->mode != FF_MODE_STATE) return FF_ERR_BADARG;
+        if (a->probe || a->dlogp_out || a->k1_in || a->kl1_in || a->dlogp_in || a->jac_out || a->n_aux > 0 || a->noise) return FF_ERR_BADARG;
+        d.record = true; d.tangents = 0; d.one_wave = ff::g_rec_kernels[index].launch; d.name = ff::g_rec_kernels[index].name;
+    }
+    if (dadj) {
+        // the transposed row program over a record: K cotangents as given, the FORWARD launch's table and maps
+        const int index = plan->kernel_id - FF_PULL_KERNEL_BASE;
+        if (index < 0 || index >= n_dadj_kernels() || !ff::g_dadj_kernels[index].launch) return FF_ERR_BADARG;
+        if (!dadj->record_in || !dadj->cotangent_in || !dadj->cot_x_out || a->mode != FF_MODE_HUTCH) return FF_ERR_BADARG;
+        if (a->tangent_count < 1 || a->tangent_count + 1 > plan->tile) return FF_ERR_BADARG;
+        if (a->probe || a->dlogp_out || a->k1_in || a->kl1_in || a->dlogp_in || a->jac_out || a->n_aux > 0 || a->noise) return FF_ERR_BADARG;
+        if (dadj->cot_cond_out && plan->cond_dim == 0) return FF_ERR_BADARG;
+        const int ns = a->stage_slots > 0 && a->stage_slots <= FF_MAX_SLOTS ? a->stage_slots : FF_MAX_SLOTS;
+        if (vjp_lds_bytes(plan, a->tangent_count, ns) > kPullLdsLimit) return FF_ERR_UNSUPPORTED;      // the stash does not fit
+        d.discrete = true; d.one_wave = ff::g_dadj_kernels[index].launch; d.name = ff::g_dadj_kernels[index].name;
+    }
     if (vjp) {
         // whole fixed-grid solves of the state with K products per evaluation row: the pull launch's refusals, its own buffers
         const int index = plan->kernel_id - FF_PULL_KERNEL_BASE;
@@ -1017,7 +1092,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
         if (a->k1_in || a->kl1_in || a->dlogp_in || a->n_aux > 0 || a->jac_out) return FF_ERR_BADARG;
     }
     if (d.family == kSplit) return launch_split(plan, *d.split, a, hip_stream);
-    if (!a->x_in || !a->x_out || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
+    // (a discrete-adjoint launch reads the record instead of a state and writes none)
+    if (((!a->x_in || !a->x_out) && !dadj) || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
     int nt, unit;
     int rc = tangents_of_mode(a->mode, plan->dim, plan->tile, &nt, &unit);
@@ -1038,8 +1114,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     }
     // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
     if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;
-    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull && !vjp) return FF_ERR_BADARG;      // (push: no state tangents = zero)
-    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull && !vjp) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull && !vjp && !dadj) return FF_ERR_BADARG;      // (push: no state tangents = zero)
+    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull && !vjp && !dadj) return FF_ERR_BADARG;
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->batch == 0 && d.empty_batch_first) return FF_OK;
     if (a->n_aux < 0 || a->n_aux > d.max_aux || (a->k1_in && !d.takes_k1)) return FF_ERR_BADARG;
@@ -1049,7 +1125,7 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
 
     ff::KernelArgs ka = fill_args(plan, a, !d.state_only, nt, unit, tfirst);
     ka.etab_stride = FF_ROW_HDR + d.row_nets * plan->width;
-    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull || vjp ? pull_layout(plan).total_floats : 0);
+    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull || vjp || rec || dadj ? pull_layout(plan).total_floats : 0);
     if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
@@ -1063,6 +1139,15 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     // (nor does a products launch, which takes no noise either: ff_mlp_vjp.hpp)
     if (vjp) {
         ka.probe = vjp->seed_in; ka.dlogp_out = vjp->prod_out; ka.noise_stride = vjp->seed_row_stride;
+        ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;
+    }
+    // (the record and discrete-adjoint launches: ff_mlp_dadj.hpp)
+    if (rec) {
+        ka.dlogp_out = rec->record_out;
+        ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;
+    }
+    if (dadj) {
+        ka.probe = dadj->cotangent_in; ka.dlogp_out = dadj->cot_x_out; ka.jac_out = dadj->cot_cond_out; ka.k1_in = dadj->record_in;
         ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;
     }
     return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
@@ -1097,6 +1182,19 @@ extern "C" int ff_mlp_ode_launch_vjp(const ff_mlp_plan_t* plan, const ff_ode_arg
 {
     const VjpIo io = {seed_in, seed_row_stride, prod_out};
     return launch_ode(plan, a, nullptr, hip_stream, nullptr, nullptr, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_record(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* record_out, void* hip_stream)
+{
+    const RecIo io = {record_out};
+    return launch_ode(plan, a, nullptr, hip_stream, nullptr, nullptr, nullptr, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_pull_discrete(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* record_in,
+                                               const float* cotangent_in, float* cot_x_out, float* cot_cond_out, void* hip_stream)
+{
+    const DadjIo io = {record_in, cotangent_in, cot_x_out, cot_cond_out};
+    return launch_ode(plan, a, nullptr, hip_stream, nullptr, nullptr, nullptr, nullptr, &io);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

@@ -613,7 +613,7 @@ class ScoreModel(nn.Module):
 
     @torch.no_grad()
     def flow_vjp(self, x, cotangents, conditional=None, *, direction="to_data", method="rk4", options=None,
-                 return_retrace=False):
+                 return_retrace=False, adjoint="continuous"):
         """Extension: K cotangents pulled back through the probability-flow solve of ``flow_jvp``, reverse mode: returns
         ``(x_out [B, D], gx [B, K, D], gc [B, K, C] or None)`` -- plus ``retrace [B]`` with ``return_retrace`` -- with
         ``gx[b, k] = cotangents[b, k]^T d x_out[b] / d x[b]`` and ``gc`` likewise for ``conditional``; ``cotangents`` is
@@ -627,14 +627,21 @@ class ScoreModel(nn.Module):
         count until it is small.  (Measured in float64 on a VP model: gap to ``w^T flow_jacobian`` 4e-4 with 32 rk4 steps,
         4e-6 with 128; with 128 EULER steps ``to_base`` the gap is 0.7 and the retrace 0.4.)
 
-        No parameter gradients, no torch.autograd integration, no adaptive step control, no exact discrete adjoint: see
-        ``odeint.solve_pull``."""
-        return self._flow_vjp(x, cotangents, conditional, direction, method, options, return_retrace)
+        ``adjoint="discrete"`` (keyword only) takes the exact discrete adjoint instead (``odeint.solve_pull_discrete``): a
+        forward launch records the stage state of every evaluation row and a second one runs the transposed row program
+        backwards over them, so ``gx`` and ``gc`` are the transpose of what ``flow_jvp`` differentiates up to rounding at ANY
+        step count -- the gradient of the function that is actually evaluated.  ``x_out`` is then the record launch's state
+        (bitwise the fixed-grid solve's, as on the default route), nothing is retraced (``return_retrace`` raises), and
+        the record costs ``n_evals * B * D`` floats of device memory per piece of rows.  Any other value raises ValueError.
 
-    def _flow_vjp(self, x, cotangents, conditional, direction, method, options, return_retrace, **maps):
+        No parameter gradients, no torch.autograd integration, no adaptive step control: see ``odeint.solve_pull`` and
+        ``odeint.solve_pull_discrete``."""
+        return self._flow_vjp(x, cotangents, conditional, direction, method, options, return_retrace, adjoint)
+
+    def _flow_vjp(self, x, cotangents, conditional, direction, method, options, return_retrace, adjoint="continuous", **maps):
         t_span, gain = self._push_args(x, direction)
-        return odeint.solve_pull(self, x, t_span, method, options, cotangents, cond=conditional, tangent_gain=gain,
-                                 return_retrace=return_retrace, **maps)
+        return odeint.solve_pull_by(adjoint, self, x, t_span, method, options, cotangents, cond=conditional, tangent_gain=gain,
+                                    return_retrace=return_retrace, **maps)
 
     def _flow_jacobian(self, x, conditional, direction, method, options, **maps):
         t_span, gain = self._push_args(x, direction)
@@ -901,11 +908,11 @@ class _PopulationModel(nn.Module):
         return self.score_model._flow_jacobian(x, cond, direction, method, options, **maps)
 
     @torch.no_grad()
-    def _flow_vjp(self, x, cotangents, conditional, direction, method, options, return_retrace):
+    def _flow_vjp(self, x, cotangents, conditional, direction, method, options, return_retrace, adjoint="continuous"):
         """``flow_vjp`` of the two wrappers: ``ScoreModel.flow_vjp`` of the inner score model between the wrappers' affine
         maps, so that ``x``, ``x_out``, ``conditional`` and every cotangent are in the user's units."""
         cond, maps = self._push_maps(conditional, direction)
-        return self.score_model._flow_vjp(x, cotangents, cond, direction, method, options, return_retrace, **maps)
+        return self.score_model._flow_vjp(x, cotangents, cond, direction, method, options, return_retrace, adjoint, **maps)
 
     @torch.no_grad()
     def _log_prob_noisy(self, x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
@@ -966,11 +973,14 @@ class PopulationModelDiffusion(_PopulationModel):
         """Extension: ``ScoreModel.flow_jacobian`` in the units of this wrapper: ``(x_out [B, D], J_x [B, D, D], None)``."""
         return self._flow_jacobian(x, None, direction, method, options)
 
-    def flow_vjp(self, x, cotangents, *, direction="to_data", method="rk4", options=None, return_retrace=False):
+    def flow_vjp(self, x, cotangents, *, direction="to_data", method="rk4", options=None, return_retrace=False,
+                 adjoint="continuous"):
         """Extension: ``ScoreModel.flow_vjp`` in the units of this wrapper: ``(x_out [B, D], gx [B, K, D], None)`` (and
         ``retrace [B]``), ``gx[b, k] = cotangents[b, k]^T d x_out[b] / d x[b]`` -- the continuous adjoint: use rk4 or
-        better, read ``retrace``, raise the step count (``options={"step_size": h}``; the default grid is ONE step)."""
-        return self._flow_vjp(x, cotangents, None, direction, method, options, return_retrace)
+        better, read ``retrace``, raise the step count (``options={"step_size": h}``; the default grid is ONE step).
+        ``adjoint="discrete"``: the exact discrete adjoint from recorded stage states instead -- the transpose of
+        ``flow_jvp`` at any step count, the default one-step grid included; nothing is retraced."""
+        return self._flow_vjp(x, cotangents, None, direction, method, options, return_retrace, adjoint)
 
     def log_prob_noisy(self, x, noise_std, num_draws=16, atol=1e-5, rtol=1e-5, *, seed=None, sample_offset=0,
                        chunk_points=None, return_ess=False, num_probes=1):
@@ -1030,12 +1040,13 @@ class PopulationModelDiffusionConditional(_PopulationModel):
         return self._flow_jacobian(x, conditional, direction, method, options)
 
     def flow_vjp(self, x, cotangents, conditional=None, *, direction="to_data", method="rk4", options=None,
-                 return_retrace=False):
+                 return_retrace=False, adjoint="continuous"):
         """Extension: ``ScoreModel.flow_vjp`` in the units of this wrapper: ``(x_out [B, D], gx [B, K, D], gc [B, K, C])``
         (and ``retrace [B]``), ``gc`` with respect to the RAW conditional (the population hyper-parameters) -- the
         continuous adjoint: use rk4 or better, read ``retrace``, raise the step count (``options={"step_size": h}``; the
-        default grid is ONE step)."""
-        return self._flow_vjp(x, cotangents, conditional, direction, method, options, return_retrace)
+        default grid is ONE step).  ``adjoint="discrete"``: the exact discrete adjoint from recorded stage states instead
+        -- the transpose of ``flow_jvp`` at any step count, the default one-step grid included; nothing is retraced."""
+        return self._flow_vjp(x, cotangents, conditional, direction, method, options, return_retrace, adjoint)
 
     def log_prob_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-5, rtol=1e-5, *, seed=None,
                        sample_offset=0, chunk_points=None, return_ess=False, num_probes=1):

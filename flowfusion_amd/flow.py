@@ -229,7 +229,7 @@ class _FlowBase(nn.Module):
 
     @torch.no_grad()
     def flow_vjp(self, x, cotangents, conditional=None, *, direction="to_data", method="rk4", options=None,
-                 return_retrace=False):
+                 return_retrace=False, adjoint="continuous"):
         """Extension: K cotangents pulled back through the solve of ``sample`` (``direction="to_data"``, ``x`` = base points)
         or of ``log_prob`` (``"to_base"``, ``x`` = target-space points), reverse mode: returns ``(x_out [B, D], gx [B, K, D],
         gc [B, K, C] or None)`` -- plus ``retrace [B]`` with ``return_retrace`` -- with ``gx[b, k] = cotangents[b, k]^T
@@ -244,10 +244,17 @@ class _FlowBase(nn.Module):
         from ``x``, in its units), and raise the step count until it is small.  (Measured in float64 on a small flow: gap to
         ``w^T flow_jacobian`` 6e-11 with 16 rk4 steps, 9e-3 with 128 euler steps.)
 
+        ``adjoint="discrete"`` (keyword only) takes the exact discrete adjoint instead (``odeint.solve_pull_discrete``): a
+        forward launch records the stage state of every evaluation row and a second one runs the transposed row program
+        backwards over them, so ``gx`` and ``gc`` are the transpose of what ``flow_jvp`` differentiates up to rounding at ANY
+        step count -- the gradient of the function that is actually evaluated.  ``x_out`` is then the record launch's state
+        (bitwise the fixed-grid solve's, as on the default route), nothing is retraced (``return_retrace`` raises), and
+        the record costs ``n_evals * B * D`` floats of device memory per piece of rows.  Any other value raises ValueError.
+
         No parameter gradients, no torch.autograd integration (the call runs under ``no_grad``), no adaptive step
-        control, no exact discrete adjoint: see ``odeint.solve_pull``."""
+        control: see ``odeint.solve_pull`` and ``odeint.solve_pull_discrete``."""
         t_span, kw = self._push_args(x, conditional, direction)
-        return odeint.solve_pull(self, x, t_span, method, options, cotangents, return_retrace=return_retrace, **kw)
+        return odeint.solve_pull_by(adjoint, self, x, t_span, method, options, cotangents, return_retrace=return_retrace, **kw)
 
     # -- the public methods' bodies, written once (``conditional=None``: the unconditional flow) -----------------------------
     def compute_linear_velocity_field(self, x0, xT, t):

@@ -306,6 +306,64 @@ class FusedNet:
             _native.plan_words(plan, stage_slots), want)
         return y, gx, (gc if want else None), status
 
+    def _pull_cond(self, cond: Optional[torch.Tensor], B: int, dev) -> Optional[torch.Tensor]:
+        """``cond`` as the record and discrete-adjoint launches take it: [B, cond_dim] fp32 on ``dev``, None without inputs."""
+        if self.cond_dim == 0:
+            return None
+        if cond is None:
+            raise ValueError("this network has conditional inputs; `conditional` is required")
+        cond = f32_on(cond, dev)
+        if cond.dim() != 2 or cond.shape != (B, self.cond_dim):
+            raise ValueError(f"conditional must be [batch, {self.cond_dim}], got {tuple(cond.shape)}")
+        return cond
+
+    def record(self, x: torch.Tensor, etab: torch.Tensor, cond: Optional[torch.Tensor] = None, stage_slots: int = 0,
+               in_shift=None, in_scale=None, out_scale=None, out_shift=None):
+        """The fused fixed-grid solve of the state on the record unit (the sibling of ``pull_plan``'s; ``etab`` has ITS width
+        and holds the rows of the FORWARD span) that writes every stage state down.  Returns (x_out [B, D], record
+        [n_evals, B, D], status [1]): ``record[e, b]`` = the stage state y_e of row e in the integrated state's units --
+        what ``pullback_discrete`` reads backwards."""
+        if not x.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {x.device}); there is no CPU fallback")
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(x.shape)}")
+        dev = x.device
+        plan = self.pull_plan()
+        cond = self._pull_cond(cond, x.shape[0], dev)
+        return torch.ops.flowfusion_amd.mlp_ode_record(
+            f32_on(x, dev), cond, self.wpack(dev, MODE_HUTCH, plan), f32_on(etab, dev),
+            f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots))
+
+    def pullback_discrete(self, record: torch.Tensor, etab: torch.Tensor, cotangents: torch.Tensor,
+                          cond: Optional[torch.Tensor] = None, want_cond: bool = False, in_shift=None, in_scale=None,
+                          out_scale=None, out_shift=None, stage_slots: int = 0):
+        """The exact discrete adjoint on the discrete-adjoint unit (the sibling of ``pull_plan``'s): the transposed row program
+        of the FORWARD rows ``etab``, run backwards over ``record`` (``record`` of the same table, conditional and maps --
+        the maps here are the FORWARD solve's, unlike ``pullback``'s).  Returns (gx [B, K, D], gc [B, K, C] or None, status
+        [1]): ``gx[b, k] = cotangents[b, k]^T d x_out[b] / d x[b]`` and ``gc`` likewise for ``cond`` as given -- the transpose
+        of ``pushforward``'s derivative."""
+        if not record.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {record.device}); there is no CPU fallback")
+        if record.dim() != 3 or record.shape[2] != self.dim or record.shape[0] != etab.shape[0]:
+            raise ValueError(f"expected a [{int(etab.shape[0])}, batch, {self.dim}] record, got {tuple(record.shape)}")
+        dev = record.device
+        plan = self.pull_plan()
+        B = int(record.shape[1])
+        cond = self._pull_cond(cond, B, dev)
+        if cotangents is None or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, self.dim):
+            raise ValueError(f"pullback_discrete: cotangents [batch, K, {self.dim}]")
+        want = bool(want_cond and self.cond_dim > 0)
+        gx, gc, status = torch.ops.flowfusion_amd.mlp_ode_pull_discrete(
+            f32_on(record, dev), cond, f32_on(cotangents, dev).contiguous(), self.wpack(dev, MODE_HUTCH, plan), f32_on(etab, dev),
+            f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots), want)
+        return gx, (gc if want else None), status
+
     def vjp_products(self, x: torch.Tensor, etab: torch.Tensor, seeds: torch.Tensor, per_row: bool = False,
                      cond: Optional[torch.Tensor] = None, stage_slots: int = 0, in_shift=None, in_scale=None, out_scale=None,
                      out_shift=None):

@@ -400,30 +400,9 @@ def solve_push_jacobian(front, x, t_span, method, options, cond=None, tangent_ga
     return y, Jx, Jc
 
 
-def solve_pull(front, x, t_span, method, options, cotangents, cond=None, in_shift=None, in_scale=None, out_scale=None,
-               out_shift=None, tangent_gain=None, cond_tangent_scale=None, return_retrace=False):
-    """Flow-map pull-backs (extension): K cotangents per sample pulled back through the fixed-grid solve of ``solve`` in
-    MODE_STATE, by the CONTINUOUS adjoint, as torchdiffeq's ``odeint_adjoint`` does.  Returns ``(y [B, D], gx [B, K, D],
-    gc [B, K, C] or None)`` -- and ``retrace [B]`` with ``return_retrace`` -- where ``gx[b, k] = cotangents[b, k]^T d y[b] /
-    d x[b]`` and ``gc`` likewise for ``cond`` (times ``1 / cond_tangent_scale``: the caller's raw conditional).
-
-    Two launches per piece of rows: the ordinary state-only solve ``x -> y`` (``y`` is bitwise what ``solve`` returns), then
-    ONE launch of a pull-back unit (FusedNet.pullback) over the REVERSED span, same method and step, on the augmented state
-    ``[y | alpha_k | gamma_k]`` from ``[y, w_k, 0]``: ``dalpha/dt = -(df/dy)^T alpha``, ``dgamma/dt = -(df/dc)^T alpha``.
-    This is NOT the transpose of the discrete map ``solve_push`` differentiates: the two differ by the discretisation
-    error of the method (order p in the step), and the backward sweep retraces ``y`` instead of storing it.
-    ``retrace[b] = max_d |y_back - x|`` in the units of ``x`` says how far the retraced trajectory ended from where the
-    forward one began: read it, use rk4 or better, and raise the step count until it is small.  (An Euler sweep of a VP
-    score model with 128 steps retraces to 0.4 and its gradient is off by 0.7; rk4 with 128 steps is off by 4e-6.)
-
-    The affine maps are those of the forward solve, as in ``solve_push``; ``tangent_gain``: the solve starts from
-    ``x * tangent_gain`` (a VE model's sigma_max), and ``gx`` carries the factor.  Rows are cut so that a [rows, K, D]
-    device buffer stays under ``PROBE_BUFFER_FLOATS`` floats; rows are independent, so any cut gives bitwise the same.
-
-    Refused with ValueError before the device is touched: adaptive methods, ``grid_constructor`` / ``perturb``, K > 15,
-    shapes that do not match, ``precision`` other than f32.  NotImplementedError: a network outside the pull-back units
-    (``_native.PULL_ENVELOPE``), or a ``model=`` module.  Out of scope: parameter gradients and torch.autograd
-    integration, the exact discrete adjoint (checkpointed states), adaptive control, sharded entry points."""
+def _pull_checks(front, x, method, options, cotangents, cond):
+    """What ``solve_pull`` and ``solve_pull_discrete`` refuse, in one order and with one set of messages, before the device is
+    touched; returns ``(net, plan, B, D, K, C)``."""
     if method in solvers.ALL_ADAPTIVE or method in solvers.ADAPTIVE_METHODS:
         raise ValueError(f"flow-map pull-backs with the adaptive method={method!r}: the adjoint sweep runs over the reversed "
                          "fixed grid of the forward solve; use method=\"rk4\" / \"dopri5_fixed\" with "
@@ -464,6 +443,34 @@ def solve_pull(front, x, t_span, method, options, cotangents, cond=None, in_shif
         raise ValueError("flow-map pull-backs: this model has no conditional inputs")
     require_fp32(front, x, cond, cotangents, what="a flow-map pull-back solve")
     _need_gpu(x)
+    return net, plan, B, D, K, C
+
+
+def solve_pull(front, x, t_span, method, options, cotangents, cond=None, in_shift=None, in_scale=None, out_scale=None,
+               out_shift=None, tangent_gain=None, cond_tangent_scale=None, return_retrace=False):
+    """Flow-map pull-backs (extension): K cotangents per sample pulled back through the fixed-grid solve of ``solve`` in
+    MODE_STATE, by the CONTINUOUS adjoint, as torchdiffeq's ``odeint_adjoint`` does.  Returns ``(y [B, D], gx [B, K, D],
+    gc [B, K, C] or None)`` -- and ``retrace [B]`` with ``return_retrace`` -- where ``gx[b, k] = cotangents[b, k]^T d y[b] /
+    d x[b]`` and ``gc`` likewise for ``cond`` (times ``1 / cond_tangent_scale``: the caller's raw conditional).
+
+    Two launches per piece of rows: the ordinary state-only solve ``x -> y`` (``y`` is bitwise what ``solve`` returns), then
+    ONE launch of a pull-back unit (FusedNet.pullback) over the REVERSED span, same method and step, on the augmented state
+    ``[y | alpha_k | gamma_k]`` from ``[y, w_k, 0]``: ``dalpha/dt = -(df/dy)^T alpha``, ``dgamma/dt = -(df/dc)^T alpha``.
+    This is NOT the transpose of the discrete map ``solve_push`` differentiates: the two differ by the discretisation
+    error of the method (order p in the step), and the backward sweep retraces ``y`` instead of storing it.
+    ``retrace[b] = max_d |y_back - x|`` in the units of ``x`` says how far the retraced trajectory ended from where the
+    forward one began: read it, use rk4 or better, and raise the step count until it is small.  (An Euler sweep of a VP
+    score model with 128 steps retraces to 0.4 and its gradient is off by 0.7; rk4 with 128 steps is off by 4e-6.)
+
+    The affine maps are those of the forward solve, as in ``solve_push``; ``tangent_gain``: the solve starts from
+    ``x * tangent_gain`` (a VE model's sigma_max), and ``gx`` carries the factor.  Rows are cut so that a [rows, K, D]
+    device buffer stays under ``PROBE_BUFFER_FLOATS`` floats; rows are independent, so any cut gives bitwise the same.
+
+    Refused with ValueError before the device is touched: adaptive methods, ``grid_constructor`` / ``perturb``, K > 15,
+    shapes that do not match, ``precision`` other than f32.  NotImplementedError: a network outside the pull-back units
+    (``_native.PULL_ENVELOPE``), or a ``model=`` module.  Out of scope: parameter gradients and torch.autograd
+    integration, adaptive control, sharded entry points.  The exact discrete adjoint is ``solve_pull_discrete``."""
+    net, plan, B, D, K, C = _pull_checks(front, x, method, options, cotangents, cond)
     x0 = x if tangent_gain is None else x * tangent_gain
     y, _ = solve(front, x0, t_span, method, options, MODE_STATE, 0.0, 0.0, cond=cond, in_shift=in_shift, in_scale=in_scale,
                  out_scale=out_scale, out_shift=out_shift)
@@ -495,6 +502,80 @@ def solve_pull(front, x, t_span, method, options, cotangents, cond=None, in_shif
     if not return_retrace:
         return y, gx, gc
     return y, gx, gc, (yb - x).abs().amax(dim=1)
+
+
+def discrete_piece_rows(B, K, E, D):
+    """Rows per piece of ``solve_pull_discrete``: neither a [rows, K, D] buffer nor the [E, rows, D] record reaches
+    ``PROBE_BUFFER_FLOATS`` floats.  Even pieces, whole tiles where the bound allows: a long piece and a short one would each
+    end on a part-filled round of wavefronts (at 2^16 rows of a 400-row record, 6 + 3 rounds of the chip where two halves
+    take 4 + 4)."""
+    most = max(1, (PROBE_BUFFER_FLOATS - 1) // (max(K, E, 1) * D))
+    rows = -(-max(B, 1) // -(-max(B, 1) // most))
+    return min(most, -(-rows // 16) * 16) if most >= 16 else rows
+
+
+def solve_pull_discrete(front, x, t_span, method, options, cotangents, cond=None, in_shift=None, in_scale=None, out_scale=None,
+                        out_shift=None, tangent_gain=None, cond_tangent_scale=None):
+    """Flow-map pull-backs by the exact DISCRETE adjoint (extension): K cotangents per sample pulled back through the
+    fixed-grid solve of ``solve`` in MODE_STATE by the transpose of the map that solve applies -- the transpose of what
+    ``solve_push`` differentiates, so ``<w, solve_push(v)> = <solve_pull_discrete(w), v>`` up to rounding at ANY step
+    count, one Euler step included.  Returns ``(y [B, D], gx [B, K, D], gc [B, K, C] or None)`` as ``solve_pull`` does.
+
+    Two launches per piece of rows over the SAME forward table: the record unit (FusedNet.record) integrates ``x -> y`` and
+    writes the stage state of every evaluation row down, [E, rows, D]; the discrete-adjoint unit
+    (FusedNet.pullback_discrete) runs the transposed row program from the last row to the first on those states.  Nothing
+    is retraced: there is no ``retrace`` to read.  ``y`` is the record launch's state: it does not depend on K, on the
+    cotangents or on the cut, and is bitwise what ``solve`` returns (the record unit runs the state kernels' fp32 chains in
+    their order).
+
+    The affine maps, ``tangent_gain`` and ``cond_tangent_scale`` are as in ``solve_pull``.  Rows are cut so that neither a
+    [rows, K, D] buffer nor the [E, rows, D] record reaches ``PROBE_BUFFER_FLOATS`` floats; rows are independent, so any
+    cut gives bitwise the same.  Refusals: ``solve_pull``'s, with its messages.  Out of scope: parameter gradients and
+    torch.autograd integration, adaptive control, ``grid_constructor`` grids, sharded entry points."""
+    net, plan, B, D, K, C = _pull_checks(front, x, method, options, cotangents, cond)
+    x0 = x if tangent_gain is None else x * tangent_gain
+    tab = solvers.plan_ode(t_span, method, options)          # (rows of a fixed-grid ODE method: none carries a noise flag)
+    width = int(plan.width)
+    key = ("pull_discrete", tuple(float(v) for v in torch.as_tensor(t_span)), method,
+           repr(sorted((options or {}).items()))) + front._schedule_key()
+    table = net.cached_table(key, x.device, lambda: solvers.build_table(tab, *front._host_schedule()(tab.t_eval), width))
+    E = max(1, int(table.shape[0]))
+    rows = discrete_piece_rows(B, K, E, D)
+    pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    slots = solvers.resolve_method(method).stages
+    ys, gxs, gcs = [], [], []
+    for r0, r1 in pieces:
+        maps = dict(in_shift=in_shift, in_scale=in_scale, out_scale=out_scale, out_shift=out_shift)
+        yp, rec, _ = net.record(cut(x0, r0, r1), table, cond=cut(cond, r0, r1), stage_slots=slots, **maps)
+        gx, gc, _ = net.pullback_discrete(rec, table, cut(cotangents, r0, r1), cond=cut(cond, r0, r1), want_cond=C > 0,
+                                          stage_slots=slots, **maps)
+        del rec
+        ys.append(yp)
+        gxs.append(gx)
+        gcs.append(gc)
+    y, gx = (ys[0], gxs[0]) if whole else (torch.cat(ys), torch.cat(gxs))
+    gc = None if C == 0 else (gcs[0] if whole else torch.cat(gcs))
+    if tangent_gain is not None:
+        gx = gx * tangent_gain
+    if cond_tangent_scale is not None and gc is not None:
+        gc = gc / cond_tangent_scale
+    return y, gx, gc
+
+
+def solve_pull_by(adjoint, front, x, t_span, method, options, cotangents, return_retrace=False, **kw):
+    """``flow_vjp``'s choice of route: ``adjoint="continuous"`` is ``solve_pull``, ``"discrete"`` ``solve_pull_discrete``
+    (which retraces nothing: ``return_retrace`` raises); anything else raises ValueError."""
+    if adjoint == "continuous":
+        return solve_pull(front, x, t_span, method, options, cotangents, return_retrace=return_retrace, **kw)
+    if adjoint != "discrete":
+        raise ValueError(f"flow-map pull-backs: adjoint={adjoint!r}; \"continuous\" (the adjoint ODE over the reversed grid) or "
+                         "\"discrete\" (the transpose of the discrete solver map, from recorded stage states)")
+    if return_retrace:
+        raise ValueError("flow-map pull-backs: return_retrace with adjoint=\"discrete\": the discrete adjoint reads recorded "
+                         "stage states and retraces nothing")
+    return solve_pull_discrete(front, x, t_span, method, options, cotangents, **kw)
 
 
 def solve_leapfrog(front, x, grid, cond=None):

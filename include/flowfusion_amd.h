@@ -416,6 +416,49 @@ const char* ff_vjp_kernel_name(int index);
 int ff_mlp_ode_launch_vjp(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* seed_in, int64_t seed_row_stride,
                           float* prod_out /* [n_evals, batch, K, dim] */, void* hip_stream);
 
+/* ---- the exact discrete adjoint of a fixed-grid solve, from recorded stage states ----------------------------------------
+ * ff_mlp_ode_launch_pull integrates the CONTINUOUS adjoint; it is not the transpose of the map the forward kernels apply.  The
+ * two units of csrc/ff_mlp_dadj.hpp, one sibling of each per pull-back unit, compute that transpose.  The forward solve is a
+ * program over the rows e = 0 .. n_evals - 1 of an ordinary table,
+ *     y_e = x + sum_s cin_e[s] k[s];  r_e = a_e y_e + b_e NET(y_e, c);  k[slot_e] = r_e;  FF_ROW_STEP_END: x += sum_s cout_e[s] k[s]
+ * and its transpose runs the SAME table from the last row to the first on adjoint slots; it needs y_e of every row.
+ *
+ * ff_mlp_ode_launch_record(plan, args, record_out, stream): `plan` is a PULL plan and args->wpack its two packs
+ * (ff_mlp_pull_wpack); args as for a state-only ff_mlp_ode_launch (FF_MODE_STATE).  Integrates the state (stage slots, the
+ * affine maps, args->x_out, args->status) on one wavefront per tile of plan->tile samples and stores, at every row,
+ *     record_out[(e * batch + b) * dim + d] = y_e[d]           in the integrated state's units (after the input map)
+ * ff_mlp_record_floats(batch, n_evals, dim) floats of DEVICE memory.  LDS = stage_slots * dregs * 256 bytes.
+ *
+ * ff_mlp_ode_launch_pull_discrete(plan, args, record_in, cotangent_in, cot_x_out, cot_cond_out, stream): args is the FORWARD
+ * launch's -- same table, same cond, same affine maps -- with args->mode == FF_MODE_HUTCH and K = args->tangent_count;
+ * args->x_in and args->x_out are ignored.  Cotangents are taken in the units of the forward x_out (times out_scale) and handed
+ * back in the units of the forward x_in (over in_scale): cot_x_out[b][k] = w_k^T d x_out / d x_in of the discrete map, exactly,
+ * cot_cond_out[b][k] = w_k^T d x_out / d cond.  A tile holds tile / (1 + K) samples; LDS = stage_slots * dregs * 256 bytes of
+ * adjoint slots and the stash of ff_mlp_ode_launch_pull -- never more than that launch's.
+ *
+ * Both refuse, before anything is enqueued:
+ *     a plan that is not a pull plan                                                                   FF_ERR_BADARG
+ *     record: a mode other than FF_MODE_STATE; discrete: other than FF_MODE_HUTCH, K < 1, K > tile - 1 FF_ERR_BADARG
+ *     record_out / record_in, cotangent_in or cot_x_out NULL; cot_cond_out with cond_dim == 0          FF_ERR_BADARG
+ *     noise, k1_in, kl1_in, dlogp_in, jac_out, dlogp_out or probe set, n_aux > 0                       FF_ERR_BADARG
+ *     a depth whose stash does not fit the LDS at this K                                               FF_ERR_UNSUPPORTED
+ * The kernel ids FF_REC_KERNEL_BASE + index and FF_DADJ_KERNEL_BASE + index name the units (index = plan->kernel_id -
+ * FF_PULL_KERNEL_BASE); no plan carries them.  FF_STATUS_BAD_SLOT: a row names a slot beyond args->stage_slots (it stores
+ * nothing forward and contributes nothing backward).  FF_STATUS_NOISE_ROW: the table holds a noise row; the record launch
+ * leaves the noise out, so the results belong to another map. */
+#define FF_REC_KERNEL_BASE 0x70000
+#define FF_DADJ_KERNEL_BASE 0x80000
+int ff_rec_kernel_count(void);
+const char* ff_rec_kernel_name(int index);
+int ff_dadj_kernel_count(void);
+const char* ff_dadj_kernel_name(int index);
+size_t ff_mlp_record_floats(int64_t batch, int32_t n_evals, int32_t dim);
+int ff_mlp_ode_launch_record(const ff_mlp_plan_t* plan, const ff_ode_args* args, float* record_out /* [n_evals, batch, dim] */,
+                             void* hip_stream);
+int ff_mlp_ode_launch_pull_discrete(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* record_in,
+                                    const float* cotangent_in /* [batch, K, dim] */, float* cot_x_out /* [batch, K, dim] */,
+                                    float* cot_cond_out /* [batch, K, cond_dim] or NULL */, void* hip_stream);
+
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
  * query, so that callers, benchmarks and tests can name the kernel that ran without timing it.  Honours FF_COOP /
