@@ -82,9 +82,10 @@ def per_sample(prod):
 
 
 # ---- the raw launch, between guard words -------------------------------------------------------------------------------------
-def raw_vjp(sm, plan_rows, method, x, seeds, per_row, cond=None, noise_row=None, status_is=0):
+def raw_vjp(sm, plan_rows, method, x, seeds, per_row, cond=None, noise_row=None, status_is=0, slots=None):
     """ff_mlp_ode_launch_vjp on buffers of the test's own over the forward table of ``plan_rows``: (x_out [B, D],
-    prod [n, B, K, D], the kernel's name), guards checked.  ``noise_row``: that row gets the FF_ROW_NOISE flag."""
+    prod [n, B, K, D], the kernel's name), guards checked.  ``noise_row``: that row gets the FF_ROW_NOISE flag;
+    ``slots``: the stage slots kept in LDS (default: the method's stages)."""
     net = sm.to(DEV)._net()
     plan = net.pull_plan()
     table = solvers.build_table(plan_rows, *sm._host_schedule()(plan_rows.t_eval), int(plan.width))
@@ -102,7 +103,7 @@ def raw_vjp(sm, plan_rows, method, x, seeds, per_row, cond=None, noise_row=None,
     a.x_in, a.x_out, a.wpack, a.etab, a.status = x.data_ptr(), xo.data_ptr() + 4 * GUARD, wp.data_ptr(), table.data_ptr(), status.data_ptr()
     a.cond = 0 if cond is None else cond.data_ptr()
     a.batch, a.n_evals, a.tangent_count, a.mode = B, n, K, _native.MODE_HUTCH
-    a.stage_slots = solvers.resolve_method(method).stages
+    a.stage_slots = solvers.resolve_method(method).stages if slots is None else slots
     rc = _native.lib().ff_mlp_ode_launch_vjp(ctypes.byref(plan), ctypes.byref(a), seeds.data_ptr(), B * K * D if per_row else 0,
                                              prod.data_ptr() + 4 * GUARD, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == _native.FF_OK, rc

@@ -48,10 +48,12 @@ def forward_state(front, x_in, t_span, method, opts, cond, maps):
     return y
 
 
-def raw_pull(front, y, t_span, method, options, cotangents, cond=None, maps=None, want_cond=True, noise_row=None, status_is=0):
+def raw_pull(front, y, t_span, method, options, cotangents, cond=None, maps=None, want_cond=True, noise_row=None, status_is=0,
+             slots=None):
     """ff_mlp_ode_launch_pull on buffers of the test's own, over the REVERSED span of the solve that gave ``y``, with the
     forward solve's ``maps`` turned round: (retraced state [B, D], cot_x [B, K, D], cot_cond [B, K, C] or None), guards
-    checked.  ``noise_row``: that row of the table gets the FF_ROW_NOISE flag; ``status_is``: what the status word must read."""
+    checked.  ``noise_row``: that row of the table gets the FF_ROW_NOISE flag; ``status_is``: what the status word must read;
+    ``slots``: the stage slots kept in LDS (default: the method's stages)."""
     net = front.to(DEV)._net()
     plan = net.pull_plan()
     tab = solvers.plan_ode(torch.flip(t_span, dims=(0,)), method, options)
@@ -74,7 +76,7 @@ def raw_pull(front, y, t_span, method, options, cotangents, cond=None, maps=None
     for name, t in keep.items():
         setattr(a, name, t.data_ptr())
     a.batch, a.n_evals, a.tangent_count, a.mode = B, table.shape[0], K, _native.MODE_HUTCH
-    a.stage_slots = solvers.resolve_method(method).stages
+    a.stage_slots = solvers.resolve_method(method).stages if slots is None else slots
     rc = _native.lib().ff_mlp_ode_launch_pull(ctypes.byref(plan), ctypes.byref(a), w.data_ptr(), gx.data_ptr() + 4 * GUARD,
                                               0 if gc is None else gc.data_ptr() + 4 * GUARD,
                                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))

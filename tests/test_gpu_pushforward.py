@@ -25,6 +25,7 @@ from flowfusion_amd import _native, odeint, solvers
 from flowfusion_amd import diffusion as Dm
 from flowfusion_amd import flow as Fm
 from tests import _pushforward_ref as R
+from tests._deep_models import apply_gain
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -41,17 +42,22 @@ def _need_gpu(built_library):
 
 
 # ---- models and their references ---------------------------------------------------------------------------------------------
-def make_front(kind, D, C, width, nh, seed=5, affine=False):
-    """(front end on the CPU, SolverMap keywords) of a seeded model: kind in vp / ve / subvp (ScoreModel) or flow."""
+def make_front(kind, D, C, width, nh, seed=5, affine=False, gain=1.0):
+    """(front end on the CPU, SolverMap keywords) of a seeded model: kind in vp / ve / subvp (ScoreModel) or flow.  ``width``: one
+    width for all ``nh`` hidden layers, or the sequence of their widths.  ``gain`` multiplies the hidden-to-hidden weight
+    matrices in place before the reference reads the parameters (tests/_deep_models.py: at default init a deep stack's
+    Jacobian vanishes); 1.0 leaves the seeded model as it is, bit for bit."""
     torch.manual_seed(seed)
-    units = [width] * nh
+    units = [width] * nh if isinstance(width, int) else list(width)
     if kind == "flow":
         kw = {}
         if affine:
             kw = dict(target_shift=torch.linspace(-1.0, 1.0, D), target_scale=torch.linspace(0.5, 2.0, D))
         f = Fm.ODEFlow(D, units, **kw) if C == 0 else Fm.ConditionalODEFlow(D, C, units, **kw)
+        apply_gain(f._linears(), gain)
         return f.eval(), dict(kind="flow", params=R.flow_params(f))
     m = Dm.MLP(n_dimensions=D, n_conditionals=C, embedding_dimensions=8, units=units)
+    apply_gain(list(m.NN), gain)
     sm = Dm.ScoreModel(m, getattr(Dm, SDE[kind])(), no_sigma=False).eval()
     return sm, dict(kind="score", params=R.score_params(m), sde=kind)
 

@@ -18,6 +18,7 @@ from flowfusion_amd import flow as F
 from flowfusion_amd import symplectic as S
 from tests import _emulator as E
 from tests import _pushforward_ref as R
+from tests._deep_models import apply_gain
 
 ROOT = Path(__file__).resolve().parent.parent
 BAD, UNS, OK = _native.FF_ERR_BADARG, _native.FF_ERR_UNSUPPORTED, _native.FF_OK
@@ -248,14 +249,16 @@ def test_seventh_op_is_registered_with_a_fake():
     (1, 0, [32]), (16, 1, [128] * 4), (17, 16, [256]), (32, 0, [256] * 4), (16, 16, [128, 32, 256, 32]), (32, 1, [32]),
     (1, 16, [128, 32, 32, 128]),
 ])
-def test_forward_pack_then_transposed_pack_reproduce_the_vjp_of_the_network(Dn, C, hidden):
+def test_forward_pack_then_transposed_pack_reproduce_the_vjp_of_the_network(Dn, C, hidden, gain=1.0):
     """What the kernel reads, decoded (tests/_emulator.py) and run in float64 the way the kernel runs it: net A from the
     first pack gives the slopes, net B from the second pack -- first layer on [alpha | 0], a multiply by the slope after
     every layer, output rows = the state dimensions and the conditional inputs at the places of net A's registers -- must
-    give J_net^T alpha and (dNET/dc)^T alpha of the network itself (torch.func.vjp)."""
+    give J_net^T alpha and (dNET/dc)^T alpha of the network itself (torch.func.vjp).  ``gain`` (tests/_deep_models.py): the
+    hidden-to-hidden weights times it, for the deep shapes of tests/test_derivative_depth_host.py."""
     torch.manual_seed(Dn * 100 + C)
     sizes = [Dn + C + 3] + list(hidden) + [Dn]                       # first layer input: [3 time columns | x | cond]
     lin = [nn.Linear(a, b) for a, b in zip(sizes[:-1], sizes[1:])]
+    apply_gain(lin, gain)
     x_col0, c_col0 = 3, 3 + Dn
     plan = _native.make_pull_plan(Dn, C, list(hidden))
     pack = _native.pack_weights(plan, [l.weight for l in lin], [l.bias for l in lin], list(hidden), x_col0, c_col0)
