@@ -100,6 +100,7 @@ VJP_KERNEL_BASE = 0x60000                                   # FF_VJP_KERNEL_BASE
 MAX_VJP_SEEDS = 15                                          # seed columns beside the value column of a 16-column tile
 REC_KERNEL_BASE = 0x70000                                   # FF_REC_KERNEL_BASE
 DADJ_KERNEL_BASE = 0x80000                                  # FF_DADJ_KERNEL_BASE
+LGRAD_KERNEL_BASE = 0x90000                                 # FF_LGRAD_KERNEL_BASE
 ADAPT_START, ADAPT_FINISH = 1, 2            # FF_ADAPT_START / FF_ADAPT_FINISH
 ADAPT_ERR_UNDERFLOW, ADAPT_ERR_NONFINITE, ADAPT_ERR_MAXSTEPS = 1, 2, 3
 ADAPT_MAX_PASSES = 8
@@ -303,6 +304,11 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_ode_launch_pull_discrete.restype = ctypes.c_int
     L.ff_mlp_ode_launch_pull_discrete.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_lgrad_kernel_count.restype = ctypes.c_int
+    L.ff_lgrad_kernel_name.restype = ctypes.c_char_p
+    L.ff_lgrad_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_ode_launch_logp_grad.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_logp_grad.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs)] + [ctypes.c_void_p] * 7
     L.ff_mlp_samples_per_workgroup.restype = ctypes.c_int
     L.ff_mlp_samples_per_workgroup.argtypes = [ctypes.POINTER(PlanStruct), ctypes.c_int]
     L.ff_last_hip_error.restype = ctypes.c_int
@@ -1010,14 +1016,15 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
 
 
 def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, vjp=None,
-                record=None, discrete=None, **fields) -> None:
+                record=None, discrete=None, logp_grad=None, **fields) -> None:
     """The one launch of the ten ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
     ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, ff_mlp_ode_launch_push with
     ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, ff_mlp_ode_launch_pull with
     ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``, or ff_mlp_ode_launch_vjp with
     ``vjp = (seeds, seed_row_stride, prod_out [n_evals, B, K, D])``, ff_mlp_ode_launch_record with ``record = record_out
     [n_evals, B, D]``, or ff_mlp_ode_launch_pull_discrete with ``discrete = (record [n_evals, B, D], cotangents [B, K, D],
-    cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``.  ``tensors``: the caller's
+    cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``, or ff_mlp_ode_launch_logp_grad with ``logp_grad = (record, probes
+    [B, D], weight [B] or None, cotangent [B, D], grad_x_out [B, D], grad_cond_out [B, C] or None)``.  ``tensors``: the caller's
     tensors (or None) by ff_ode_args field name, each checked by ``_chk``; ``fields``: the scalar fields and the addresses
     of what the op allocated itself.  A field named in neither stays zero."""
     a = OdeArgs(**fields)
@@ -1030,6 +1037,12 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             what = "ff_mlp_ode_launch_record"
             rc = lib().ff_mlp_ode_launch_record(ctypes.byref(p), ctypes.byref(a), _chk(record, "record_out", dev),
                                                 ctypes.c_void_p(stream))
+        elif logp_grad is not None:
+            what = "ff_mlp_ode_launch_logp_grad"
+            rc = lib().ff_mlp_ode_launch_logp_grad(ctypes.byref(p), ctypes.byref(a), _chk(logp_grad[0], "record", dev),
+                                                   _chk(logp_grad[1], "probes", dev), _chk(logp_grad[2], "weight", dev),
+                                                   _chk(logp_grad[3], "cotangent", dev), _chk(logp_grad[4], "grad_x_out", dev),
+                                                   _chk(logp_grad[5], "grad_cond_out", dev), ctypes.c_void_p(stream))
         elif discrete is not None:
             what = "ff_mlp_ode_launch_pull_discrete"
             rc = lib().ff_mlp_ode_launch_pull_discrete(ctypes.byref(p), ctypes.byref(a), _chk(discrete[0], "record", dev),
@@ -1369,6 +1382,55 @@ def _(record, cond, cotangents, wpack, etab, in_shift, in_scale, out_scale, out_
     C = _plan_from_words(plan).cond_dim if want_cond else 0
     return (record.new_empty(B, K, record.shape[2]), record.new_empty(B, K, C),
             torch.empty(1, dtype=torch.int32, device=record.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_logp_grad", mutates_args=())
+def mlp_ode_logp_grad(record: torch.Tensor, cond: Optional[torch.Tensor], probes: torch.Tensor, weight: Optional[torch.Tensor],
+                      cotangent: torch.Tensor, wpack: torch.Tensor, etab: torch.Tensor, in_shift: Optional[torch.Tensor],
+                      in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor], out_shift: Optional[torch.Tensor],
+                      plan: List[int], want_cond: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The gradient of a fixed-grid Hutchinson log-density (ff_mlp_ode_launch_logp_grad): the transposed row program of the
+    FORWARD rows ``etab`` with the divergence integral in it, run backwards over ``record`` [n_evals, B, D] (``mlp_ode_record``
+    of the same table, cond and maps).  ``probes`` [B, D]: each row's probe; ``weight`` [B] or None (= 1): the cotangent of its
+    divergence integral; ``cotangent`` [B, D]: that of its final state.  Returns (grad_x [B, D], grad_cond [B, C] -- [B, 0]
+    unless ``want_cond`` --, status [1])."""
+    if not record.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_logp_grad needs tensors on the GPU (there is no CPU path)")
+    dev = record.device
+    p = _plan_from_words(plan)
+    n = int(etab.shape[0])
+    if record.dim() != 3 or record.shape[0] != n or record.shape[2] != p.dim:
+        raise RuntimeError(f"record has shape {tuple(record.shape)}, expected [{n}, B, {p.dim}]")
+    B, D = int(record.shape[1]), int(record.shape[2])
+    for name, t in (("probes", probes), ("cotangent", cotangent)):
+        if tuple(t.shape) != (B, D):
+            raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected {(B, D)}")
+    if weight is not None and tuple(weight.shape) != (B,):
+        raise RuntimeError(f"weight has shape {tuple(weight.shape)}, expected {(B,)}")
+    C = int(p.cond_dim) if want_cond else 0
+    if want_cond and p.cond_dim == 0:
+        raise RuntimeError("want_cond on a plan without conditional inputs")
+    gx = torch.empty(B, D, dtype=torch.float32, device=dev)
+    gc = torch.empty(B, C, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return gx, gc, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"cond": cond, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                logp_grad=(record, probes, weight, cotangent, gx, gc if want_cond else None), status=status.data_ptr(), batch=B,
+                n_evals=n, mode=MODE_HUTCH, tangent_count=1, stage_slots=_slots_hint(plan))
+    return gx, gc, status
+
+
+@mlp_ode_logp_grad.register_fake
+def _(record, cond, probes, weight, cotangent, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, want_cond):
+    B = record.shape[1]
+    C = _plan_from_words(plan).cond_dim if want_cond else 0
+    return (record.new_empty(B, record.shape[2]), record.new_empty(B, C), torch.empty(1, dtype=torch.int32, device=record.device))
 
 
 @torch.library.custom_op("flowfusion_amd::mlp_ode_step", mutates_args=())

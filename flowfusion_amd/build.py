@@ -169,6 +169,14 @@ def _dadj_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_dadj_m{tile}_h{h}_d{d}_c{c}"
 
 
+# Log-density gradient units (ff_mlp_lgrad.hpp; ff_mlp_ode_launch_logp_grad): the transposed row program of the discrete-adjoint
+# unit with the Hutchinson divergence integral in it, reverse over forward mode -- log_prob_grad.  One sibling per pull-back unit,
+# same shape and the same two weight packs: a pull plan launches entry i of g_lgrad_kernels (FF_LGRAD_KERNEL_BASE names them, no
+# plan carries it).
+def _lgrad_name(tile, h, d, c, wps, ring) -> str:
+    return f"mlp_lgrad_m{tile}_h{h}_d{d}_c{c}"
+
+
 # split-precision family (opt-in `precision=`): (hidden layers, TANGENTS, bf16 parts per operand: 3 = FF_PREC_BF16X3,
 # 2 = FF_PREC_BF16X2, 16-dimension tiles of the state: 1 = dim <= 16; 2 = dim <= 32 (two-part kernels only), on-chip
 # width: 256, or 128 for networks up to 128 wide).  TANGENTS: 0 state only, 1 Hutchinson column pairs, 2 exact trace.
@@ -313,7 +321,10 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     dadjs = [(_rec_name(*i), "ff_mlp_dadj.hpp", f"mlp_rec_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES] + \
             [(_dadj_name(*i), "ff_mlp_dadj.hpp", f"mlp_dadj_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
     files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_dadj_registry.h")) for name, header, expr in dadjs]
-    units = units + pulls + vjps + dadjs
+    # the log-density gradient siblings
+    lgrads = [(_lgrad_name(*i), "ff_mlp_lgrad.hpp", f"mlp_lgrad_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
+    files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_lgrad_registry.h")) for name, header, expr in lgrads]
+    units = units + pulls + vjps + dadjs + lgrads
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
     fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
@@ -355,11 +366,15 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     dadj_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_dadj_name(*i)}, "{_dadj_name(*i)}"}}' for i in PULL_INSTANCES
     ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the discrete-adjoint units)
+    lgrad_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_lgrad_name(*i)}, "{_lgrad_name(*i)}"}}' for i in PULL_INSTANCES
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the log-density gradient units)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
 #include "ff_vjp_registry.h"
 #include "ff_dadj_registry.h"
+#include "ff_lgrad_registry.h"
 namespace ff {{
 {decls}
 const KernelEntry g_kernels[] = {{
@@ -394,6 +409,10 @@ const PullKernelEntry g_dadj_kernels[] = {{
 {dadj_rows}
 }};
 const int g_n_dadj_kernels = {len(PULL_INSTANCES)};
+const PullKernelEntry g_lgrad_kernels[] = {{
+{lgrad_rows}
+}};
+const int g_n_lgrad_kernels = {len(PULL_INSTANCES)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -424,7 +443,7 @@ def _cost(src: Path) -> float:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
     if n.startswith("mlp_push_"):
         return 16 if "_h256_" in n else 6
-    if n.startswith("mlp_pull_") or n.startswith("mlp_vjp_") or n.startswith("mlp_dadj_"):
+    if n.startswith("mlp_pull_") or n.startswith("mlp_vjp_") or n.startswith("mlp_dadj_") or n.startswith("mlp_lgrad_"):
         return 40 if "_h256_" in n else 15
     if n.startswith("mlp_rec_"):
         return 16 if "_h256_" in n else 6

@@ -10,6 +10,7 @@
 #include "ff_pull_registry.h"
 #include "ff_vjp_registry.h"
 #include "ff_dadj_registry.h"
+#include "ff_lgrad_registry.h"
 #include "ff_adapt_logic.h"
 
 static_assert(FF_MAX_SLOTS == ff::kSlots, "slot count mismatch between header and kernel");
@@ -183,6 +184,7 @@ struct LaunchDesc {
     const ff::SplitKernelEntry* split;      // kSplit: the entry (that family keeps its own launch geometry, launch_split)
     bool products;             // kPull: the launch runs the plan's products sibling (ff_mlp_ode_launch_vjp sets it: ff_mlp_vjp.hpp)
     bool record, discrete;     // kPull: the plan's record / discrete-adjoint sibling (ff_mlp_ode_launch_record, _pull_discrete: ff_mlp_dadj.hpp)
+    bool logp_grad;            // kPull: the plan's log-density gradient sibling (ff_mlp_ode_launch_logp_grad: ff_mlp_lgrad.hpp)
 };
 
 static bool shape_ok(const ff_mlp_plan_t* p, int tile, int H, int dregs, int cregs)
@@ -306,6 +308,14 @@ static size_t rec_lds_bytes(const ff_mlp_plan_t* p, int n_slots = ff::kSlots)
     return (size_t)n_slots * (p->dregs / 4) * 64 * 16;
 }
 
+// The same of a log-density gradient tile (ff_mlp_lgrad.hpp): adjoint slots of dregs words per lane, then two words per hidden
+// unit for each of its tile / 2 rows.
+static size_t lgrad_lds_bytes(const ff_mlp_plan_t* p, int n_slots = ff::kSlots)
+{
+    const size_t slots = (size_t)n_slots * (p->dregs / 4) * 64 * 16;
+    return slots + (size_t)(p->tile / 2) * p->n_hidden * p->width * 2 * 4;
+}
+
 extern "C" const char* ff_plan_kernel_name(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
@@ -404,6 +414,20 @@ extern "C" int ff_dadj_kernel_count(void) { return n_dadj_kernels(); }
 extern "C" const char* ff_dadj_kernel_name(int index)
 {
     return index >= 0 && index < n_dadj_kernels() ? ff::g_dadj_kernels[index].name : NULL;
+}
+
+// The log-density gradient table: weak for the same reason.
+namespace ff {
+extern const PullKernelEntry g_lgrad_kernels[] __attribute__((weak));
+extern const int g_n_lgrad_kernels __attribute__((weak));
+}
+static int n_lgrad_kernels() { return &ff::g_n_lgrad_kernels ? ff::g_n_lgrad_kernels : 0; }
+
+extern "C" int ff_lgrad_kernel_count(void) { return n_lgrad_kernels(); }
+
+extern "C" const char* ff_lgrad_kernel_name(int index)
+{
+    return index >= 0 && index < n_lgrad_kernels() ? ff::g_lgrad_kernels[index].name : NULL;
 }
 
 // floats of the record of a solve: one stage state per evaluation row and sample; 0 for arguments that describe none
@@ -941,6 +965,7 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
         // a wavefront per workgroup and per tile; LDS = stage slots + the slope stash of the tile's samples
         const long long tiles = (batch + spt - 1) / spt;
         const size_t lds = d.record ? rec_lds_bytes(plan, ka.tangent_first)
+                         : d.logp_grad ? lgrad_lds_bytes(plan, ka.tangent_first)
                                     : (d.products || d.discrete ? vjp_lds_bytes : pull_lds_bytes)(plan, ka.n_tangent, ka.tangent_first);
         if (lds > kPullLdsLimit || tiles > 0x7fffffffll) return FF_ERR_UNSUPPORTED;
         const int herr = d.one_wave(&ka, (unsigned)tiles, (unsigned)lds, stream);
@@ -1024,16 +1049,28 @@ struct DadjIo {
     float* cot_cond_out;
 };
 
+// What ff_mlp_ode_launch_logp_grad adds to a launch (NULL: not a log-density gradient launch).
+struct LgradIo {
+    const float* record_in;
+    const float* probe_in;
+    const float* dlogp_cotangent;
+    const float* cotangent_in;
+    float* grad_x_out;
+    float* grad_cond_out;
+};
+
 // ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push, ff_mlp_ode_launch_pull,
-// ff_mlp_ode_launch_vjp, ff_mlp_ode_launch_record and ff_mlp_ode_launch_pull_discrete: one argument check, one launch path
+// ff_mlp_ode_launch_vjp, ff_mlp_ode_launch_record, ff_mlp_ode_launch_pull_discrete and ff_mlp_ode_launch_logp_grad: one argument
+// check, one launch path
 static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr,
-                      const PullIo* pull = nullptr, const VjpIo* vjp = nullptr, const RecIo* rec = nullptr, const DadjIo* dadj = nullptr)
+                      const PullIo* pull = nullptr, const VjpIo* vjp = nullptr, const RecIo* rec = nullptr, const DadjIo* dadj = nullptr,
+                      const LgradIo* lgrad = nullptr)
 {
     LaunchDesc d;
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
-    if ((pull || vjp || rec || dadj) && d.family == kSplit) return FF_ERR_UNSUPPORTED;
+    if ((pull || vjp || rec || dadj || lgrad) && d.family == kSplit) return FF_ERR_UNSUPPORTED;
     // pull plans launch through their own entries, and only they
-    if ((d.family == kPull) != (pull != nullptr || vjp != nullptr || rec != nullptr || dadj != nullptr)) return FF_ERR_BADARG;
+    if ((d.family == kPull) != (pull != nullptr || vjp != nullptr || rec != nullptr || dadj != nullptr || lgrad != nullptr)) return FF_ERR_BADARG;
     if (rec) {
         // a whole fixed-grid solve of the state that writes every stage state down: a state-only launch's arguments, the pull
         // launch's refusals.  No cotangent columns: no stash, and the tile's columns are all samples
@@ -1054,6 +1091,19 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
         const int ns = a->stage_slots > 0 && a->stage_slots <= FF_MAX_SLOTS ? a->stage_slots : FF_MAX_SLOTS;
         if (vjp_lds_bytes(plan, a->tangent_count, ns) > kPullLdsLimit) return FF_ERR_UNSUPPORTED;      // the stash does not fit
         d.discrete = true; d.one_wave = ff::g_dadj_kernels[index].launch; d.name = ff::g_dadj_kernels[index].name;
+    }
+    if (lgrad) {
+        // the transposed row program with the divergence integral in it: one probe and one final cotangent per row, the FORWARD
+        // launch's table and maps
+        const int index = plan->kernel_id - FF_PULL_KERNEL_BASE;
+        if (index < 0 || index >= n_lgrad_kernels() || !ff::g_lgrad_kernels[index].launch) return FF_ERR_BADARG;
+        if (!lgrad->record_in || !lgrad->probe_in || !lgrad->cotangent_in || !lgrad->grad_x_out || a->mode != FF_MODE_HUTCH) return FF_ERR_BADARG;
+        if (a->tangent_count < 0 || a->tangent_count > 1) return FF_ERR_BADARG;
+        if (a->probe || a->dlogp_out || a->k1_in || a->kl1_in || a->dlogp_in || a->jac_out || a->n_aux > 0 || a->noise) return FF_ERR_BADARG;
+        if (lgrad->grad_cond_out && plan->cond_dim == 0) return FF_ERR_BADARG;
+        const int ns = a->stage_slots > 0 && a->stage_slots <= FF_MAX_SLOTS ? a->stage_slots : FF_MAX_SLOTS;
+        if (lgrad_lds_bytes(plan, ns) > kPullLdsLimit) return FF_ERR_UNSUPPORTED;      // the stash does not fit
+        d.logp_grad = true; d.one_wave = ff::g_lgrad_kernels[index].launch; d.name = ff::g_lgrad_kernels[index].name;
     }
     if (vjp) {
         // whole fixed-grid solves of the state with K products per evaluation row: the pull launch's refusals, its own buffers
@@ -1093,7 +1143,7 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     }
     if (d.family == kSplit) return launch_split(plan, *d.split, a, hip_stream);
     // (a discrete-adjoint launch reads the record instead of a state and writes none)
-    if (((!a->x_in || !a->x_out) && !dadj) || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
+    if (((!a->x_in || !a->x_out) && !dadj && !lgrad) || !a->wpack || !a->etab || a->batch < 0 || a->n_evals < 0) return FF_ERR_BADARG;
     if (plan->cond_dim > 0 && !a->cond) return FF_ERR_BADARG;
     int nt, unit;
     int rc = tangents_of_mode(a->mode, plan->dim, plan->tile, &nt, &unit);
@@ -1114,8 +1164,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     }
     // (a state-only family has no tangent kernels: every mode but FF_MODE_STATE ends here, divergence-free by construction)
     if ((a->mode != FF_MODE_STATE) != (d.tangents != 0)) return FF_ERR_BADARG;
-    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull && !vjp && !dadj) return FF_ERR_BADARG;      // (push: no state tangents = zero)
-    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull && !vjp && !dadj) return FF_ERR_BADARG;
+    if (a->mode == FF_MODE_HUTCH && !a->probe && !push && !pull && !vjp && !dadj && !lgrad) return FF_ERR_BADARG;      // (push: no state tangents = zero)
+    if (a->mode != FF_MODE_STATE && !a->dlogp_out && !push && !pull && !vjp && !dadj && !lgrad) return FF_ERR_BADARG;
     if (a->stage_slots < 0 || a->stage_slots > FF_MAX_SLOTS) return FF_ERR_BADARG;
     if (a->batch == 0 && d.empty_batch_first) return FF_OK;
     if (a->n_aux < 0 || a->n_aux > d.max_aux || (a->k1_in && !d.takes_k1)) return FF_ERR_BADARG;
@@ -1125,7 +1175,7 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
 
     ff::KernelArgs ka = fill_args(plan, a, !d.state_only, nt, unit, tfirst);
     ka.etab_stride = FF_ROW_HDR + d.row_nets * plan->width;
-    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull || vjp || rec || dadj ? pull_layout(plan).total_floats : 0);
+    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull || vjp || rec || dadj || lgrad ? pull_layout(plan).total_floats : 0);
     if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
@@ -1148,6 +1198,12 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     }
     if (dadj) {
         ka.probe = dadj->cotangent_in; ka.dlogp_out = dadj->cot_x_out; ka.jac_out = dadj->cot_cond_out; ka.k1_in = dadj->record_in;
+        ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;
+    }
+    // (the log-density gradient launch: ff_mlp_lgrad.hpp)
+    if (lgrad) {
+        ka.probe = lgrad->cotangent_in; ka.dlogp_out = lgrad->grad_x_out; ka.jac_out = lgrad->grad_cond_out; ka.k1_in = lgrad->record_in;
+        ka.kl1_in = lgrad->probe_in; ka.dlogp_in = lgrad->dlogp_cotangent;
         ka.tangent_first = a->stage_slots > 0 ? a->stage_slots : FF_MAX_SLOTS;
     }
     return enqueue(d, plan, ka, plan->tile / (1 + nt), a->jac_out != nullptr, (hipStream_t)hip_stream);
@@ -1195,6 +1251,14 @@ extern "C" int ff_mlp_ode_launch_pull_discrete(const ff_mlp_plan_t* plan, const 
 {
     const DadjIo io = {record_in, cotangent_in, cot_x_out, cot_cond_out};
     return launch_ode(plan, a, nullptr, hip_stream, nullptr, nullptr, nullptr, nullptr, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_logp_grad(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* record_in, const float* probe_in,
+                                           const float* dlogp_cotangent, const float* cotangent_in, float* grad_x_out,
+                                           float* grad_cond_out, void* hip_stream)
+{
+    const LgradIo io = {record_in, probe_in, dlogp_cotangent, cotangent_in, grad_x_out, grad_cond_out};
+    return launch_ode(plan, a, nullptr, hip_stream, nullptr, nullptr, nullptr, nullptr, nullptr, &io);
 }
 
 // ---- the device-side adaptive controller's arithmetic, on the host (tests without a GPU; ff_adapt_logic.h) ------------

@@ -793,6 +793,53 @@ class ScoreModel(nn.Module):
         return (logp, out[2]) if return_stderr else logp
 
     @torch.no_grad()
+    def log_prob_grad(self, x, conditional=None, *, method="rk4", options=None, probe="torch", seed=None, sample_offset=0,
+                      num_probes=1):
+        """Extension: ``log_prob`` on a fixed grid together with its gradient: returns ``(log_p [B, 1], grad_x [B, D],
+        grad_c [B, C] or None)`` -- what HMC / NUTS or L-BFGS over ``x`` or over the conditional inputs needs.  ``log_p`` is
+        bitwise ``log_prob(x, conditional, method=method, options=options, probe=..., ...)``.  On a ``hutchinson=True``
+        model the gradient launches take the very probes of that solve (``self.e``), and ``grad_x`` / ``grad_c`` are the
+        exact gradient of that value as a function of ``(x, conditional)`` at FIXED probes -- the discrete adjoint with the
+        divergence integral in it (reverse mode over the forward-mode tangent, ``odeint.solve_logp_grad``), exact at any
+        step count.  On an exact-trace model the value comes from the exact-trace solve and the gradient from the D unit
+        probes with weight 1: the gradient of the same discrete sum, to rounding.  Three launches per piece of rows: the
+        value solve, the record launch, the gradient launch; K probes are K rows each.
+
+        Fixed grids only (``method="rk4"`` / ``"dopri5_fixed"`` / ``"euler"`` with ``options={"step_size": h}``; the default
+        grid is ONE step): adaptive methods, ``grid_constructor`` / ``perturb``, ``precision`` other than f32 and Hutch++ /
+        XTrace models raise before the device is touched.  No parameter gradients, no torch.autograd integration (the call
+        runs under ``no_grad``), no gradients of ``log_prob_noisy``: see ``odeint.solve_logp_grad``."""
+        return self._log_prob_grad(x, conditional, method, options, probe, seed, sample_offset, num_probes)
+
+    def _log_prob_grad(self, x, conditional, method, options, probe, seed, sample_offset, num_probes, in_shift=None,
+                       in_scale=None, cond_tangent_scale=None):
+        """``log_prob_grad`` proper; the affine input map and the conditional scale of the population wrappers as in
+        ``_flow_vjp``."""
+        if (self.hutchpp or self.xtrace) and not self.hutch:
+            raise ValueError("log-density gradients of a Hutch++ / XTrace model: the estimators' products are not differentiated "
+                             "(the reference detaches them too); construct the model with hutchinson=True, or without an "
+                             "estimator (the exact trace)")
+        trace_estimators.check_num_probes(num_probes, bool(self.hutch), "construct the model with hutchinson=True")
+        rng = trace_estimators.probe_rng(probe, seed, sample_offset, bool(self.hutch),
+                                         "probe='philox' draws the probes of a Hutchinson model: construct it with hutchinson=True")
+        odeint.check_logp_grad(self, x, method, options, conditional)
+        xT, lp, _ = self._solve_forward(x, conditional, 0.0, 0.0, method, options, in_shift=in_shift, in_scale=in_scale,
+                                        probe_rng=rng, num_probes=num_probes)
+        logp = lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
+        B, D = x.shape
+        if self.hutch:
+            probes = self.e if self.e.dim() == 3 else self.e.unsqueeze(1)
+            weight = 1.0 / probes.shape[1]
+        else:
+            probes, weight = torch.eye(D, dtype=torch.float32, device=x.device).expand(B, D, D), 1.0
+        var = float(getattr(self.sde, "sigma_max", 1.0)) ** 2          # the prior: N(0, sigma_max^2) on a VE model, else N(0, 1)
+        t_span = torch.tensor([float(self.sde.epsilon), 1.0], dtype=torch.float32)
+        _, gx, gc = odeint.solve_logp_grad(self, x, t_span, method, options, probes.contiguous(), weight, cond=conditional,
+                                           in_shift=in_shift, in_scale=in_scale, cond_tangent_scale=cond_tangent_scale,
+                                           prior_grad=lambda y: -y / var)
+        return logp, gx, gc
+
+    @torch.no_grad()
     def log_prob_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-4, rtol=1e-4, method="dopri5",
                        options={"min_step": 1e-6}, *, seed=None, sample_offset=0, chunk_points=None, return_ess=False,
                        num_probes=1):
@@ -915,6 +962,21 @@ class _PopulationModel(nn.Module):
         return self.score_model._flow_vjp(x, cotangents, cond, direction, method, options, return_retrace, adjoint, **maps)
 
     @torch.no_grad()
+    def _log_prob_grad(self, x, conditional, method, options, probe, seed, sample_offset, num_probes):
+        """``log_prob_grad`` of the two wrappers: ``ScoreModel.log_prob_grad`` of the inner score model behind ``(x - shift) /
+        scale`` (in the kernel), so that ``grad_x`` is in the units of the user's ``x`` and ``grad_c`` in those of the RAW
+        conditional.  ``log_p`` is this wrapper's ``log_prob`` formula on the fixed grid of ``method`` / ``options`` (its
+        ``log_prob`` itself is hard-wired to adaptive dopri5, which has no discrete adjoint)."""
+        cond, maps = None, {"in_shift": self.shift, "in_scale": self.scale}
+        if conditional is not None:
+            C = int(self.model.n_conditionals)
+            if not hasattr(self, "conditional_scale") or not torch.is_tensor(conditional) or conditional.dim() != 2 or \
+                    conditional.shape[1] != C:
+                raise ValueError(f"log-density gradients: conditional must be [batch, {C}] (and the wrapper a conditional one)")
+            cond, maps = self._cond(conditional), dict(maps, cond_tangent_scale=self.conditional_scale)
+        return self.score_model._log_prob_grad(x, cond, method, options, probe, seed, sample_offset, num_probes, **maps)
+
+    @torch.no_grad()
     def _log_prob_noisy(self, x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
                         return_ess, num_probes):
         """``log_prob_noisy`` of the two wrappers: ``ScoreModel.log_prob_noisy`` around this wrapper's own ``log_prob`` --
@@ -962,6 +1024,15 @@ class PopulationModelDiffusion(_PopulationModel):
         options={"step_size": h}, num_probes=K, return_stderr=True)`` on the normalised points is the route.)
         ``num_probes`` (extension): see ``ScoreModel.solve_odes_forward``; a model built with ``hutchinson=True``."""
         return self._log_prob(x, None, atol, rtol, num_probes)
+
+    def log_prob_grad(self, x, conditional=None, *, method="rk4", options=None, probe="torch", seed=None, sample_offset=0,
+                      num_probes=1):
+        """Extension: ``ScoreModel.log_prob_grad`` in the units of this wrapper: ``(log_p [B, 1], grad_x [B, D], None)`` on
+        the fixed grid of ``method`` / ``options`` (the default grid is ONE rk4 step: pass ``options={"step_size": h}``).
+        ``conditional`` must stay None (the signature is the conditional wrapper's).  See ``_log_prob_grad``."""
+        if conditional is not None:
+            raise ValueError("log-density gradients: this model has no conditional inputs")
+        return self._log_prob_grad(x, None, method, options, probe, seed, sample_offset, num_probes)
 
     def flow_jvp(self, x, tangents, *, direction="to_data", method="rk4", options=None):
         """Extension: ``ScoreModel.flow_jvp`` in the units of this wrapper: ``to_data`` differentiates ``forward(x)``
@@ -1025,6 +1096,14 @@ class PopulationModelDiffusionConditional(_PopulationModel):
         """(No ``return_stderr`` here: like the reference's, this solve is hard-wired to adaptive dopri5 -- and this
         wrapper's score model takes the exact trace, which has no probes to spread; ``num_probes`` > 1 is refused there.)"""
         return self._log_prob(x, conditional, atol, rtol, num_probes)
+
+    def log_prob_grad(self, x, conditional=None, *, method="rk4", options=None, probe="torch", seed=None, sample_offset=0,
+                      num_probes=1):
+        """Extension: ``ScoreModel.log_prob_grad`` in the units of this wrapper: ``(log_p [B, 1], grad_x [B, D],
+        grad_c [B, C])`` with ``grad_c`` the gradient with respect to the RAW conditional (the population
+        hyper-parameters), on the fixed grid of ``method`` / ``options`` (the default grid is ONE rk4 step: pass
+        ``options={"step_size": h}``).  This wrapper's score model takes the exact trace.  See ``_log_prob_grad``."""
+        return self._log_prob_grad(x, conditional, method, options, probe, seed, sample_offset, num_probes)
 
     def flow_jvp(self, x, tangents=None, conditional=None, conditional_tangents=None, *, direction="to_data", method="rk4",
                  options=None):

@@ -256,6 +256,49 @@ class _FlowBase(nn.Module):
         t_span, kw = self._push_args(x, conditional, direction)
         return odeint.solve_pull_by(adjoint, self, x, t_span, method, options, cotangents, return_retrace=return_retrace, **kw)
 
+    @torch.no_grad()
+    def _log_prob_grad(self, x, conditional, method, options, hutchinson, probe, seed, sample_offset, num_probes):
+        """``log_prob_grad`` of both flows (extension): ``log_prob`` on a fixed grid with its gradient, ``(log_p [B, 1],
+        grad_x [B, D], grad_c [B, C] or None)`` in the units of the target-space ``x`` and the raw ``conditional``.  ``log_p`` is
+        bitwise ``log_prob(x, [conditional,] method=method, options=options, hutchinson=hutchinson, probe=..., ...)`` (as a
+        column).  ``hutchinson=True``: the gradient launches take the very probes of that solve, and the gradient is exact for
+        that value at FIXED probes -- the discrete adjoint with the divergence integral in it (``odeint.solve_logp_grad``),
+        exact at any step count.  ``hutchinson=False``: the value comes from the exact-trace solve, the gradient from the D
+        unit probes with weight 1 -- the gradient of the same discrete sum, to rounding.  ``- sum log target_scale`` is a
+        constant; ``(x - target_shift) / target_scale`` contributes ``1 / target_scale``.
+
+        Fixed grids only (``method="rk4"`` / ``"dopri5_fixed"`` / ``"euler"`` with ``options={"step_size": h}``; the default
+        grid is ONE step): adaptive methods, ``grid_constructor`` / ``perturb`` and ``precision`` other than f32 raise
+        before the device is touched.  No parameter gradients, no torch.autograd integration, no gradients of
+        ``log_prob_noisy``."""
+        C = getattr(self, "conditional_dimension", 0)
+        cond, kw = None, {}
+        if conditional is not None:
+            if C == 0:
+                raise ValueError("log-density gradients: this model has no conditional inputs")
+            if not torch.is_tensor(conditional) or conditional.dim() != 2 or conditional.shape[1] != C:
+                raise ValueError(f"log-density gradients: conditional must be [batch, {C}]")
+            cond, kw = self._norm_cond(conditional), {"cond_tangent_scale": self.conditional_scale}
+        K = trace_estimators.check_num_probes(num_probes, hutchinson, "pass hutchinson=True")
+        rng = self._probe_rng(probe, seed, sample_offset, hutchinson)
+        odeint.check_logp_grad(self, x, method, options, cond)
+        xn = (x - self.target_shift) / self.target_scale
+        t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
+        norm_only = () if conditional is None else (conditional,)
+        B, D = x.shape
+        if hutchinson:
+            kept = []
+            xT, logj, _ = odeint.solve_hutchinson(self, xn, t_span, method, options, 1e-5, 1e-5, K, rng, keep=kept.append,
+                                                  cond=cond, norm_only=norm_only)
+            probes, weight = (kept[-1] if K > 1 else kept[-1].unsqueeze(1)), 1.0 / K
+        else:
+            xT, logj = self._solve(xn, t_span, method, options, MODE_EXACT, 1e-5, 1e-5, cond=cond, norm_only=norm_only)
+            probes, weight = torch.eye(D, dtype=torch.float32, device=x.device).expand(B, D, D), 1.0
+        base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
+        logp = base + logj.view(-1, 1).squeeze(1) - torch.sum(torch.log(self.target_scale))
+        _, gx, gc = odeint.solve_logp_grad(self, xn, t_span, method, options, probes.contiguous(), weight, cond=cond, **kw)
+        return logp.view(-1, 1), gx / self.target_scale, gc
+
     # -- the public methods' bodies, written once (``conditional=None``: the unconditional flow) -----------------------------
     def compute_linear_velocity_field(self, x0, xT, t):
         x0 = (x0 - self.target_shift) / self.target_scale
@@ -392,6 +435,15 @@ class ODEFlow(_FlowBase):
                              num_probes, return_stderr)
         return out if return_stderr else out[0]
 
+    def log_prob_grad(self, x, conditional=None, *, method: str = "rk4", options: Optional[dict] = None,
+                      hutchinson: bool = False, probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0,
+                      num_probes: int = 1):
+        """Extension: ``(log_p [B, 1], grad_x [B, D], None)``: ``log_prob`` on a fixed grid and its gradient with respect to
+        ``x`` (see ``_log_prob_grad``).  ``conditional`` must stay None (the signature is the conditional flow's)."""
+        if conditional is not None:
+            raise ValueError("log-density gradients: this model has no conditional inputs")
+        return self._log_prob_grad(x, None, method, options, hutchinson, probe, seed, sample_offset, num_probes)
+
     def log_prob_noisy(self, x, noise_std, num_draws: int = 16, atol: float = 1e-5, rtol: float = 1e-5,
                        method: str = "dopri5", options: Optional[dict] = None, *, hutchinson: bool = False,
                        seed: Optional[int] = None, sample_offset: int = 0, chunk_points: Optional[int] = None,
@@ -475,6 +527,13 @@ class ConditionalODEFlow(_FlowBase):
         out = self._log_prob(x, conditional, atol, rtol, method, options, adjoint, hutchinson, probe, seed, sample_offset,
                              num_probes, return_stderr)
         return out if return_stderr else out[0]
+
+    def log_prob_grad(self, x, conditional=None, *, method: str = "rk4", options: Optional[dict] = None,
+                      hutchinson: bool = False, probe: str = "torch", seed: Optional[int] = None, sample_offset: int = 0,
+                      num_probes: int = 1):
+        """Extension: ``(log_p [B, 1], grad_x [B, D], grad_c [B, C])``: ``log_prob`` on a fixed grid and its gradient with
+        respect to ``x`` and the raw ``conditional`` (see ``_log_prob_grad``)."""
+        return self._log_prob_grad(x, conditional, method, options, hutchinson, probe, seed, sample_offset, num_probes)
 
     def log_prob_noisy(self, x, noise_std, conditional, num_draws: int = 16, atol: float = 1e-5, rtol: float = 1e-5,
                        method: str = "dopri5", options: Optional[dict] = None, *, hutchinson: bool = False,

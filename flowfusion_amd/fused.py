@@ -364,6 +364,37 @@ class FusedNet:
             _native.plan_words(plan, stage_slots), want)
         return gx, (gc if want else None), status
 
+    def logp_grad(self, rec: torch.Tensor, table: torch.Tensor, probe: torch.Tensor, cot: torch.Tensor,
+                  weight: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, want_cond: bool = False,
+                  stage_slots: int = 0, in_shift=None, in_scale=None, out_scale=None, out_shift=None):
+        """The gradient of a fixed-grid Hutchinson log-density on the log-density gradient unit (the sibling of
+        ``pull_plan``'s): the transposed row program of the FORWARD rows ``table`` with the divergence integral in it, run
+        backwards over ``rec`` (``record`` of the same table, conditional and maps).  ``probe`` [B, D]: each row's probe;
+        ``cot`` [B, D]: the cotangent of its final state; ``weight`` [B] or None (= 1): that of its divergence integral.
+        Returns (gx [B, D], gc [B, C] or None, status [1]): the gradient of ``weight * lp + <cot, x_out>`` with respect to the
+        record launch's ``x`` and ``cond`` as given, at fixed probes."""
+        if not rec.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {rec.device}); there is no CPU fallback")
+        if rec.dim() != 3 or rec.shape[2] != self.dim or rec.shape[0] != table.shape[0]:
+            raise ValueError(f"expected a [{int(table.shape[0])}, batch, {self.dim}] record, got {tuple(rec.shape)}")
+        dev = rec.device
+        plan = self.pull_plan()
+        B = int(rec.shape[1])
+        cond = self._pull_cond(cond, B, dev)
+        for name, t in (("probe", probe), ("cot", cot)):
+            if t is None or tuple(t.shape) != (B, self.dim):
+                raise ValueError(f"logp_grad: {name} [batch, {self.dim}]")
+        if weight is not None and tuple(weight.shape) != (B,):
+            raise ValueError("logp_grad: weight [batch]")
+        want = bool(want_cond and self.cond_dim > 0)
+        gx, gc, status = torch.ops.flowfusion_amd.mlp_ode_logp_grad(
+            f32_on(rec, dev), cond, f32_on(probe, dev), f32_on(weight, dev), f32_on(cot, dev), self.wpack(dev, MODE_HUTCH, plan),
+            f32_on(table, dev), f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots), want)
+        return gx, (gc if want else None), status
+
     def vjp_products(self, x: torch.Tensor, etab: torch.Tensor, seeds: torch.Tensor, per_row: bool = False,
                      cond: Optional[torch.Tensor] = None, stage_slots: int = 0, in_shift=None, in_scale=None, out_scale=None,
                      out_shift=None):

@@ -400,31 +400,32 @@ def solve_push_jacobian(front, x, t_span, method, options, cond=None, tangent_ga
     return y, Jx, Jc
 
 
-def _pull_checks(front, x, method, options, cotangents, cond):
+def _pull_checks(front, x, method, options, cotangents, cond, what="flow-map pull-backs", tile_limit=True):
     """What ``solve_pull`` and ``solve_pull_discrete`` refuse, in one order and with one set of messages, before the device is
-    touched; returns ``(net, plan, B, D, K, C)``."""
+    touched; returns ``(net, plan, B, D, K, C)``.  ``solve_logp_grad`` refuses the same, under its own name ``what``; its K
+    probes are rows of their own, not columns of a tile (``tile_limit=False``)."""
     if method in solvers.ALL_ADAPTIVE or method in solvers.ADAPTIVE_METHODS:
-        raise ValueError(f"flow-map pull-backs with the adaptive method={method!r}: the adjoint sweep runs over the reversed "
+        raise ValueError(f"{what} with the adaptive method={method!r}: the adjoint sweep runs over the reversed "
                          "fixed grid of the forward solve; use method=\"rk4\" / \"dopri5_fixed\" with "
                          "options={\"step_size\": h}")
     solvers.resolve_method(method)
     for name in ("grid_constructor", "perturb"):
         if (options or {}).get(name) not in (None, False):
-            raise ValueError(f"flow-map pull-backs with options[{name!r}]: the grid is the uniform one of "
+            raise ValueError(f"{what} with options[{name!r}]: the grid is the uniform one of "
                              "options={\"step_size\": h} (or the nodes of t_span)")
     if not torch.is_tensor(x) or x.dim() != 2:
-        raise ValueError("flow-map pull-backs: x must be a [batch, dim] tensor")
+        raise ValueError(f"{what}: x must be a [batch, dim] tensor")
     B, D = int(x.shape[0]), int(x.shape[1])
     prec = getattr(front, "precision", "f32")
     if prec != "f32":
-        raise ValueError(f"flow-map pull-backs with precision={prec!r}: the pull-back kernels compute in f32; use "
+        raise ValueError(f"{what} with precision={prec!r}: the pull-back kernels compute in f32; use "
                          "precision='f32'")
     if not torch.is_tensor(cotangents) or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, D) or cotangents.shape[1] < 1:
-        raise ValueError(f"flow-map pull-backs: cotangents must be [{B}, K >= 1, {D}], got "
+        raise ValueError(f"{what}: cotangents must be [{B}, K >= 1, {D}], got "
                          f"{tuple(cotangents.shape) if torch.is_tensor(cotangents) else type(cotangents).__name__}")
     K = int(cotangents.shape[1])
-    if K > _native.MAX_PULL_COTANGENTS:
-        raise ValueError(f"flow-map pull-backs: K={K} cotangents per sample; a sample and its cotangents share the 16 columns "
+    if tile_limit and K > _native.MAX_PULL_COTANGENTS:
+        raise ValueError(f"{what}: K={K} cotangents per sample; a sample and its cotangents share the 16 columns "
                          f"of one tile, so at most {_native.MAX_PULL_COTANGENTS} per call")
     try:
         net = front._net()                  # (a ``model=`` module that is not the library's MLP raises here)
@@ -434,14 +435,14 @@ def _pull_checks(front, x, method, options, cotangents, cond):
         raise NotImplementedError(msg if _native.PULL_ENVELOPE in msg else
                                   f"{msg} -- {_native.PULL_ENVELOPE}; there is no module-path fallback") from None
     if D != net.dim:
-        raise ValueError(f"flow-map pull-backs: x has {D} columns, the model has {net.dim} dimensions")
+        raise ValueError(f"{what}: x has {D} columns, the model has {net.dim} dimensions")
     C = net.cond_dim
     if C > 0 and (cond is None or cond.dim() != 2 or tuple(cond.shape) != (B, C)):
-        raise ValueError(f"flow-map pull-backs: conditional must be [{B}, {C}], got "
+        raise ValueError(f"{what}: conditional must be [{B}, {C}], got "
                          f"{None if cond is None else tuple(cond.shape)}")
     if C == 0 and cond is not None:
-        raise ValueError("flow-map pull-backs: this model has no conditional inputs")
-    require_fp32(front, x, cond, cotangents, what="a flow-map pull-back solve")
+        raise ValueError(f"{what}: this model has no conditional inputs")
+    require_fp32(front, x, cond, cotangents, what="a flow-map pull-back solve" if tile_limit else "a log-density gradient solve")
     _need_gpu(x)
     return net, plan, B, D, K, C
 
@@ -576,6 +577,75 @@ def solve_pull_by(adjoint, front, x, t_span, method, options, cotangents, return
         raise ValueError("flow-map pull-backs: return_retrace with adjoint=\"discrete\": the discrete adjoint reads recorded "
                          "stage states and retraces nothing")
     return solve_pull_discrete(front, x, t_span, method, options, cotangents, **kw)
+
+
+def check_logp_grad(front, x, method, options, cond):
+    """The refusals of ``solve_logp_grad`` that need no probes: the front ends call it before the value solve, so that a
+    ``log_prob_grad`` that cannot run raises before the device is touched."""
+    stand_in = x.unsqueeze(1) if torch.is_tensor(x) and x.dim() == 2 else None       # (a view: the probes' shape, no device work)
+    _pull_checks(front, x, method, options, stand_in, cond, what="log-density gradients", tile_limit=False)
+
+
+def solve_logp_grad(front, x, t_span, method, options, probes, probe_weight, cond=None, in_shift=None, in_scale=None,
+                    cond_tangent_scale=None, prior_grad=None):
+    """Log-density gradients (extension): the gradient of the fixed-grid Hutchinson log-density
+    ``sum_k probe_weight * lp(x, cond; probes[:, k]) + log prior(y)`` with respect to ``x`` and ``cond`` at FIXED probes, by
+    the exact discrete adjoint with the divergence integral in it (csrc/ff_mlp_lgrad.hpp) -- reverse mode over the
+    forward-mode tangent, so exact for the discrete sum that ``solve`` in MODE_HUTCH evaluates, at any step count.  Returns
+    ``(y [B, D], gx [B, D], gc [B, C] or None)``.  ``probes`` [B, K, D]: K >= 1 probes per point, every one a row of its own
+    (the kernel carries two columns per row: no tile limit on K); ``probe_weight``: 1 / K for a probe average, 1 for the D
+    unit probes of an exact trace.  ``prior_grad(y)``: the gradient of the log prior at the final state (default ``-y``: a
+    standard normal).
+
+    Per piece of rows, cut by ``discrete_piece_rows`` on the expanded B K rows (whole points): the record launch on the
+    repeated rows, the prior's gradient at its state as the final cotangent of replica 0 of each point (zero on the
+    others), ONE launch of the log-density gradient unit (FusedNet.logp_grad), and the sum over a point's K replicas in the
+    order k = 0 .. K - 1.  Rows are independent, so any cut gives bitwise the same.  ``y`` is the record launch's state:
+    bitwise the fixed-grid solve's.  The affine input map and ``cond_tangent_scale`` are as in ``solve_pull_discrete``.
+
+    Refusals: ``_pull_checks``', under the name "log-density gradients".  Out of scope: parameter gradients and
+    torch.autograd integration, adaptive control, a multi-probe column layout, twins, split precision, non-SiLU units, a
+    module-path fallback, sharded entry points (rows are independent: slice), gradients of ``log_prob_noisy``."""
+    net, plan, B, D, K, C = _pull_checks(front, x, method, options, probes, cond, what="log-density gradients", tile_limit=False)
+    tab = solvers.plan_ode(t_span, method, options)          # (rows of a fixed-grid ODE method: none carries a noise flag)
+    width = int(plan.width)
+    key = ("pull_discrete", tuple(float(v) for v in torch.as_tensor(t_span)), method,
+           repr(sorted((options or {}).items()))) + front._schedule_key()
+    table = net.cached_table(key, x.device, lambda: solvers.build_table(tab, *front._host_schedule()(tab.t_eval), width))
+    E = max(1, int(table.shape[0]))
+    points = max(1, discrete_piece_rows(B * K, 1, E, D) // K)
+    pieces = [(r0, min(B, r0 + points)) for r0 in range(0, B, points)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    rep = lambda t: t if (t is None or K == 1) else t.repeat_interleave(K, dim=0)
+    slots = solvers.resolve_method(method).stages
+    maps = dict(in_shift=in_shift, in_scale=in_scale)
+    ys, gxs, gcs = [], [], []
+    for r0, r1 in pieces:
+        n = r1 - r0
+        ck = rep(cut(cond, r0, r1))
+        yp, rec, _ = net.record(rep(cut(x, r0, r1)), table, cond=ck, stage_slots=slots, **maps)
+        y0 = yp if K == 1 else yp[::K].contiguous()
+        cot = torch.zeros(n * K, D, dtype=torch.float32, device=x.device)
+        cot[::K] = -y0 if prior_grad is None else prior_grad(y0)
+        weight = torch.full((n * K,), float(probe_weight), dtype=torch.float32, device=x.device)
+        gx, gc, _ = net.logp_grad(rec, table, cut(probes, r0, r1).reshape(n * K, D), cot, weight, cond=ck, want_cond=C > 0,
+                                  stage_slots=slots, **maps)
+        del rec
+        gx, gc = gx.view(n, K, D), (None if gc is None else gc.view(n, K, C))
+        sx, sc = gx[:, 0].clone(), (None if gc is None else gc[:, 0].clone())
+        for k in range(1, K):                   # a fixed order: the sum does not depend on the cut
+            sx += gx[:, k]
+            if sc is not None:
+                sc += gc[:, k]
+        ys.append(y0)
+        gxs.append(sx)
+        gcs.append(sc)
+    y, gx = (ys[0], gxs[0]) if whole else (torch.cat(ys), torch.cat(gxs))
+    gc = None if C == 0 else (gcs[0] if whole else torch.cat(gcs))
+    if cond_tangent_scale is not None and gc is not None:
+        gc = gc / cond_tangent_scale
+    return y, gx, gc
 
 
 def solve_leapfrog(front, x, grid, cond=None):

@@ -111,6 +111,11 @@ class SymplecticFlowModel(nn.Module):
         raise NotImplementedError("flow_vjp of a SymplecticFlowModel: the two-network kernels carry no cotangent columns -- "
                                   f"{_native.PULL_ENVELOPE}, on ScoreModel, ODEFlow and ConditionalODEFlow")
 
+    def log_prob_grad(self, *args, **kwargs):
+        """Log-density gradients (``ODEFlow.log_prob_grad``) are not built for the two-network kernels."""
+        raise NotImplementedError("log_prob_grad of a SymplecticFlowModel: the two-network kernels carry no adjoint columns -- "
+                                  f"{_native.PULL_ENVELOPE}, on ScoreModel, ODEFlow and ConditionalODEFlow")
+
     @torch.no_grad()
     def log_prob(self, x, conditional=None, atol=1e-5, rtol=1e-5):
         """``log N(z1) - log N(p0) - sum log scale`` with z1 the dopri5 solution over t: 0 -> 1 of [q0 | p0],

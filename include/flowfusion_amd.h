@@ -459,6 +459,43 @@ int ff_mlp_ode_launch_pull_discrete(const ff_mlp_plan_t* plan, const ff_ode_args
                                     const float* cotangent_in /* [batch, K, dim] */, float* cot_x_out /* [batch, K, dim] */,
                                     float* cot_cond_out /* [batch, K, cond_dim] or NULL */, void* hip_stream);
 
+/* ---- the gradient of a fixed-grid Hutchinson log-density, from recorded stage states ---------------------------------------
+ * With one probe eps per row the forward program above also integrates the divergence,
+ *     kl[slot_e] = a_e eps.eps + b_e eps^T J_net(y_e, c) eps;   FF_ROW_STEP_END: lp += sum_s cout_e[s] kl[s]
+ * and a log-density is  lp + log prior(x_out).  The unit of csrc/ff_mlp_lgrad.hpp, one sibling per pull-back unit, runs the
+ * transposed row program of ff_mlp_ode_launch_pull_discrete with one scalar adjoint slot per stage slot for lp and the
+ * second-order source  w grad (eps^T J_net eps)  in every row: reverse mode over the forward-mode tangent, exact for the discrete
+ * sum at fixed probes.
+ *
+ * ff_mlp_ode_launch_logp_grad(plan, args, record_in, probe_in, dlogp_cotangent, cotangent_in, grad_x_out, grad_cond_out, stream):
+ * `plan` is a PULL plan and args->wpack its two packs; args is the FORWARD launch's -- same table, same cond, same affine maps --
+ * with args->mode == FF_MODE_HUTCH and args->tangent_count 0 or 1; args->x_in and args->x_out are ignored.
+ *     record_in        [n_evals, batch, dim]       the record launch's output
+ *     probe_in         [batch, dim]                the Hutchinson probe of each row (in the integrated state's units)
+ *     dlogp_cotangent  [batch] or NULL (= 1)       per-row weight of the divergence integral: 1 / K for a probe average over K
+ *                                                  rows, 1 for unit probes of an exact trace, 0 switches the second-order path off
+ *     cotangent_in     [batch, dim]                cotangent of the final state (the prior's gradient), units of x_out
+ *     grad_x_out       [batch, dim]                d (w lp + cotangent . x_out) / d x_in
+ *     grad_cond_out    [batch, cond_dim] or NULL   the same with respect to cond
+ * Two columns per row, tile / 2 rows per tile; LDS = stage_slots * dregs * 256 bytes of adjoint slots + 64 * n_hidden * width
+ * bytes of stash (two words per hidden unit and row).
+ *
+ * It refuses, before anything is enqueued:
+ *     a plan that is not a pull plan                                                                   FF_ERR_BADARG
+ *     a mode other than FF_MODE_HUTCH, tangent_count > 1                                               FF_ERR_BADARG
+ *     record_in, probe_in, cotangent_in or grad_x_out NULL; grad_cond_out with cond_dim == 0           FF_ERR_BADARG
+ *     noise, k1_in, kl1_in, dlogp_in, jac_out, dlogp_out or probe set, n_aux > 0                       FF_ERR_BADARG
+ *     a depth whose stash does not fit the LDS (above about 9 x 256, 19 x 128)                         FF_ERR_UNSUPPORTED
+ * FF_LGRAD_KERNEL_BASE + index names the unit (index = plan->kernel_id - FF_PULL_KERNEL_BASE); no plan carries it.
+ * FF_STATUS_BAD_SLOT and FF_STATUS_NOISE_ROW: as for ff_mlp_ode_launch_pull_discrete. */
+#define FF_LGRAD_KERNEL_BASE 0x90000
+int ff_lgrad_kernel_count(void);
+const char* ff_lgrad_kernel_name(int index);
+int ff_mlp_ode_launch_logp_grad(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* record_in,
+                                const float* probe_in /* [batch, dim] */, const float* dlogp_cotangent /* [batch] or NULL */,
+                                const float* cotangent_in /* [batch, dim] */, float* grad_x_out /* [batch, dim] */,
+                                float* grad_cond_out /* [batch, cond_dim] or NULL */, void* hip_stream);
+
 /* Which kernel(s) ff_mlp_ode_launch enqueues for `batch` samples of a plan in `mode` (`tangent_count`: as in ff_ode_args,
  * 0 = the mode's default; `jac_out` != 0: a launch with a Jacobian output, which is never split): the launcher's rule as a
  * query, so that callers, benchmarks and tests can name the kernel that ran without timing it.  Honours FF_COOP /
