@@ -345,6 +345,13 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
                 ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.ff_weighted_resample.restype = L.ff_weighted_resample_host.restype = ctypes.c_int
     L.ff_weighted_resample.argtypes, L.ff_weighted_resample_host.argtypes = resample + [ctypes.c_void_p], resample
+    obs_keep = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]
+    grad_reduce = [ctypes.c_void_p] * 5 + [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_observe_keep.restype = L.ff_observe_keep_host.restype = ctypes.c_int
+    L.ff_observe_grad_reduce.restype = L.ff_observe_grad_reduce_host.restype = ctypes.c_int
+    L.ff_observe_keep.argtypes, L.ff_observe_keep_host.argtypes = obs_keep + [ctypes.c_void_p], obs_keep
+    L.ff_observe_grad_reduce.argtypes, L.ff_observe_grad_reduce_host.argtypes = grad_reduce + [ctypes.c_void_p], grad_reduce
     L.ff_mlp_ode_adaptive.restype = ctypes.c_int
     L.ff_mlp_ode_adaptive.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.POINTER(AdaptConfig),
                                       ctypes.POINTER(AdaptBuffers), ctypes.c_double, ctypes.c_double, ctypes.c_int32,
@@ -798,6 +805,92 @@ def weighted_resample(y: torch.Tensor, lp: torch.Tensor, num_draws: int, num_sam
     if rc != FF_OK:
         raise _err(rc, "ff_weighted_resample")
     return samples, index, mean, var
+
+
+def _lp_points(lp: torch.Tensor, num_draws: int, what: str) -> Tuple[int, int]:
+    """(B, K) of the B K log-densities ``lp`` ([B K] or [B K, 1]) of an observe reduction."""
+    K = int(num_draws)
+    if not 1 <= K <= MAX_OBS_DRAWS:
+        raise ValueError(f"num_draws={num_draws}: 1 .. {MAX_OBS_DRAWS} noise draws per data point")
+    if lp.numel() % K or lp.dim() > 2 or (lp.dim() == 2 and lp.shape[1] != 1):
+        raise RuntimeError(f"{what}: lp has shape {tuple(lp.shape)}, expected [B * {K}] or [B * {K}, 1]")
+    return lp.numel() // K, K
+
+
+def observe_keep(lp: torch.Tensor, num_draws: int, min_weight: float = 0.0) -> torch.Tensor:
+    """ff_observe_keep: ``keep`` [B K] int32, 1 where draw k of its point has a normalised weight ``exp(lp - max) / W`` that
+    is > 0 and >= ``min_weight`` (0 <= min_weight < 1), in double; a degenerate point (a NaN or +inf among its ``lp``, or
+    all -inf) keeps nothing.  ``lp``: B K elements, [B K] or [B K, 1].  Device tensors on the current stream; CPU tensors
+    go to ff_observe_keep_host."""
+    dev = lp.device
+    B, K = _lp_points(lp, num_draws, "observe_keep")
+    m = float(min_weight)
+    if not 0.0 <= m < 1.0:
+        raise ValueError(f"min_weight={min_weight}: a normalised weight, 0 <= min_weight < 1 (0 keeps every draw of non-zero weight)")
+    keep = torch.empty(B * K, dtype=torch.int32, device=dev)
+    ptr = _chk(lp, "lp", dev)
+    if B == 0:
+        return keep
+    L = lib()
+    rc = _on_stream(dev, L.ff_observe_keep, L.ff_observe_keep_host, (ptr, B, K, m, keep.data_ptr()))
+    if rc != FF_OK:
+        raise _err(rc, "ff_observe_keep")
+    return keep
+
+
+def observe_grad_reduce(lp: torch.Tensor, row_of: torch.Tensor, gx_rows: torch.Tensor, gc_rows: Optional[torch.Tensor],
+                        noise_std: torch.Tensor, num_draws: int, seed: int, sample_offset: int = 0,
+                        want_noise_grad: bool = True, grad_x: Optional[torch.Tensor] = None,
+                        grad_c: Optional[torch.Tensor] = None, grad_noise_std: Optional[torch.Tensor] = None):
+    """ff_observe_grad_reduce: ``(grad_x [B, D], grad_c [B, C] or None, grad_noise_std [B, D] or None)``, the gradient of
+    ff_logmeanexp of ``lp`` (B K elements) from the kept rows' own gradients: ``sum_k wn_k gx_rows[row_of[r K + k]]``,
+    likewise ``gc_rows``, and ``-sum_k wn_k z_k gx_rows[row_of[r K + k]]`` with the noise draws regenerated from ``seed`` and
+    global row ``sample_offset + r``; ``wn`` the normalised weights of the full sum, in double.  ``row_of`` [B K] int32: the
+    row of a draw's gradient in ``gx_rows`` [n, D] / ``gc_rows`` [n, C], < 0 for a draw that is skipped (checked here to stay
+    below n).  ``noise_std`` [D] or [B, D] as ff_observe_expand took it.  The outputs are allocated where not given.  Device
+    tensors on the current stream; CPU tensors go to ff_observe_grad_reduce_host."""
+    dev = lp.device
+    B, K = _lp_points(lp, num_draws, "observe_grad_reduce")
+    if gx_rows.dim() != 2 or gx_rows.shape[1] < 1:
+        raise RuntimeError(f"observe_grad_reduce: gx_rows has shape {tuple(gx_rows.shape)}, expected [n, D >= 1]")
+    n, D = gx_rows.shape
+    if gc_rows is not None and (gc_rows.dim() != 2 or gc_rows.shape[0] != n or gc_rows.shape[1] < 1):
+        raise RuntimeError(f"observe_grad_reduce: gc_rows has shape {tuple(gc_rows.shape)}, expected [{n}, C >= 1]")
+    C = 0 if gc_rows is None else int(gc_rows.shape[1])
+    if row_of.dtype != torch.int32 or row_of.numel() != B * K or not row_of.is_contiguous() or row_of.device != dev:
+        raise RuntimeError(f"observe_grad_reduce: row_of must be a contiguous int32 tensor of {B * K} elements on {dev}")
+    if B > 0 and int(row_of.max()) >= n:
+        raise RuntimeError(f"observe_grad_reduce: row_of points at row {int(row_of.max())}, gx_rows has {n} rows")
+    if tuple(noise_std.shape) == (D,):
+        stride = 0
+    elif tuple(noise_std.shape) == (B, D):
+        stride = D
+    else:
+        raise RuntimeError(f"observe_grad_reduce: noise_std has shape {tuple(noise_std.shape)}, expected [{D}] or [{B}, {D}]")
+    if grad_x is None:
+        grad_x = torch.empty(B, D, dtype=torch.float32, device=dev)
+    if grad_c is None and gc_rows is not None:
+        grad_c = torch.empty(B, C, dtype=torch.float32, device=dev)
+    if grad_noise_std is None and want_noise_grad:
+        grad_noise_std = torch.empty(B, D, dtype=torch.float32, device=dev)
+    for t, name, cols in ((grad_x, "grad_x", D), (grad_c, "grad_c", C), (grad_noise_std, "grad_noise_std", D)):
+        if t is not None and t.numel() != B * cols:
+            raise RuntimeError(f"observe_grad_reduce: {name} has {t.numel()} elements for [{B}, {cols}]")
+    if n == 0:                                              # nothing was kept: no row is read, but the pointer is mandatory
+        gx_rows = torch.zeros(1, D, dtype=torch.float32, device=dev)
+        gc_rows = None if gc_rows is None else torch.zeros(1, C, dtype=torch.float32, device=dev)
+    ptrs = (_chk(lp, "lp", dev), _chk(gx_rows, "gx_rows", dev), _chk(gc_rows, "gc_rows", dev), _chk(noise_std, "noise_std", dev),
+            _chk(grad_x, "grad_x", dev), _chk(grad_c if gc_rows is not None else None, "grad_c", dev),
+            _chk(grad_noise_std, "grad_noise_std", dev))
+    if B == 0:
+        return grad_x, grad_c, grad_noise_std
+    L = lib()
+    rc = _on_stream(dev, L.ff_observe_grad_reduce, L.ff_observe_grad_reduce_host,
+                    (ptrs[0], row_of.data_ptr(), ptrs[1], ptrs[2], ptrs[3], stride, B, D, C, K, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                     int(sample_offset), ptrs[4], ptrs[5], ptrs[6]))
+    if rc != FF_OK:
+        raise _err(rc, "ff_observe_grad_reduce")
+    return grad_x, grad_c, grad_noise_std
 
 
 def trace_kind_and_probes(kind: str, probes):

@@ -1,7 +1,8 @@
 // ff_observe.h -- the arithmetic of the K-draw log-density of noisy observations, shared by the gfx950 kernels
-// (ff_observe.hip: observe_expand_kernel / logmeanexp_kernel / weighted_resample_kernel) and the host entry points the
-// CPU tests call (ff_observe_expand_host / ff_logmeanexp_host / ff_weighted_resample_host, compiled from the host pass of
-// the same file).
+// (ff_observe.hip: observe_expand_kernel / logmeanexp_kernel / weighted_resample_kernel / observe_keep_kernel /
+// observe_grad_reduce_kernel) and the host entry points the CPU tests call (ff_observe_expand_host / ff_logmeanexp_host /
+// ff_weighted_resample_host / ff_observe_keep_host / ff_observe_grad_reduce_host, compiled from the host pass of the same
+// file).
 //
 // An observation xhat = x + n, n ~ N(0, diag(sigma^2)) with sigma known per object and dimension, has the convolved
 // density p_obs(xhat | sigma) = E_{z ~ N(0, I)}[p(xhat - sigma z)]; the extension estimates it from K draws per point,
@@ -97,6 +98,31 @@ FF_HD void moment2_add(double (&acc)[4], double w, const float (&v)[4], const do
         const double d = (double)v[j] - mean[j];
         acc[j] += w * (d * d);
     }
+}
+
+// ---- the gradient of the K-draw log-density (ff_observe_keep / ff_observe_grad_reduce) ------------------------------------
+// L = logsumexp_k lp_k - log K has dL / d lp_k = wn_k = w_k / W, the normalised weight of draw k, so with y_k = xhat -
+// sigma z_k the gradients of L are the wn-weighted sums of the rows' own gradients g_k = grad_y lp_k (and grad_c lp_k),
+// and dL / d sigma_d = -sum_k wn_k z_kd g_kd.  A draw whose normalised weight is 0, or below the caller's min_weight, adds
+// nothing (at most min_weight |g_k|): it is not KEPT, and its gradient row is never computed or read.
+
+// a point without a gradient: what has no posterior (weight_bad, or no draw above -inf)
+FF_HD bool point_degenerate(bool bad, double mx) { return bad || mx == -INFINITY; }
+
+// draw k of a point with maximum mx and weight sum W is kept iff its normalised weight is positive and >= min_weight
+FF_HD int32_t keep_draw(float lp, double mx, double W, double min_weight)
+{
+#pragma clang fp contract(off)
+    const double wn = weight(lp, mx) / W;
+    return wn > 0.0 && wn >= min_weight ? 1 : 0;
+}
+
+// one draw's share of a block of four dimensions of dL / d sigma, before the sign: acc += w (z g) -- the product of two
+// floats is exact in double
+FF_HD void noise_add(double (&acc)[4], double w, const float (&z)[4], const float (&g)[4])
+{
+#pragma clang fp contract(off)
+    for (int j = 0; j < 4; ++j) acc[j] += w * ((double)z[j] * (double)g[j]);
 }
 
 } // namespace observe

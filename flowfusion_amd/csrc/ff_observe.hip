@@ -19,6 +19,14 @@
 //                       and a minimum over the group.  The moments take one block of four dimensions at a time: every
 //                       lane adds its segment, a butterfly adds the lanes; the variance is a second pass about the mean.
 //
+//   ff_observe_keep     which of the K rows of a point carry weight in the GRADIENT of its log-mean-exp: keep[r K + k] =
+//                       (normalised weight > 0 and >= min_weight), from the reduction's own state and butterfly.
+//   ff_observe_grad_reduce  the gradient of the log-mean-exp from the kept rows' own gradients: sum_k w_k g_k / W for x and
+//                       the conditional, -sum_k w_k z_k g_k / W for noise_std with z regenerated, one block of four
+//                       dimensions at a time as the moments above.  Written in torch ops: a float64 softmax, K
+//                       ff_normal_fill launches, two weighted sums over [B K, D] temporaries -- here one pass over lp and
+//                       the kept rows; a row that was not kept is not read.
+//
 // All are streaming kernels in the style of ff_marginal.hip (roofline: HBM): grid-stride loops, 16-byte accesses where
 // the pointers and D allow (a scalar body otherwise, same arithmetic in the same order), consecutive lanes on consecutive
 // addresses, no LDS, no atomics.  A row of the expansion is shared by P = lanes_per_row(D) lanes (one block of four
@@ -308,6 +316,151 @@ __global__ __launch_bounds__(256) void weighted_resample_kernel(const ResampleAr
     }
 }
 
+struct KeepArgs {
+    const float* lp;
+    int32_t* keep;
+    long long B;
+    int K;
+    double min_weight;
+    int log_g;                      // log2 of the lanes per data point
+};
+
+__global__ __launch_bounds__(256) void observe_keep_kernel(const KeepArgs a)
+{
+    const int G = 1 << a.log_g, K = a.K;
+    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = (int)(gtid & (G - 1));
+    const long long ngroups = ((long long)gridDim.x * blockDim.x) >> a.log_g;
+    // (the bound is uniform over a group, as in logmeanexp_kernel: the shuffles below always find their partners)
+    for (long long pt = gtid >> a.log_g; pt < a.B; pt += ngroups) {
+        const float* lr = a.lp + pt * K;
+        int32_t* kr = a.keep + pt * K;
+        Lse st = lse_empty();
+        int bad = 0;
+        for (int k = lane; k < K; k += G) {
+            const float v = lr[k];
+            bad |= weight_bad(v);
+            lse_add(st, (double)v);
+        }
+        for (int off = 1; off < G; off <<= 1) {
+            Lse o;
+            o.m = __shfl_xor(st.m, off);
+            o.s1 = __shfl_xor(st.s1, off);
+            o.s2 = __shfl_xor(st.s2, off);
+            st = lse_merge(st, o);
+            bad |= __shfl_xor(bad, off);
+        }
+        const bool none = point_degenerate(bad, st.m);
+        for (int k = lane; k < K; k += G) kr[k] = none ? 0 : keep_draw(lr[k], st.m, st.s1, a.min_weight);
+    }
+}
+
+struct GradReduceArgs {
+    const float* lp;
+    const int32_t* row_of;
+    const float* gx_rows;
+    const float* gc_rows;
+    float* grad_x;
+    float* grad_c;
+    float* grad_noise_std;
+    long long B;
+    int D, C, K;
+    unsigned long long seed;
+    long long sample_offset;
+    int log_g;                      // log2 of the lanes per data point
+    int seg;                        // draws per lane: lane l holds the draws [l seg, (l + 1) seg) below K
+    int vec, cvec;                  // gx_rows / gc_rows move as 16-byte elements
+};
+
+__global__ __launch_bounds__(256) void observe_grad_reduce_kernel(const GradReduceArgs a)
+{
+    const int G = 1 << a.log_g, K = a.K, D = a.D, C = a.C, nblk = (D + 3) / 4, ncblk = (C + 3) / 4;
+    const long long gtid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = (int)(gtid & (G - 1));
+    const long long ngroups = ((long long)gridDim.x * blockDim.x) >> a.log_g;
+    const int k0 = lane * a.seg < K ? lane * a.seg : K, k1 = k0 + a.seg < K ? k0 + a.seg : K;
+    const float qnan = __builtin_nanf("");
+    // (the bound is uniform over a group, as in logmeanexp_kernel: the shuffles below always find their partners)
+    for (long long pt = gtid >> a.log_g; pt < a.B; pt += ngroups) {
+        const float* lr = a.lp + pt * K;
+        const int32_t* ro = a.row_of + pt * K;
+        const unsigned long long gs = (unsigned long long)(a.sample_offset + pt);
+
+        float mx = -INFINITY;
+        int bad = 0;
+        for (int k = k0; k < k1; ++k) {
+            const float v = lr[k];
+            bad |= weight_bad(v);
+            mx = v > mx ? v : mx;
+        }
+        for (int off = 1; off < G; off <<= 1) {
+            const float o = __shfl_xor(mx, off);
+            mx = o > mx ? o : mx;
+            bad |= __shfl_xor(bad, off);
+        }
+        if (point_degenerate(bad, (double)mx)) {
+            for (int d = lane; d < D; d += G) {
+                a.grad_x[pt * D + d] = qnan;
+                if (a.grad_noise_std) a.grad_noise_std[pt * D + d] = qnan;
+            }
+            if (a.gc_rows)
+                for (int c = lane; c < C; c += G) a.grad_c[pt * C + c] = qnan;
+            continue;
+        }
+
+        // the weights of the full sum W, kept or not: the lane's segment in index order, then the butterfly
+        const double m = (double)mx;
+        double W = 0.0;
+        for (int k = k0; k < k1; ++k) W += weight(lr[k], m);
+        for (int off = 1; off < G; off <<= 1) W += __shfl_xor(W, off);
+        const double rW = 1.0 / W;                            // one division per point: the gradients are sums times 1 / W
+
+        for (int blk = 0; blk < nblk; ++blk) {
+            const int d0 = 4 * blk;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0}, accz[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int k = k0; k < k1; ++k) {
+                const int row = ro[k];
+                if (row < 0) continue;
+                const double w = weight(lr[k], m);
+                float g[4];
+                load_block(a.gx_rows + (long long)row * D, d0, D, a.vec, g);
+                moment1_add(acc, w, g);
+                if (a.grad_noise_std) {
+                    float z[4];
+                    normals4(a.seed, gs, FF_OBS_NOISE_BASE + (uint32_t)k, (uint32_t)blk, z);
+                    noise_add(accz, w, z, g);
+                }
+            }
+            group_sum4(acc, G);
+            if (a.grad_noise_std) group_sum4(accz, G);
+            if (lane == 0)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (d0 + j < D) {
+                        a.grad_x[pt * D + d0 + j] = (float)(acc[j] * rW);
+                        if (a.grad_noise_std) a.grad_noise_std[pt * D + d0 + j] = (float)-(accz[j] * rW);
+                    }
+        }
+        if (a.gc_rows)
+            for (int blk = 0; blk < ncblk; ++blk) {
+                const int c0 = 4 * blk;
+                double acc[4] = {0.0, 0.0, 0.0, 0.0};
+                for (int k = k0; k < k1; ++k) {
+                    const int row = ro[k];
+                    if (row < 0) continue;
+                    float g[4];
+                    load_block(a.gc_rows + (long long)row * C, c0, C, a.cvec, g);
+                    moment1_add(acc, weight(lr[k], m), g);
+                }
+                group_sum4(acc, G);
+                if (lane == 0)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (c0 + j < C) a.grad_c[pt * C + c0 + j] = (float)(acc[j] * rW);
+            }
+    }
+}
+
 static unsigned stream_grid(long long threads)
 {
     // a few workgroups per CU (256 CUs) saturate HBM with 16-byte accesses; never more than needed (ff_aux.hip)
@@ -342,6 +495,21 @@ static bool resample_args_ok(const float* y, const float* lp, int64_t B, int32_t
 {
     if (!y || !lp || B < 0 || D < 1 || K < 1 || K > kMaxDraws || M < 0 || M > kMaxSamples) return false;
     return samples || index || mean || var;
+}
+
+static bool keep_args_ok(const float* lp, int64_t B, int32_t K, double min_weight, const int32_t* keep)
+{
+    return lp && keep && B >= 0 && K >= 1 && K <= kMaxDraws && min_weight >= 0.0 && min_weight < 1.0;
+}
+
+static bool grad_reduce_args_ok(const float* lp, const int32_t* row_of, const float* gx_rows, const float* gc_rows,
+                                const float* noise_std, int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K,
+                                const float* grad_x, const float* grad_c)
+{
+    if (!lp || !row_of || !gx_rows || !noise_std || !grad_x || B < 0 || D < 1 || K < 1 || K > kMaxDraws) return false;
+    if (std_row_stride != 0 && std_row_stride != D) return false;
+    if (gc_rows && (C < 1 || !grad_c)) return false;
+    return true;
 }
 
 } // namespace observe
@@ -405,7 +573,126 @@ extern "C" int ff_weighted_resample(const float* y, const float* lp, int64_t B, 
     return hipGetLastError() == hipSuccess ? FF_OK : FF_ERR_HIP;
 }
 
+extern "C" int ff_observe_keep(const float* lp, int64_t B, int32_t K, double min_weight, int32_t* keep, void* hip_stream)
+{
+    if (!keep_args_ok(lp, B, K, min_weight, keep)) return FF_ERR_BADARG;
+    if (B == 0) return FF_OK;
+    KeepArgs a;
+    a.lp = lp; a.keep = keep;
+    a.B = B; a.K = K;
+    a.min_weight = min_weight;
+    const int G = lanes_per_point(K);
+    a.log_g = log2_of(G);
+    hipLaunchKernelGGL(observe_keep_kernel, dim3(stream_grid((long long)B * G)), dim3(256), 0, (hipStream_t)hip_stream, a);
+    return hipGetLastError() == hipSuccess ? FF_OK : FF_ERR_HIP;
+}
+
+extern "C" int ff_observe_grad_reduce(const float* lp, const int32_t* row_of, const float* gx_rows, const float* gc_rows,
+                                      const float* noise_std, int32_t std_row_stride, int64_t B, int32_t D, int32_t C,
+                                      int32_t K, uint64_t seed, int64_t sample_offset, float* grad_x, float* grad_c,
+                                      float* grad_noise_std, void* hip_stream)
+{
+    if (!grad_reduce_args_ok(lp, row_of, gx_rows, gc_rows, noise_std, std_row_stride, B, D, C, K, grad_x, grad_c))
+        return FF_ERR_BADARG;
+    if (B == 0) return FF_OK;
+    GradReduceArgs a;
+    a.lp = lp; a.row_of = row_of; a.gx_rows = gx_rows; a.gc_rows = gc_rows;
+    a.grad_x = grad_x; a.grad_c = gc_rows ? grad_c : nullptr; a.grad_noise_std = grad_noise_std;
+    a.B = B; a.D = D; a.C = gc_rows ? C : 0; a.K = K;
+    a.seed = seed; a.sample_offset = sample_offset;
+    const int G = lanes_per_point(K);
+    a.log_g = log2_of(G);
+    a.seg = (K + G - 1) / G;
+    a.vec = (D & 3) == 0 && ((uintptr_t)gx_rows & 15) == 0;
+    a.cvec = gc_rows && (C & 3) == 0 && ((uintptr_t)gc_rows & 15) == 0;
+    hipLaunchKernelGGL(observe_grad_reduce_kernel, dim3(stream_grid((long long)B * G)), dim3(256), 0, (hipStream_t)hip_stream,
+                       a);
+    return hipGetLastError() == hipSuccess ? FF_OK : FF_ERR_HIP;
+}
+
 // ---- the host twins (CPU tests): the same header, rows and draws in index order ---------------------------------------
+extern "C" int ff_observe_keep_host(const float* lp, int64_t B, int32_t K, double min_weight, int32_t* keep)
+{
+    if (!keep_args_ok(lp, B, K, min_weight, keep)) return FF_ERR_BADARG;
+    for (int64_t r = 0; r < B; ++r) {
+        const float* lr = lp + r * K;
+        Lse st = lse_empty();
+        bool bad = false;
+        for (int k = 0; k < K; ++k) {
+            bad = bad || weight_bad(lr[k]);
+            lse_add(st, (double)lr[k]);
+        }
+        const bool none = point_degenerate(bad, st.m);
+        for (int k = 0; k < K; ++k) keep[r * K + k] = none ? 0 : keep_draw(lr[k], st.m, st.s1, min_weight);
+    }
+    return FF_OK;
+}
+
+extern "C" int ff_observe_grad_reduce_host(const float* lp, const int32_t* row_of, const float* gx_rows, const float* gc_rows,
+                                           const float* noise_std, int32_t std_row_stride, int64_t B, int32_t D, int32_t C,
+                                           int32_t K, uint64_t seed, int64_t sample_offset, float* grad_x, float* grad_c,
+                                           float* grad_noise_std)
+{
+    if (!grad_reduce_args_ok(lp, row_of, gx_rows, gc_rows, noise_std, std_row_stride, B, D, C, K, grad_x, grad_c))
+        return FF_ERR_BADARG;
+    const float qnan = nanf("");
+    if (!gc_rows) C = 0;
+    const int nblk = (D + 3) / 4, ncblk = (C + 3) / 4;
+    for (int64_t r = 0; r < B; ++r) {
+        const float* lr = lp + r * K;
+        const int32_t* ro = row_of + r * K;
+        float mx = -INFINITY;
+        bool bad = false;
+        for (int k = 0; k < K; ++k) {
+            bad = bad || weight_bad(lr[k]);
+            mx = lr[k] > mx ? lr[k] : mx;
+        }
+        if (point_degenerate(bad, (double)mx)) {
+            for (int d = 0; d < D; ++d) {
+                grad_x[r * D + d] = qnan;
+                if (grad_noise_std) grad_noise_std[r * D + d] = qnan;
+            }
+            for (int c = 0; c < C; ++c) grad_c[r * C + c] = qnan;
+            continue;
+        }
+        const double m = (double)mx;
+        double W = 0.0;
+        for (int k = 0; k < K; ++k) W += weight(lr[k], m);
+        const double rW = 1.0 / W;
+        for (int blk = 0; blk < nblk; ++blk) {
+            const int d0 = 4 * blk;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0}, accz[4] = {0.0, 0.0, 0.0, 0.0};
+            float g[4], z[4];
+            for (int k = 0; k < K; ++k) {
+                if (ro[k] < 0) continue;
+                const double w = weight(lr[k], m);
+                for (int j = 0; j < 4; ++j) g[j] = d0 + j < D ? gx_rows[(int64_t)ro[k] * D + d0 + j] : 0.f;
+                moment1_add(acc, w, g);
+                if (grad_noise_std) {
+                    normals4(seed, (uint64_t)(sample_offset + r), FF_OBS_NOISE_BASE + (uint32_t)k, (uint32_t)blk, z);
+                    noise_add(accz, w, z, g);
+                }
+            }
+            for (int j = 0; j < 4 && d0 + j < D; ++j) {
+                grad_x[r * D + d0 + j] = (float)(acc[j] * rW);
+                if (grad_noise_std) grad_noise_std[r * D + d0 + j] = (float)-(accz[j] * rW);
+            }
+        }
+        for (int blk = 0; blk < ncblk; ++blk) {
+            const int c0 = 4 * blk;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            float g[4];
+            for (int k = 0; k < K; ++k) {
+                if (ro[k] < 0) continue;
+                for (int j = 0; j < 4; ++j) g[j] = c0 + j < C ? gc_rows[(int64_t)ro[k] * C + c0 + j] : 0.f;
+                moment1_add(acc, weight(lr[k], m), g);
+            }
+            for (int j = 0; j < 4 && c0 + j < C; ++j) grad_c[r * C + c0 + j] = (float)(acc[j] * rW);
+        }
+    }
+    return FF_OK;
+}
+
 extern "C" int ff_weighted_resample_host(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M,
                                          uint64_t seed, int64_t sample_offset, float* samples, int32_t* index, float* mean,
                                          float* var)

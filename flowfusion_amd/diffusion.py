@@ -808,13 +808,21 @@ class ScoreModel(nn.Module):
         Fixed grids only (``method="rk4"`` / ``"dopri5_fixed"`` / ``"euler"`` with ``options={"step_size": h}``; the default
         grid is ONE step): adaptive methods, ``grid_constructor`` / ``perturb``, ``precision`` other than f32 and Hutch++ /
         XTrace models raise before the device is touched.  No parameter gradients, no torch.autograd integration (the call
-        runs under ``no_grad``), no gradients of ``log_prob_noisy``: see ``odeint.solve_logp_grad``."""
+        runs under ``no_grad``): see ``odeint.solve_logp_grad``; the gradient of ``log_prob_noisy`` is ``log_prob_noisy_grad``."""
         return self._log_prob_grad(x, conditional, method, options, probe, seed, sample_offset, num_probes)
 
     def _log_prob_grad(self, x, conditional, method, options, probe, seed, sample_offset, num_probes, in_shift=None,
                        in_scale=None, cond_tangent_scale=None):
         """``log_prob_grad`` proper; the affine input map and the conditional scale of the population wrappers as in
         ``_flow_vjp``."""
+        rng = self._logp_grad_checks(x, conditional, method, options, probe, seed, sample_offset, num_probes)
+        logp = self._logp_value(x, conditional, method, options, rng, num_probes, in_shift, in_scale)
+        gx, gc = self._logp_grad_rows(x, conditional, method, options, self.e if self.hutch else None, in_shift=in_shift,
+                                      in_scale=in_scale, cond_tangent_scale=cond_tangent_scale)
+        return logp, gx, gc
+
+    def _logp_grad_checks(self, x, conditional, method, options, probe, seed, sample_offset, num_probes):
+        """What ``log_prob_grad`` and ``log_prob_noisy_grad`` refuse, before the device is touched; returns the probes' key."""
         if (self.hutchpp or self.xtrace) and not self.hutch:
             raise ValueError("log-density gradients of a Hutch++ / XTrace model: the estimators' products are not differentiated "
                              "(the reference detaches them too); construct the model with hutchinson=True, or without an "
@@ -823,12 +831,21 @@ class ScoreModel(nn.Module):
         rng = trace_estimators.probe_rng(probe, seed, sample_offset, bool(self.hutch),
                                          "probe='philox' draws the probes of a Hutchinson model: construct it with hutchinson=True")
         odeint.check_logp_grad(self, x, method, options, conditional)
+        return rng
+
+    def _logp_value(self, x, conditional, method, options, rng, num_probes, in_shift=None, in_scale=None):
+        """The value half of ``log_prob_grad``: the fixed-grid ``log_prob`` [B, 1] of the rows ``x``; a Hutchinson model's
+        probes stay in ``self.e``."""
         xT, lp, _ = self._solve_forward(x, conditional, 0.0, 0.0, method, options, in_shift=in_shift, in_scale=in_scale,
                                         probe_rng=rng, num_probes=num_probes)
-        logp = lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
+        return lp + torch.sum(self.sde.prior(xT.shape).log_prob(xT), dim=1, keepdim=True)
+
+    def _logp_grad_rows(self, x, conditional, method, options, e, in_shift=None, in_scale=None, cond_tangent_scale=None):
+        """The gradient half of ``log_prob_grad``: ``(gx [B, D], gc [B, C] or None)`` of the rows ``x`` with the Hutchinson
+        probes ``e`` ([B, D] or [B, K, D]) of their value solve, or with the D unit probes of the exact trace (``e`` None)."""
         B, D = x.shape
-        if self.hutch:
-            probes = self.e if self.e.dim() == 3 else self.e.unsqueeze(1)
+        if e is not None:
+            probes = e if e.dim() == 3 else e.unsqueeze(1)
             weight = 1.0 / probes.shape[1]
         else:
             probes, weight = torch.eye(D, dtype=torch.float32, device=x.device).expand(B, D, D), 1.0
@@ -837,7 +854,65 @@ class ScoreModel(nn.Module):
         _, gx, gc = odeint.solve_logp_grad(self, x, t_span, method, options, probes.contiguous(), weight, cond=conditional,
                                            in_shift=in_shift, in_scale=in_scale, cond_tangent_scale=cond_tangent_scale,
                                            prior_grad=lambda y: -y / var)
-        return logp, gx, gc
+        return gx, gc
+
+    @torch.no_grad()
+    def log_prob_noisy_grad(self, x, noise_std, conditional=None, num_draws=16, *, method="rk4", options=None, seed=None,
+                            sample_offset=0, chunk_points=None, num_probes=1, min_weight=0.0, return_ess=False,
+                            return_noise_grad=False):
+        """Extension: ``log_prob_noisy`` on a fixed grid together with its gradient: returns ``(log_p [B, 1], grad_x [B, D],
+        grad_c [B, C] or None)`` -- then ``ess [B]`` with ``return_ess`` and ``grad_noise_std [B, D]`` with
+        ``return_noise_grad`` -- what HMC / NUTS or L-BFGS over the population hyper-parameters (``conditional``) of a
+        catalogue of measured objects needs: ``sum_r log_p[r]`` is the hierarchical likelihood, ``grad_c`` its gradient per
+        object.  ``log_p`` and ``ess`` are bitwise ``log_prob_noisy(x, noise_std, conditional, num_draws, method=method,
+        options=options, seed=seed, ..., return_ess=True)``.  With ``wn_k`` the normalised weight of draw k (double),
+        ``grad_x = sum_k wn_k grad_y lp_k``, ``grad_c = sum_k wn_k grad_c lp_k`` and ``grad_noise_std = -sum_k wn_k z_k
+        grad_y lp_k`` (per object and dimension, whatever the shape of ``noise_std``), ``grad lp_k`` the discrete adjoint of
+        ``log_prob_grad`` on row k: the exact gradient of the value returned at fixed draws -- and, on a ``hutchinson=True``
+        model, at fixed probes (the very probes of the value solve of those rows, ``probe="philox"`` under the same
+        ``seed``) -- at any step count.  On an exact-trace model the value comes from the exact-trace solve and the
+        gradient from the D unit probes with weight 1: D gradient rows per kept draw, and ``min_weight`` is the lever.
+
+        ``min_weight`` = m (0 <= m < 1): only draws with ``wn_k > 0`` and ``wn_k >= m`` go through the record and gradient
+        launches (typically most draws carry no weight: ess is a small fraction of K).  The sums keep the weights of the
+        full sum, not renormalised, so the truncation error is at most ``sum_skipped wn_k |grad lp_k| <= K m max |grad
+        lp|``; m = 0 keeps every draw of non-zero weight.  ``self.last_noisy_grad_stats`` = ``{"rows": B K, "rows_kept": n,
+        "gradient_rows": rows that reached the gradient launch}`` after the call.  A point with a NaN or +inf among its
+        rows' log-densities, or with no weight at all, has NaN gradients; its ``log_p`` is what ``log_prob_noisy`` gives.
+
+        Fixed grids only (``method="rk4"`` / ``"dopri5_fixed"`` / ``"euler"`` with ``options={"step_size": h}``; the default
+        grid is ONE step): every refusal of ``log_prob_grad`` applies, before the device is touched.  ``noise_std``,
+        ``num_draws``, ``seed``, ``sample_offset``, ``chunk_points``: as in ``log_prob_noisy``; any chunking and any slice of
+        the batch at its ``sample_offset`` give bitwise the same.  Out of scope: sharded entry points (slice), adaptive
+        methods, gradients of ``posterior_noisy``, parameter gradients and torch.autograd integration."""
+        return self._log_prob_noisy_grad(x, noise_std, conditional, num_draws, method, options, seed, sample_offset,
+                                         chunk_points, num_probes, min_weight, return_ess, return_noise_grad)
+
+    def _log_prob_noisy_grad(self, x, noise_std, conditional, num_draws, method, options, seed, sample_offset, chunk_points,
+                             num_probes, min_weight, return_ess, return_noise_grad, **maps):
+        """``log_prob_noisy_grad`` proper (``odeint.log_prob_noisy_grad`` around the two halves of ``log_prob_grad``);
+        ``maps``: the affine input map and the conditional scale of the population wrappers."""
+        value_maps = {k: v for k, v in maps.items() if k != "cond_tangent_scale"}
+        hutch = bool(self.hutch)
+
+        def checks():
+            self._logp_grad_checks(x, conditional, method, options, "philox" if hutch else "torch", 0 if hutch else None, 0,
+                                   num_probes)
+
+        def value_rows(y, c, extra):
+            rng = (extra["seed"], extra["sample_offset"]) if extra else None
+            lp = self._logp_value(y, c, method, options, rng, num_probes, **value_maps)
+            return lp, ((self.e if self.e.dim() == 3 else self.e.unsqueeze(1)) if hutch else None)
+
+        def grad_rows(y, c, probes):
+            gx, gc = self._logp_grad_rows(y, c, method, options, probes, **maps)
+            return gx, gc, y.shape[0] * (probes.shape[1] if hutch else y.shape[1])
+
+        self.last_noisy_grad_stats = {}
+        out = odeint.log_prob_noisy_grad(value_rows, grad_rows, hutch, x, noise_std, conditional, num_draws, method, seed,
+                                         sample_offset, chunk_points, min_weight, return_ess, return_noise_grad, checks=checks,
+                                         stats=self.last_noisy_grad_stats)
+        return (out[0].view(-1, 1),) + out[1:]
 
     @torch.no_grad()
     def log_prob_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-4, rtol=1e-4, method="dopri5",
@@ -967,6 +1042,11 @@ class _PopulationModel(nn.Module):
         scale`` (in the kernel), so that ``grad_x`` is in the units of the user's ``x`` and ``grad_c`` in those of the RAW
         conditional.  ``log_p`` is this wrapper's ``log_prob`` formula on the fixed grid of ``method`` / ``options`` (its
         ``log_prob`` itself is hard-wired to adaptive dopri5, which has no discrete adjoint)."""
+        cond, maps = self._logp_grad_maps(conditional)
+        return self.score_model._log_prob_grad(x, cond, method, options, probe, seed, sample_offset, num_probes, **maps)
+
+    def _logp_grad_maps(self, conditional):
+        """(normalised conditional, the maps of the inner score model's log-density gradients) in the user's units."""
         cond, maps = None, {"in_shift": self.shift, "in_scale": self.scale}
         if conditional is not None:
             C = int(self.model.n_conditionals)
@@ -974,7 +1054,22 @@ class _PopulationModel(nn.Module):
                     conditional.shape[1] != C:
                 raise ValueError(f"log-density gradients: conditional must be [batch, {C}] (and the wrapper a conditional one)")
             cond, maps = self._cond(conditional), dict(maps, cond_tangent_scale=self.conditional_scale)
-        return self.score_model._log_prob_grad(x, cond, method, options, probe, seed, sample_offset, num_probes, **maps)
+        return cond, maps
+
+    @torch.no_grad()
+    def _log_prob_noisy_grad(self, x, noise_std, conditional, num_draws, method, options, seed, sample_offset, chunk_points,
+                             num_probes, min_weight, return_ess, return_noise_grad):
+        """``log_prob_noisy_grad`` of the two wrappers: ``ScoreModel.log_prob_noisy_grad`` of the inner score model behind
+        ``(x - shift) / scale`` (in the kernel).  The noise lives in the data space of ``x``, so ``grad_x`` and
+        ``grad_noise_std`` are in the units of the user's ``x`` and ``noise_std``, ``grad_c`` in those of the RAW conditional
+        (normalised per point, then repeated for the draws).  ``log_p`` is ff_logmeanexp of this wrapper's ``log_prob``
+        formula on the fixed grid of ``method`` / ``options``, as in ``_log_prob_grad`` (its ``log_prob_noisy`` itself is
+        hard-wired to adaptive dopri5, which has no discrete adjoint)."""
+        cond, maps = self._logp_grad_maps(conditional)
+        out = self.score_model._log_prob_noisy_grad(x, noise_std, cond, num_draws, method, options, seed, sample_offset,
+                                                    chunk_points, num_probes, min_weight, return_ess, return_noise_grad, **maps)
+        self.last_noisy_grad_stats = self.score_model.last_noisy_grad_stats
+        return out
 
     @torch.no_grad()
     def _log_prob_noisy(self, x, noise_std, conditional, num_draws, atol, rtol, seed, sample_offset, chunk_points,
@@ -1033,6 +1128,15 @@ class PopulationModelDiffusion(_PopulationModel):
         if conditional is not None:
             raise ValueError("log-density gradients: this model has no conditional inputs")
         return self._log_prob_grad(x, None, method, options, probe, seed, sample_offset, num_probes)
+
+    def log_prob_noisy_grad(self, x, noise_std, num_draws=16, *, method="rk4", options=None, seed=None, sample_offset=0,
+                            chunk_points=None, num_probes=1, min_weight=0.0, return_ess=False, return_noise_grad=False):
+        """Extension: ``ScoreModel.log_prob_noisy_grad`` in the units of this wrapper: ``(log_p [B, 1], grad_x [B, D], None
+        [, ess [B]] [, grad_noise_std [B, D]])`` of observations ``x`` measured with Gaussian errors ``noise_std``, on the
+        fixed grid of ``method`` / ``options`` (the default grid is ONE rk4 step: pass ``options={"step_size": h}``).
+        ``min_weight`` and ``self.last_noisy_grad_stats``: as there.  See ``_log_prob_noisy_grad``."""
+        return self._log_prob_noisy_grad(x, noise_std, None, num_draws, method, options, seed, sample_offset, chunk_points,
+                                         num_probes, min_weight, return_ess, return_noise_grad)
 
     def flow_jvp(self, x, tangents, *, direction="to_data", method="rk4", options=None):
         """Extension: ``ScoreModel.flow_jvp`` in the units of this wrapper: ``to_data`` differentiates ``forward(x)``
@@ -1104,6 +1208,18 @@ class PopulationModelDiffusionConditional(_PopulationModel):
         hyper-parameters), on the fixed grid of ``method`` / ``options`` (the default grid is ONE rk4 step: pass
         ``options={"step_size": h}``).  This wrapper's score model takes the exact trace.  See ``_log_prob_grad``."""
         return self._log_prob_grad(x, conditional, method, options, probe, seed, sample_offset, num_probes)
+
+    def log_prob_noisy_grad(self, x, noise_std, conditional=None, num_draws=16, *, method="rk4", options=None, seed=None,
+                            sample_offset=0, chunk_points=None, num_probes=1, min_weight=0.0, return_ess=False,
+                            return_noise_grad=False):
+        """Extension: ``ScoreModel.log_prob_noisy_grad`` in the units of this wrapper: ``(log_p [B, 1], grad_x [B, D],
+        grad_c [B, C] [, ess [B]] [, grad_noise_std [B, D]])`` of observations ``x`` measured with Gaussian errors
+        ``noise_std``, ``grad_c`` with respect to the RAW conditional (the population hyper-parameters: ``grad_c.sum(0)`` is
+        the gradient of the hierarchical likelihood of a catalogue that shares them), on the fixed grid of ``method`` /
+        ``options`` (the default grid is ONE rk4 step: pass ``options={"step_size": h}``).  This wrapper's score model takes
+        the exact trace: D gradient rows per kept draw, ``min_weight`` is the lever.  See ``_log_prob_noisy_grad``."""
+        return self._log_prob_noisy_grad(x, noise_std, conditional, num_draws, method, options, seed, sample_offset,
+                                         chunk_points, num_probes, min_weight, return_ess, return_noise_grad)
 
     def flow_jvp(self, x, tangents=None, conditional=None, conditional_tangents=None, *, direction="to_data", method="rk4",
                  options=None):

@@ -269,35 +269,107 @@ class _FlowBase(nn.Module):
 
         Fixed grids only (``method="rk4"`` / ``"dopri5_fixed"`` / ``"euler"`` with ``options={"step_size": h}``; the default
         grid is ONE step): adaptive methods, ``grid_constructor`` / ``perturb`` and ``precision`` other than f32 raise
-        before the device is touched.  No parameter gradients, no torch.autograd integration, no gradients of
-        ``log_prob_noisy``."""
-        C = getattr(self, "conditional_dimension", 0)
-        cond, kw = None, {}
-        if conditional is not None:
-            if C == 0:
-                raise ValueError("log-density gradients: this model has no conditional inputs")
-            if not torch.is_tensor(conditional) or conditional.dim() != 2 or conditional.shape[1] != C:
-                raise ValueError(f"log-density gradients: conditional must be [batch, {C}]")
-            cond, kw = self._norm_cond(conditional), {"cond_tangent_scale": self.conditional_scale}
+        before the device is touched.  No parameter gradients, no torch.autograd integration; the gradient of
+        ``log_prob_noisy`` is ``log_prob_noisy_grad``."""
+        cond, kw = self._logp_grad_cond(conditional)
         K = trace_estimators.check_num_probes(num_probes, hutchinson, "pass hutchinson=True")
         rng = self._probe_rng(probe, seed, sample_offset, hutchinson)
         odeint.check_logp_grad(self, x, method, options, cond)
+        logp, probes = self._logp_value(x, conditional, cond, method, options, hutchinson, K, rng)
+        gx, gc = self._logp_grad_rows(x, cond, method, options, probes, kw)
+        return logp.view(-1, 1), gx, gc
+
+    def _logp_grad_cond(self, conditional):
+        """(normalised conditional, keywords of ``odeint.solve_logp_grad``) of a raw ``conditional``, checked."""
+        C = getattr(self, "conditional_dimension", 0)
+        if conditional is None:
+            return None, {}
+        if C == 0:
+            raise ValueError("log-density gradients: this model has no conditional inputs")
+        if not torch.is_tensor(conditional) or conditional.dim() != 2 or conditional.shape[1] != C:
+            raise ValueError(f"log-density gradients: conditional must be [batch, {C}]")
+        return self._norm_cond(conditional), {"cond_tangent_scale": self.conditional_scale}
+
+    def _logp_value(self, x, conditional, cond, method, options, hutchinson, K, rng):
+        """The value half of ``_log_prob_grad``: ``(log_p [B], probes [B, K, D] or None)``, the fixed-grid ``log_prob`` of the
+        rows ``x`` and the Hutchinson probes it took (None: the exact trace).  ``cond``: ``conditional`` normalised."""
         xn = (x - self.target_shift) / self.target_scale
         t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
         norm_only = () if conditional is None else (conditional,)
-        B, D = x.shape
         if hutchinson:
             kept = []
             xT, logj, _ = odeint.solve_hutchinson(self, xn, t_span, method, options, 1e-5, 1e-5, K, rng, keep=kept.append,
                                                   cond=cond, norm_only=norm_only)
-            probes, weight = (kept[-1] if K > 1 else kept[-1].unsqueeze(1)), 1.0 / K
+            probes = kept[-1] if K > 1 else kept[-1].unsqueeze(1)
         else:
             xT, logj = self._solve(xn, t_span, method, options, MODE_EXACT, 1e-5, 1e-5, cond=cond, norm_only=norm_only)
-            probes, weight = torch.eye(D, dtype=torch.float32, device=x.device).expand(B, D, D), 1.0
+            probes = None
         base = torch.sum(-0.5 * xT ** 2 - 0.5 * torch.log(self.twopi), dim=1)
-        logp = base + logj.view(-1, 1).squeeze(1) - torch.sum(torch.log(self.target_scale))
+        return base + logj.view(-1, 1).squeeze(1) - torch.sum(torch.log(self.target_scale)), probes
+
+    def _logp_grad_rows(self, x, cond, method, options, probes, kw):
+        """The gradient half of ``_log_prob_grad``: ``(gx [B, D], gc [B, C] or None)`` of the rows ``x`` with the probes of
+        their value solve, or with the D unit probes of the exact trace (``probes`` None)."""
+        B, D = x.shape
+        xn = (x - self.target_shift) / self.target_scale
+        t_span = torch.tensor([0.0, 1.0], dtype=torch.float32)
+        if probes is not None:
+            weight = 1.0 / probes.shape[1]
+        else:
+            probes, weight = torch.eye(D, dtype=torch.float32, device=x.device).expand(B, D, D), 1.0
         _, gx, gc = odeint.solve_logp_grad(self, xn, t_span, method, options, probes.contiguous(), weight, cond=cond, **kw)
-        return logp.view(-1, 1), gx / self.target_scale, gc
+        return gx / self.target_scale, gc
+
+    @torch.no_grad()
+    def _log_prob_noisy_grad(self, x, noise_std, conditional, num_draws, method, options, hutchinson, seed, sample_offset,
+                             chunk_points, num_probes, min_weight, return_ess, return_noise_grad):
+        """``log_prob_noisy_grad`` of both flows (extension): ``log_prob_noisy`` on a fixed grid with its gradient, ``(log_p
+        [B, 1], grad_x [B, D], grad_c [B, C] or None)`` -- then ``ess [B]`` with ``return_ess`` and ``grad_noise_std [B, D]``
+        with ``return_noise_grad`` -- in the units of the target-space ``x``, its ``noise_std`` and the raw ``conditional``:
+        what HMC / NUTS or L-BFGS over the population hyper-parameters of a catalogue of measured objects needs.  ``log_p``
+        (as a column) and ``ess`` are bitwise ``log_prob_noisy(x, noise_std, [conditional,] num_draws, method=method,
+        options=options, hutchinson=hutchinson, seed=seed, ..., return_ess=True)``.  With ``wn_k`` the normalised weight of
+        draw k (double), ``grad_x = sum_k wn_k grad_y lp_k``, ``grad_c = sum_k wn_k grad_c lp_k`` and ``grad_noise_std = -sum_k
+        wn_k z_k grad_y lp_k`` (per object and dimension, whatever the shape of ``noise_std``), ``grad lp_k`` the discrete
+        adjoint of ``_log_prob_grad`` on row k: the exact gradient of the value returned at fixed draws -- and, with
+        ``hutchinson=True``, at fixed probes (the very probes of the value solve of those rows, ``probe="philox"`` under the
+        same ``seed``) -- at any step count.  ``hutchinson=False``: the value comes from the exact-trace solve and the
+        gradient from the D unit probes with weight 1, D gradient rows per kept draw: ``min_weight`` is the lever.
+
+        ``min_weight`` = m (0 <= m < 1): only draws with ``wn_k > 0`` and ``wn_k >= m`` go through the record and gradient
+        launches.  The sums keep the weights of the full sum, not renormalised, so the truncation error is at most
+        ``sum_skipped wn_k |grad lp_k| <= K m max |grad lp|``; m = 0 keeps every draw of non-zero weight.
+        ``self.last_noisy_grad_stats`` = ``{"rows": B K, "rows_kept": n, "gradient_rows": rows that reached the gradient
+        launch}`` after the call.  A point with a NaN or +inf among its rows' log-densities, or with no weight at all, has
+        NaN gradients; its ``log_p`` is what ``log_prob_noisy`` gives.
+
+        Fixed grids only: every refusal of ``log_prob_grad`` applies, before the device is touched.  ``noise_std``,
+        ``num_draws``, ``seed``, ``sample_offset``, ``chunk_points``: as in ``log_prob_noisy``; any chunking and any slice of
+        the batch at its ``sample_offset`` give bitwise the same.  Out of scope: sharded entry points (slice), adaptive
+        methods, gradients of ``posterior_noisy``, parameter gradients and torch.autograd integration."""
+        hutchinson = bool(hutchinson)
+        K = 1
+
+        def checks():
+            nonlocal K
+            cond, _ = self._logp_grad_cond(conditional)
+            K = trace_estimators.check_num_probes(num_probes, hutchinson, "pass hutchinson=True")
+            odeint.check_logp_grad(self, x, method, options, cond)
+
+        def value_rows(y, c, extra):
+            rng = (extra["seed"], extra["sample_offset"]) if extra else None
+            return self._logp_value(y, c, None if c is None else self._norm_cond(c), method, options, hutchinson, K, rng)
+
+        def grad_rows(y, c, probes):
+            cond, kw = self._logp_grad_cond(c)
+            gx, gc = self._logp_grad_rows(y, cond, method, options, probes, kw)
+            return gx, gc, y.shape[0] * (K if hutchinson else y.shape[1])
+
+        self.last_noisy_grad_stats = {}
+        out = odeint.log_prob_noisy_grad(value_rows, grad_rows, hutchinson, x, noise_std, conditional, num_draws, method, seed,
+                                         sample_offset, chunk_points, min_weight, return_ess, return_noise_grad, checks=checks,
+                                         stats=self.last_noisy_grad_stats)
+        return (out[0].view(-1, 1),) + out[1:]
 
     # -- the public methods' bodies, written once (``conditional=None``: the unconditional flow) -----------------------------
     def compute_linear_velocity_field(self, x0, xT, t):
@@ -444,6 +516,15 @@ class ODEFlow(_FlowBase):
             raise ValueError("log-density gradients: this model has no conditional inputs")
         return self._log_prob_grad(x, None, method, options, hutchinson, probe, seed, sample_offset, num_probes)
 
+    def log_prob_noisy_grad(self, x, noise_std, num_draws: int = 16, *, method: str = "rk4", options: Optional[dict] = None,
+                            hutchinson: bool = False, seed: Optional[int] = None, sample_offset: int = 0,
+                            chunk_points: Optional[int] = None, num_probes: int = 1, min_weight: float = 0.0,
+                            return_ess: bool = False, return_noise_grad: bool = False):
+        """Extension: ``(log_p [B, 1], grad_x [B, D], None [, ess [B]] [, grad_noise_std [B, D]])``: ``log_prob_noisy`` on a
+        fixed grid and its gradient with respect to the observations and their error bars (see ``_log_prob_noisy_grad``)."""
+        return self._log_prob_noisy_grad(x, noise_std, None, num_draws, method, options, hutchinson, seed, sample_offset,
+                                         chunk_points, num_probes, min_weight, return_ess, return_noise_grad)
+
     def log_prob_noisy(self, x, noise_std, num_draws: int = 16, atol: float = 1e-5, rtol: float = 1e-5,
                        method: str = "dopri5", options: Optional[dict] = None, *, hutchinson: bool = False,
                        seed: Optional[int] = None, sample_offset: int = 0, chunk_points: Optional[int] = None,
@@ -534,6 +615,17 @@ class ConditionalODEFlow(_FlowBase):
         """Extension: ``(log_p [B, 1], grad_x [B, D], grad_c [B, C])``: ``log_prob`` on a fixed grid and its gradient with
         respect to ``x`` and the raw ``conditional`` (see ``_log_prob_grad``)."""
         return self._log_prob_grad(x, conditional, method, options, hutchinson, probe, seed, sample_offset, num_probes)
+
+    def log_prob_noisy_grad(self, x, noise_std, conditional, num_draws: int = 16, *, method: str = "rk4",
+                            options: Optional[dict] = None, hutchinson: bool = False, seed: Optional[int] = None,
+                            sample_offset: int = 0, chunk_points: Optional[int] = None, num_probes: int = 1,
+                            min_weight: float = 0.0, return_ess: bool = False, return_noise_grad: bool = False):
+        """Extension: ``(log_p [B, 1], grad_x [B, D], grad_c [B, C] [, ess [B]] [, grad_noise_std [B, D]])``: ``log_prob_noisy``
+        on a fixed grid and its gradient with respect to the observations, the raw ``conditional`` (the population
+        hyper-parameters: ``grad_c.sum(0)`` is the gradient of the hierarchical likelihood of a catalogue that shares them)
+        and the error bars (see ``_log_prob_noisy_grad``)."""
+        return self._log_prob_noisy_grad(x, noise_std, conditional, num_draws, method, options, hutchinson, seed,
+                                         sample_offset, chunk_points, num_probes, min_weight, return_ess, return_noise_grad)
 
     def log_prob_noisy(self, x, noise_std, conditional, num_draws: int = 16, atol: float = 1e-5, rtol: float = 1e-5,
                        method: str = "dopri5", options: Optional[dict] = None, *, hutchinson: bool = False,

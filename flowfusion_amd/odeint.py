@@ -605,7 +605,8 @@ def solve_logp_grad(front, x, t_span, method, options, probes, probe_weight, con
 
     Refusals: ``_pull_checks``', under the name "log-density gradients".  Out of scope: parameter gradients and
     torch.autograd integration, adaptive control, a multi-probe column layout, twins, split precision, non-SiLU units, a
-    module-path fallback, sharded entry points (rows are independent: slice), gradients of ``log_prob_noisy``."""
+    module-path fallback, sharded entry points (rows are independent: slice).  The gradient of ``log_prob_noisy`` is
+    ``log_prob_noisy_grad`` below, around this function."""
     net, plan, B, D, K, C = _pull_checks(front, x, method, options, probes, cond, what="log-density gradients", tile_limit=False)
     tab = solvers.plan_ode(t_span, method, options)          # (rows of a fixed-grid ODE method: none carries a noise flag)
     width = int(plan.width)
@@ -706,24 +707,18 @@ def log_prob_noisy(log_prob_rows, randomised, x, noise_std, cond, num_draws, met
     return (out, ess) if return_ess else out
 
 
-def _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, method, seed, sample_offset, chunk_points,
-                    want_ess, num_samples):
-    """The loop over chunks of ``log_prob_noisy`` and ``posterior_noisy``: its checks, the chunk rule and the seed draw,
-    then per chunk expand -> the model's ``log_prob`` -> the reductions.  Returns ``(log_p [B], ess [B] or None,
-    posterior)``; with ``num_samples`` = M not None the chunk's particles and log-densities also go through
-    ff_weighted_resample before they are dropped, ``posterior`` = (samples [B, M, D], index [B, M], mean, var [B, D]) --
-    else None."""
+def _observe_args(what, x, num_draws, num_samples, method, chunk_points):
+    """The checks of ``log_prob_noisy``, ``posterior_noisy`` and ``log_prob_noisy_grad`` that touch no device, and the chunk
+    rule: ``(K, M or None, points per chunk)``."""
     K = int(num_draws)
     if not 1 <= K <= _native.MAX_OBS_DRAWS:
         raise ValueError(f"num_draws={num_draws}: 1 .. {_native.MAX_OBS_DRAWS} noise draws per data point")
     M = None if num_samples is None else int(num_samples)
     if M is not None and not 0 <= M <= _native.MAX_OBS_SAMPLES:
         raise ValueError(f"num_samples={num_samples}: 0 .. {_native.MAX_OBS_SAMPLES} posterior draws per data point")
-    what = "log_prob_noisy" if M is None else "posterior_noisy"
     if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
         raise ValueError(f"{what}: x must be a [batch, dim] float32 tensor")
     B = int(x.shape[0])
-    std = noise_std_tensor(noise_std, x)
     if method not in solvers.FIXED_METHODS:
         if chunk_points is not None:
             raise ValueError(f"chunk_points with method={method!r}: an adaptive solve takes its step size from the error "
@@ -737,9 +732,26 @@ def _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, me
         chunk = int(chunk_points)
         if chunk < 1:
             raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-    seed, first = int(seed), int(sample_offset)
+    return K, M, chunk
+
+
+def _observe_seed(seed):
+    """``seed`` of the noise draws; None draws a 63-bit one from torch's default generator."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
+
+
+def _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, method, seed, sample_offset, chunk_points,
+                    want_ess, num_samples):
+    """The loop over chunks of ``log_prob_noisy`` and ``posterior_noisy``: its checks, the chunk rule and the seed draw,
+    then per chunk expand -> the model's ``log_prob`` -> the reductions.  Returns ``(log_p [B], ess [B] or None,
+    posterior)``; with ``num_samples`` = M not None the chunk's particles and log-densities also go through
+    ff_weighted_resample before they are dropped, ``posterior`` = (samples [B, M, D], index [B, M], mean, var [B, D]) --
+    else None."""
+    what = "log_prob_noisy" if num_samples is None else "posterior_noisy"
+    K, M, chunk = _observe_args(what, x, num_draws, num_samples, method, chunk_points)
+    B = int(x.shape[0])
+    std = noise_std_tensor(noise_std, x)
+    seed, first = _observe_seed(seed), int(sample_offset)
     x = x.detach().contiguous()
     cond = _native.f32_on(cond, x.device)
     out = torch.empty(B, dtype=torch.float32, device=x.device)
@@ -789,6 +801,71 @@ def posterior_noisy(log_prob_rows, randomised, x, noise_std, cond, num_draws, nu
     out, ess, (samples, index, mean, var) = _observe_chunks(log_prob_rows, randomised, x, noise_std, cond, num_draws, method,
                                                             seed, sample_offset, chunk_points, True, num_samples)
     return NoisyPosterior(samples, out, ess, mean, var, index)
+
+
+def log_prob_noisy_grad(value_rows, grad_rows, randomised, x, noise_std, cond, num_draws, method, seed, sample_offset,
+                        chunk_points, min_weight, return_ess, return_noise_grad, checks=None, stats=None):
+    """What every front end's ``log_prob_noisy_grad`` does: ``log_prob_noisy`` on a fixed grid with its gradient, ``(log_p
+    [B], grad_x [B, D], grad_c [B, C] or None [, ess [B]] [, grad_noise_std [B, D]])``.  With ``lp_k`` the log-density of row
+    ``y_k = x - noise_std z_k`` and ``wn_k = exp(lp_k - max lp) / W`` its normalised weight (double), the gradient of
+    ``logsumexp_k lp_k - log K`` at fixed draws is ``sum_k wn_k grad lp_k`` for ``x`` and ``cond`` and ``-sum_k wn_k z_k
+    grad_y lp_k`` for ``noise_std`` (per object and dimension, whatever the shape of ``noise_std``).
+
+    Per chunk of points (the chunk rule, checks and seed of ``log_prob_noisy``): ff_observe_expand -> ``value_rows(y,
+    cond_rows, extra)`` -> ``(lp [rows], probes [rows, P, D] or None)``, the model's fixed-grid log-density of the rows and, on
+    a ``randomised`` (Hutchinson) model, the probes it took (``extra`` keys them as in ``log_prob_noisy``) -> ff_logmeanexp
+    (``log_p`` and ``ess``: bitwise ``log_prob_noisy``'s) -> ff_observe_keep -> the kept rows, their conditionals and probes
+    gathered in order -> ``grad_rows(y_kept, cond_kept, probes_kept)`` -> ``(gx [n, D], gc [n, C] or None, rows launched)``,
+    the record and gradient launches of ``solve_logp_grad`` in the user's units -> ff_observe_grad_reduce.  Only kept rows
+    reach the gradient launches: draw k is kept iff ``wn_k > 0`` and ``wn_k >= min_weight``, and the sums take the weights of
+    the FULL ``W``, not renormalised, so a ``min_weight`` = m > 0 truncates by at most ``sum_skipped wn_k |grad lp_k| <= K m
+    max |grad lp|``.  A point with a NaN or +inf among its ``lp``, or with ``W = 0``, has NaN gradients.  Rows and points are
+    independent: any chunking, and any slice of the batch at its ``sample_offset``, gives bitwise the same.
+
+    ``checks()``: the front end's refusals, run after the host-only argument checks and before the device is touched.
+    ``stats``: a dict that receives ``rows``, ``rows_kept`` and ``gradient_rows`` (what ``grad_rows`` launched)."""
+    m = float(min_weight)
+    if not 0.0 <= m < 1.0:
+        raise ValueError(f"min_weight={min_weight}: a normalised weight, 0 <= min_weight < 1 (0 keeps every draw of non-zero "
+                         "weight)")
+    K, _, chunk = _observe_args("log_prob_noisy_grad", x, num_draws, None, method, chunk_points)
+    if checks is not None:
+        checks()
+    B, D = int(x.shape[0]), int(x.shape[1])
+    std = noise_std_tensor(noise_std, x)
+    seed, first = _observe_seed(seed), int(sample_offset)
+    x = x.detach().contiguous()
+    cond = _native.f32_on(cond, x.device)
+    C = 0 if cond is None else int(cond.shape[1])
+    new = lambda cols: torch.empty(B, cols, dtype=torch.float32, device=x.device)
+    out, ess = new(1).view(B), (new(1).view(B) if return_ess else None)
+    gx, gc, gs = new(D), (new(C) if C > 0 else None), (new(D) if return_noise_grad else None)
+    kept = launched = 0
+    for lo in range(0, B, chunk):
+        hi = min(B, lo + chunk)
+        std_c = std if std.dim() == 1 else std[lo:hi]
+        y, ck = _native.observe_expand(x[lo:hi], std_c, K, seed, first + lo, None if cond is None else cond[lo:hi])
+        extra = {"probe": "philox", "seed": seed, "sample_offset": (first + lo) * K} if randomised else {}
+        lp, probes = value_rows(y, ck, extra)
+        lp = lp.detach().to(torch.float32).contiguous().view(-1)
+        _native.logmeanexp(lp, K, out[lo:hi], None if ess is None else ess[lo:hi])
+        keep = _native.observe_keep(lp, K, m)
+        rows = torch.nonzero(keep).view(-1)                 # the kept rows in order: row_of is their rank
+        n = int(rows.numel())
+        row_of = torch.where(keep > 0, torch.cumsum(keep, 0, dtype=torch.int32) - 1, -1).to(torch.int32)
+        if n == 0:
+            gxr, gcr = y.new_zeros(0, D), (None if C == 0 else y.new_zeros(0, C))
+        else:
+            take = lambda t: None if t is None else (t if n == t.shape[0] else t.index_select(0, rows))
+            gxr, gcr, ran = grad_rows(take(y), take(ck), take(probes))
+            launched += int(ran)
+        kept += n
+        _native.observe_grad_reduce(lp, row_of, gxr, gcr, std_c, K, seed, first + lo, return_noise_grad, gx[lo:hi],
+                                    None if gc is None else gc[lo:hi], None if gs is None else gs[lo:hi])
+        del y, ck, lp, probes, gxr, gcr
+    if stats is not None:
+        stats.update(rows=B * K, rows_kept=kept, gradient_rows=launched)
+    return (out, gx, gc) + ((ess,) if return_ess else ()) + ((gs,) if return_noise_grad else ())
 
 
 def _host_adaptive(front, step, x, t, sign, method, options, mode, atol, rtol, norm_only):

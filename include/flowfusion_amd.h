@@ -771,6 +771,50 @@ int ff_weighted_resample(const float* y, const float* lp, int64_t B, int32_t D, 
 int ff_weighted_resample_host(const float* y, const float* lp, int64_t B, int32_t D, int32_t K, int32_t M, uint64_t seed,
                               int64_t sample_offset, float* samples, int32_t* index, float* mean, float* var);
 
+/* ---- the gradient of the K-draw log-density of noisy observations (csrc/ff_observe.hip, csrc/ff_observe.h) ----------
+ *
+ * L[r] = logsumexp_k lp[r K + k] - log K (ff_logmeanexp) of the rows y_k = xhat - sigma z_k has dL / d lp_k = wn_k, the
+ * normalised weight of draw k, so its gradients are weighted sums of the rows' own gradients g_k = grad_y lp_k, h_k =
+ * grad_c lp_k (whatever computes them; the library's: ff_mlp_ode_launch_logp_grad), per data point r, in double:
+ *     w_k = exp((double)lp[r K + k] - max_k lp),   W = sum_k w_k,   wn_k = w_k / W
+ *     grad_x[r][d]         =  sum_k w_k g_kd / W
+ *     grad_c[r][c]         =  sum_k w_k h_kc / W
+ *     grad_noise_std[r][d] = -sum_k w_k z_kd g_kd / W,   z_kd = z(seed, sample_offset + r, FF_OBS_NOISE_BASE + k, d)
+ * the exact gradient of L at fixed draws with respect to xhat, the conditional and sigma (per object and dimension,
+ * whatever the layout of noise_std).  The sums run over KEPT draws only, with the weights of the full W:
+ * ff_observe_keep:  keep[r K + k] = (wn_k > 0 && wn_k >= min_weight) ? 1 : 0, in double, W and the maximum from the
+ *   running state and the butterfly of ff_logmeanexp.  0 <= min_weight < 1; 0 keeps every draw of non-zero weight.  A
+ *   skipped draw would have added wn_k g_k: the truncation is at most sum_skipped wn_k |g_k| <= K min_weight max |g|.
+ *   A degenerate point (a NaN or +inf among its lp, or W = 0: all -inf) keeps nothing.  lp [B K]; keep [B K] int32.
+ *   FF_ERR_BADARG: lp or keep NULL; B < 0; K outside 1 .. FF_MAX_OBS_DRAWS; min_weight outside [0, 1).
+ * ff_observe_grad_reduce:  row_of [B K] int32 says where the gradient row of draw (r, k) lies: row row_of[r K + k] of
+ *   gx_rows [n][D] and gc_rows [n][C], or < 0 for a draw that was not kept -- no row of it is read and it adds nothing (the
+ *   order-preserving compaction of keep: cumsum(keep) - 1 where kept; every entry must be below n).  gc_rows may be NULL
+ *   (C and grad_c are then ignored), grad_noise_std may be NULL.  noise_std / std_row_stride are those of
+ *   ff_observe_expand and are checked like them; the derivative of xhat - sigma z in sigma is -z at any sigma, so their
+ *   values are not read.  A lane group of lanes_per_point(K) lanes with contiguous segments of draws, as
+ *   ff_weighted_resample: the weights recomputed from lp, one block of four dimensions at a time accumulated over the
+ *   lane's draws in index order and merged by the fixed butterfly, times the double 1 / W (one division per point),
+ *   rounded to fp32 once.  A degenerate point writes NaN to its three gradients.  K = 1 with a finite lp: grad_x and
+ *   grad_c are the row bit for bit, grad_noise_std is -z g rounded once.  16-byte accesses on gx_rows (gc_rows) where
+ *   they are 16-byte aligned and D % 4 == 0 (C % 4 == 0), a scalar body otherwise.
+ *   FF_ERR_BADARG, before anything is enqueued: lp, row_of, gx_rows, noise_std or grad_x NULL; B < 0; D < 1; K outside
+ *   1 .. FF_MAX_OBS_DRAWS; std_row_stride neither 0 nor D; gc_rows given with C < 1 or grad_c NULL.
+ * A data point's results are fixed by K and its own data, not by B, its position or the launch: chunks (sample_offset +
+ * first point of the chunk) and shards give bitwise the same.  DEVICE pointers, enqueued on hip_stream; B == 0 is FF_OK
+ * without a launch.  The _host twins run the same header arithmetic on HOST pointers with the draws in index order (sums
+ * agree to double rounding; the normals through libm).
+ */
+int ff_observe_keep(const float* lp, int64_t B, int32_t K, double min_weight, int32_t* keep, void* hip_stream);
+int ff_observe_grad_reduce(const float* lp, const int32_t* row_of, const float* gx_rows, const float* gc_rows,
+                           const float* noise_std, int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K,
+                           uint64_t seed, int64_t sample_offset, float* grad_x, float* grad_c, float* grad_noise_std,
+                           void* hip_stream);
+int ff_observe_keep_host(const float* lp, int64_t B, int32_t K, double min_weight, int32_t* keep);
+int ff_observe_grad_reduce_host(const float* lp, const int32_t* row_of, const float* gx_rows, const float* gc_rows,
+                                const float* noise_std, int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K,
+                                uint64_t seed, int64_t sample_offset, float* grad_x, float* grad_c, float* grad_noise_std);
+
 /* ---- Hutch++ / XTrace divergence estimates from recorded Jacobians (csrc/ff_trace.hip, csrc/ff_trace_est.h) ----
  *
  * Replaces the two estimator branches of ScoreModel.forward, diffusion.py:336-400 (Hutch++) and :402-481 (XTrace), for
