@@ -95,6 +95,7 @@ PUSH_KERNEL_BASE = 0x40000                                  # FF_PUSH_KERNEL_BAS
 STATUS_NOISE_ROW = 4                                        # FF_STATUS_NOISE_ROW
 MAX_PUSH_TANGENTS = 15                                      # tangent columns beside the value column of a 16-column tile
 PULL_KERNEL_BASE = 0x50000                                  # FF_PULL_KERNEL_BASE
+PULL_SELECT_KERNEL_BASE = 0xA0000                           # FF_PULL_SELECT_KERNEL_BASE
 MAX_PULL_COTANGENTS = 15                                    # cotangent columns beside the value column of a 16-column tile
 VJP_KERNEL_BASE = 0x60000                                   # FF_VJP_KERNEL_BASE
 MAX_VJP_SEEDS = 15                                          # seed columns beside the value column of a 16-column tile
@@ -287,6 +288,18 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_ode_launch_pull.restype = ctypes.c_int
     L.ff_mlp_ode_launch_pull.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_pullsel_kernel_count.restype = ctypes.c_int
+    L.ff_pullsel_kernel_name.restype = ctypes.c_char_p
+    L.ff_pullsel_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_pull_select_plan.restype = ctypes.c_int
+    L.ff_mlp_pull_select_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pull_select_wpack_floats.restype = ctypes.c_size_t
+    L.ff_mlp_pull_select_wpack_floats.argtypes = [ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_pull_select_wpack.restype = ctypes.c_int
+    L.ff_mlp_pull_select_wpack.argtypes = [ctypes.POINTER(PlanStruct)] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
+    L.ff_mlp_ode_launch_pull_select.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_pull_select.argtypes = L.ff_mlp_ode_launch_pull.argtypes
     L.ff_vjp_kernel_count.restype = ctypes.c_int
     L.ff_vjp_kernel_name.restype = ctypes.c_char_p
     L.ff_vjp_kernel_name.argtypes = [ctypes.c_int]
@@ -522,7 +535,7 @@ def make_pull_plan(dim: int, cond_dim: int, hidden: List[int], act: Tuple[int, f
 
 
 def is_pull_plan(plan: PlanStruct) -> bool:
-    return int(plan.kernel_id) >= PULL_KERNEL_BASE
+    return PULL_KERNEL_BASE <= int(plan.kernel_id) < PULL_SELECT_KERNEL_BASE
 
 
 def row_width(plan: PlanStruct) -> int:
@@ -547,6 +560,51 @@ def pack_pair_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[int], x
                              x_col0, c_col0, out.data_ptr())
     if rc != FF_OK:
         raise _err(rc, "ff_mlp_pair_wpack")
+    return out
+
+
+PULL_SELECT_ENVELOPE = ("the row-select pull-back kernels (sample_leapfrog_vjp / log_prob_leapfrog_grad) hold two SiLU networks of one "
+                        "shape in f32 with hidden widths up to 256, joint states [q | p] of up to 32 dimensions (16 per half) and up "
+                        "to 16 conditional inputs, up to 15 cotangents per sample, and as many hidden layers as leave the stash of "
+                        "their slopes inside 160 KiB of LDS: 18 at width 256 (17 beyond 16 joint dimensions), 36 at width 128")
+
+
+def make_pull_select_plan(dim: int, cond_dim: int, hidden: List[int]) -> PlanStruct:
+    """ff_mlp_pull_select_plan: the row-select pull-back unit for a joint state of ``dim`` = 2D dimensions
+    (NotImplementedError with the envelope if none holds it, or if its depth overflows the stash)."""
+    p = PlanStruct()
+    arr = (ctypes.c_int * len(hidden))(*hidden)
+    rc = lib().ff_mlp_pull_select_plan(dim, cond_dim, len(hidden), arr, ctypes.byref(p))
+    if rc == FF_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"no gfx950 row-select pull-back kernel for a joint state of {dim} dimensions, cond_dim={cond_dim}, "
+                                  f"units={hidden}: {PULL_SELECT_ENVELOPE}")
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_pull_select_plan")
+    return p
+
+
+def is_pull_select_plan(plan: PlanStruct) -> bool:
+    return int(plan.kernel_id) >= PULL_SELECT_KERNEL_BASE
+
+
+def pack_pull_select_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[int], x_col0: int, c_col0: int) -> torch.Tensor:
+    """ff_mlp_pull_select_wpack on host copies of the two networks' nn.Linear parameters: two pull packs, mlp_q's then mlp_p's;
+    returns the packed CPU tensor."""
+    L = lib()
+    n = L.ff_mlp_pull_select_wpack_floats(ctypes.byref(plan))
+    out = torch.empty(n, dtype=torch.float32)
+    keep, ptrs = [], []
+    for layers in (q_layers, p_layers):
+        ws = [f32_on(l.weight, "cpu") for l in layers]
+        bs = [f32_on(l.bias, "cpu") for l in layers]
+        keep += ws + bs
+        ptrs.append((ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws]))
+        ptrs.append((ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs]))
+    hw = (ctypes.c_int * len(hidden))(*hidden)
+    rc = L.ff_mlp_pull_select_wpack(ctypes.byref(plan), ptrs[0], ptrs[1], ptrs[2], ptrs[3], hw, int(q_layers[0].weight.shape[1]),
+                                    x_col0, c_col0, out.data_ptr())
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_pull_select_wpack")
     return out
 
 
@@ -1109,8 +1167,8 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
 
 
 def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, vjp=None,
-                record=None, discrete=None, logp_grad=None, **fields) -> None:
-    """The one launch of the ten ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
+                record=None, discrete=None, logp_grad=None, pull_select=None, **fields) -> None:
+    """The one launch of the eleven ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
     ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, ff_mlp_ode_launch_push with
     ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, ff_mlp_ode_launch_pull with
     ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``, or ff_mlp_ode_launch_vjp with
@@ -1145,6 +1203,11 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             what = "ff_mlp_ode_launch_vjp"
             rc = lib().ff_mlp_ode_launch_vjp(ctypes.byref(p), ctypes.byref(a), _chk(vjp[0], "seeds", dev), int(vjp[1]),
                                              _chk(vjp[2], "prod_out", dev), ctypes.c_void_p(stream))
+        elif pull_select is not None:       # (pull's triple, on a pull-select plan)
+            what = "ff_mlp_ode_launch_pull_select"
+            rc = lib().ff_mlp_ode_launch_pull_select(ctypes.byref(p), ctypes.byref(a), _chk(pull_select[0], "cotangents", dev),
+                                                     _chk(pull_select[1], "cot_x_out", dev), _chk(pull_select[2], "cot_cond_out", dev),
+                                                     ctypes.c_void_p(stream))
         elif pull is not None:
             what = "ff_mlp_ode_launch_pull"
             rc = lib().ff_mlp_ode_launch_pull(ctypes.byref(p), ctypes.byref(a), _chk(pull[0], "cotangents", dev),
@@ -1343,6 +1406,55 @@ def mlp_ode_pull(x: torch.Tensor, cond: Optional[torch.Tensor], cotangents: torc
 
 
 @mlp_ode_pull.register_fake
+def _(x, cond, cotangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, want_cond):
+    B, K = x.shape[0], cotangents.shape[1]
+    C = _plan_from_words(plan).cond_dim if want_cond else 0
+    return (torch.empty_like(x), x.new_empty(B, K, x.shape[1]), x.new_empty(B, K, C),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_pull_select", mutates_args=())
+def mlp_ode_pull_select(x: torch.Tensor, cond: Optional[torch.Tensor], cotangents: torch.Tensor, wpack: torch.Tensor, etab: torch.Tensor,
+                        in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor],
+                        out_shift: Optional[torch.Tensor], plan: List[int], want_cond: bool
+                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused pull-back through select rows (ff_mlp_ode_launch_pull_select) over the rows ``etab`` of the REVERSED leapfrog
+    grid, from ``x`` = the forward leapfrog's result [B, 2D]: returns what ``mlp_ode_pull`` returns -- (retraced state, cot_x
+    [B, K, 2D], cot_cond [B, K, C] ([B, K, 0] unless ``want_cond``), status [1]) -- with ``cot_x`` / ``cot_cond`` the exact
+    transpose of the forward leapfrog.  ``wpack``: the pull-select plan's two pull packs (``pack_pull_select_weights``)."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_pull_select needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    if not is_pull_select_plan(p):
+        raise RuntimeError("flowfusion_amd::mlp_ode_pull_select needs a pull-select plan")
+    B, D = x.shape
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    if cotangents.dim() != 3 or cotangents.shape[0] != B or cotangents.shape[2] != D or cotangents.shape[1] < 1:
+        raise RuntimeError(f"cotangents has shape {tuple(cotangents.shape)}, expected [{B}, K >= 1, {D}]")
+    K = int(cotangents.shape[1])
+    C = int(p.cond_dim) if want_cond else 0
+    if want_cond and p.cond_dim == 0:
+        raise RuntimeError("want_cond on a plan without conditional inputs")
+    x_out = torch.empty_like(x)
+    gx = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+    gc = torch.empty(B, K, C, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, gx, gc, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                pull_select=(cotangents, gx, gc if want_cond else None), x_out=x_out.data_ptr(), status=status.data_ptr(), batch=B,
+                n_evals=etab.shape[0], mode=MODE_HUTCH, tangent_count=K, stage_slots=_slots_hint(plan))
+    return x_out, gx, gc, status
+
+
+@mlp_ode_pull_select.register_fake
 def _(x, cond, cotangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, want_cond):
     B, K = x.shape[0], cotangents.shape[1]
     C = _plan_from_words(plan).cond_dim if want_cond else 0

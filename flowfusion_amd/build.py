@@ -150,6 +150,18 @@ def _pull_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_pull_m{tile}_h{h}_d{d}_c{c}"
 
 
+# Row-select pull-back units (ff_mlp_pullsel.hpp; ff_mlp_pull_select_plan): the pull-back row program on tables whose rows choose
+# between the two networks of a symplectic flow -- the transpose of a leapfrog, sample_leapfrog_vjp / log_prob_leapfrog_grad.
+# One sibling per pull-back unit, same tile, registers, ring and LDS layout; two pull packs in the weight stream.  A family of
+# its own (g_pullsel_kernels, FF_PULL_SELECT_KERNEL_BASE); one wavefront per workgroup leaves no inter-wave hazard, so there is
+# no test-only skew variant.
+PULL_SELECT_INSTANCES = list(PULL_INSTANCES)
+
+
+def _pullsel_name(tile, h, d, c, wps, ring) -> str:
+    return _pull_name(tile, h, d, c, wps, ring).replace("mlp_pull_", "mlp_pullsel_", 1)
+
+
 # Products units (ff_mlp_vjp.hpp; ff_mlp_ode_launch_vjp): the pull-back evaluation body run on a forward table, J^T seed of every
 # evaluation row written out -- the Hutch++ / XTrace route products="vjp".  One sibling per pull-back unit, same shape and the
 # same two weight packs: a pull plan launches entry i of g_vjp_kernels (FF_VJP_KERNEL_BASE names them, no plan carries it).
@@ -284,6 +296,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     SELECT = select if select is not None else globals()["PAIR_SELECT_INSTANCES"]       # (a subset of PAIR_INSTANCES)
     PUSH_INSTANCES = push if push is not None else globals()["PUSH_INSTANCES"]
     PULL_INSTANCES = pull if pull is not None else globals()["PULL_INSTANCES"]
+    PULL_SELECT = [] if pull is not None else globals()["PULL_SELECT_INSTANCES"]        # (the test variants carry none)
     GEN.mkdir(parents=True, exist_ok=True)
     tf = lambda t: "true" if t else "false"
     # every launcher of the library: (name, header, kernel expression) -> a translation unit, a declaration, a table cell
@@ -324,7 +337,10 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     # the log-density gradient siblings
     lgrads = [(_lgrad_name(*i), "ff_mlp_lgrad.hpp", f"mlp_lgrad_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_INSTANCES]
     files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_lgrad_registry.h")) for name, header, expr in lgrads]
-    units = units + pulls + vjps + dadjs + lgrads
+    # the row-select pull-back siblings
+    pullsels = [(_pullsel_name(*i), "ff_mlp_pullsel.hpp", f"mlp_pullsel_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_SELECT]
+    files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_pullsel_registry.h")) for name, header, expr in pullsels]
+    units = units + pulls + vjps + dadjs + lgrads + pullsels
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
     fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
@@ -369,12 +385,16 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     lgrad_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_lgrad_name(*i)}, "{_lgrad_name(*i)}"}}' for i in PULL_INSTANCES
     ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the log-density gradient units)
+    pullsel_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pullsel_name(*i)}, "{_pullsel_name(*i)}"}}' for i in PULL_SELECT
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the row-select pull-back units)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
 #include "ff_vjp_registry.h"
 #include "ff_dadj_registry.h"
 #include "ff_lgrad_registry.h"
+#include "ff_pullsel_registry.h"
 namespace ff {{
 {decls}
 const KernelEntry g_kernels[] = {{
@@ -413,6 +433,10 @@ const PullKernelEntry g_lgrad_kernels[] = {{
 {lgrad_rows}
 }};
 const int g_n_lgrad_kernels = {len(PULL_INSTANCES)};
+const PullKernelEntry g_pullsel_kernels[] = {{
+{pullsel_rows}
+}};
+const int g_n_pullsel_kernels = {len(PULL_SELECT)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -443,7 +467,7 @@ def _cost(src: Path) -> float:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
     if n.startswith("mlp_push_"):
         return 16 if "_h256_" in n else 6
-    if n.startswith("mlp_pull_") or n.startswith("mlp_vjp_") or n.startswith("mlp_dadj_") or n.startswith("mlp_lgrad_"):
+    if n.startswith("mlp_pullsel_") or n.startswith("mlp_pull_") or n.startswith("mlp_vjp_") or n.startswith("mlp_dadj_") or n.startswith("mlp_lgrad_"):
         return 40 if "_h256_" in n else 15
     if n.startswith("mlp_rec_"):
         return 16 if "_h256_" in n else 6

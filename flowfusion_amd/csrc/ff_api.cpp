@@ -8,6 +8,7 @@
 #include "ff_split_layout.h"
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
+#include "ff_pullsel_registry.h"
 #include "ff_vjp_registry.h"
 #include "ff_dadj_registry.h"
 #include "ff_lgrad_registry.h"
@@ -161,7 +162,7 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
 // ---- what a plan launches, as data ------------------------------------------------------------------------------------
 // describe() validates a plan once and says everything the code below needs to know about its family: the launcher,
 // ff_mlp_launch_kind and the small queries read the description and never ask which family they serve.
-enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush, kPull };
+enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush, kPull, kPullSel };
 
 struct LaunchDesc {
     PlanFamily family;
@@ -186,6 +187,14 @@ struct LaunchDesc {
     bool record, discrete;     // kPull: the plan's record / discrete-adjoint sibling (ff_mlp_ode_launch_record, _pull_discrete: ff_mlp_dadj.hpp)
     bool logp_grad;            // kPull: the plan's log-density gradient sibling (ff_mlp_ode_launch_logp_grad: ff_mlp_lgrad.hpp)
 };
+
+// The row-select pull-back table is a WEAK reference: a program that links this file with kernel tables of its own from before
+// these units (tests/sanitize/pull_wpack_main.cpp) still links, and sees a library without them.
+namespace ff {
+extern const PullKernelEntry g_pullsel_kernels[] __attribute__((weak));
+extern const int g_n_pullsel_kernels __attribute__((weak));
+}
+static int n_pullsel_kernels() { return &ff::g_n_pullsel_kernels ? ff::g_n_pullsel_kernels : 0; }
 
 static bool shape_ok(const ff_mlp_plan_t* p, int tile, int H, int dregs, int cregs)
 {
@@ -230,6 +239,18 @@ static bool describe(const ff_mlp_plan_t* p, LaunchDesc* d)
         d->tangents = k.tangents; d->nets = 1; d->row_nets = 1;
         d->exchange = k.launch ? 2 : 1;
         d->max_aux = FF_MAX_AUX; d->takes_k1 = true; d->empty_batch_first = true;
+        return true;
+    }
+    if (p->kernel_id >= FF_PULL_SELECT_KERNEL_BASE) {
+        // row-select pull-back units (ff_mlp_pullsel.hpp): the pull units' geometry over a joint state [q | p]; the packed weights
+        // are two pull packs, a row of the table carries the c1 of the one network it runs
+        const int index = p->kernel_id - FF_PULL_SELECT_KERNEL_BASE;
+        if (index >= n_pullsel_kernels()) return false;
+        const ff::PullKernelEntry& k = ff::g_pullsel_kernels[index];
+        if (!k.launch || !shape_ok(p, k.tile, k.H, k.dregs, k.cregs) || p->activation != FF_ACT_SILU || p->dim % 2 != 0) return false;
+        d->family = kPullSel; d->name = k.name; d->one_wave = k.launch;
+        twin_line(d, k.wps);
+        d->tangents = 1; d->nets = 2; d->row_nets = 1; d->exchange = 2;
         return true;
     }
     if (p->kernel_id >= FF_PULL_KERNEL_BASE) {
@@ -327,7 +348,7 @@ namespace ff {
 bool plan_steps_adaptively(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
-    return describe(plan, &d) && d.family != kSelect && d.family != kPush && d.family != kPull;
+    return describe(plan, &d) && d.family != kSelect && d.family != kPush && d.family != kPull && d.family != kPullSel;
 }
 }
 
@@ -463,6 +484,40 @@ extern "C" size_t ff_mlp_pull_wpack_floats(const ff_mlp_plan_t* plan)
     return describe(plan, &d) && d.family == kPull ? plan_layout(plan).total_floats + pull_layout(plan).total_floats : 0;
 }
 
+extern "C" int ff_pullsel_kernel_count(void) { return n_pullsel_kernels(); }
+
+extern "C" const char* ff_pullsel_kernel_name(int index)
+{
+    return index >= 0 && index < n_pullsel_kernels() ? ff::g_pullsel_kernels[index].name : NULL;
+}
+
+// the pull plan of the joint state (one envelope, one preference, the same depth ceilings), carried over to the sibling unit
+extern "C" int ff_mlp_pull_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
+{
+    if (!plan || !hidden_widths || dim < 2 || dim % 2 != 0 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
+    const int rc = ff_mlp_pull_plan(dim, cond_dim, n_hidden, hidden_widths, FF_ACT_SILU, FF_PREC_F32, plan);
+    if (rc != FF_OK) return rc;
+    const int index = plan->kernel_id - FF_PULL_KERNEL_BASE;
+    const ff::PullKernelEntry& k = ff::g_pull_kernels[index];
+    bool found = false;
+    for (int i = 0; i < n_pullsel_kernels() && !found; ++i) {
+        const ff::PullKernelEntry& s = ff::g_pullsel_kernels[i];
+        if (s.launch && s.tile == k.tile && s.H == k.H && s.dregs == k.dregs && s.cregs == k.cregs) {
+            plan->kernel_id = FF_PULL_SELECT_KERNEL_BASE + i;
+            found = true;
+        }
+    }
+    if (!found) { memset(plan, 0, sizeof(*plan)); return FF_ERR_UNSUPPORTED; }
+    return FF_OK;
+}
+
+// two pull packs back to back: [A_q | B_q | A_p | B_p]
+extern "C" size_t ff_mlp_pull_select_wpack_floats(const ff_mlp_plan_t* plan)
+{
+    LaunchDesc d;
+    return describe(plan, &d) && d.family == kPullSel ? 2 * (plan_layout(plan).total_floats + pull_layout(plan).total_floats) : 0;
+}
+
 extern "C" int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
 {
     const int rc = ff_mlp_pair_plan(dim, cond_dim, n_hidden, hidden_widths, plan);      // one envelope, one preference
@@ -487,7 +542,7 @@ extern "C" int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* 
 extern "C" size_t ff_mlp_pair_wpack_floats(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
-    return describe(plan, &d) && d.nets == 2 ? 2 * plan_layout(plan).total_floats : 0;
+    return describe(plan, &d) && d.nets == 2 && d.family != kPullSel ? 2 * plan_layout(plan).total_floats : 0;
 }
 
 extern "C" size_t ff_mlp_wpack_floats(const ff_mlp_plan_t* plan)
@@ -495,7 +550,7 @@ extern "C" size_t ff_mlp_wpack_floats(const ff_mlp_plan_t* plan)
     LaunchDesc d;
     if (!describe(plan, &d)) return 0;
     if (d.family == kSplit) return ff::split::total_words(plan->n_hidden, split_parts(plan->precision), plan->dregs / 8, plan->width);
-    if (d.family == kPull) return 0;                     // (two packs: ff_mlp_pull_wpack_floats)
+    if (d.family == kPull || d.family == kPullSel) return 0;      // (two packs: ff_mlp_pull_wpack_floats; four: ff_mlp_pull_select_wpack_floats)
     return d.nets == 1 ? plan_layout(plan).total_floats : 0;
 }
 
@@ -750,6 +805,63 @@ extern "C" int ff_mlp_pull_wpack(const ff_mlp_plan_t* plan, const float* const* 
     return rc;
 }
 
+// Pull-select packing (ff_mlp_pullsel.hpp): each network embedded in the whole joint state [q | p] exactly as ff_mlp_pair_wpack
+// embeds it, then packed as ff_mlp_pull_wpack packs a network -- mlp_q's pull pack, then mlp_p's.
+extern "C" int ff_mlp_pull_select_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq,
+                                        const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
+                                        int x_col0, int c_col0, float* out)
+{
+    LaunchDesc d;
+    if (!describe(plan, &d) || d.family != kPullSel || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
+    const int D2 = plan->dim, Dh = D2 / 2, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
+    if (x_col0 < 0 || x_col0 + Dh > in_features0) return FF_ERR_BADARG;
+    if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
+    for (int i = 0; i < NH; ++i)
+        if (hidden_widths[i] < 1 || hidden_widths[i] > H) return FF_ERR_BADARG;
+    for (int i = 0; i <= NH; ++i)
+        if (!Wq[i] || !Wp[i] || (i > 0 && (!bq[i] || !bp[i]))) return FF_ERR_BADARG;
+    // the sibling pull plan: same shape, the pull family's id -- what ff_mlp_pull_wpack takes
+    ff_mlp_plan_t pp = *plan;
+    pp.kernel_id = -1;
+    for (int i = 0; i < ff::g_n_pull_kernels; ++i) {
+        const ff::PullKernelEntry& k = ff::g_pull_kernels[i];
+        if (k.launch && k.tile == plan->tile && k.H == plan->width && k.dregs == plan->dregs && k.cregs == plan->cregs) { pp.kernel_id = FF_PULL_KERNEL_BASE + i; break; }
+    }
+    if (pp.kernel_id < 0) return FF_ERR_BADARG;
+    const size_t half_floats = plan_layout(plan).total_floats + pull_layout(plan).total_floats;
+    const int h0 = hidden_widths[0], hl = hidden_widths[NH - 1], in1 = D2 + C;
+    float* const w1 = (float*)calloc((size_t)h0 * in1, sizeof(float));
+    float* const wo = (float*)calloc((size_t)D2 * hl, sizeof(float));
+    float* const bo = (float*)calloc((size_t)D2, sizeof(float));
+    const float** const Wl = (const float**)calloc((size_t)NH + 1, sizeof(float*));
+    const float** const bl = (const float**)calloc((size_t)NH + 1, sizeof(float*));
+    int rc = (w1 && wo && bo && Wl && bl) ? FF_OK : FF_ERR_BADARG;
+    for (int half = 0; half < 2 && rc == FF_OK; ++half) {
+        const float* const* W = half ? Wp : Wq;
+        const float* const* b = half ? bp : bq;
+        const int in_col = half ? 0 : Dh;        // state columns this network reads: p (mlp_q) or q (mlp_p)
+        const int out_row = half ? Dh : 0;       // state rows it writes
+        const float sgn = half ? -1.f : 1.f;
+        memset(w1, 0, (size_t)h0 * in1 * sizeof(float));
+        memset(wo, 0, (size_t)D2 * hl * sizeof(float));
+        memset(bo, 0, (size_t)D2 * sizeof(float));
+        for (int r = 0; r < h0; ++r) {
+            for (int dd = 0; dd < Dh; ++dd) w1[(size_t)r * in1 + in_col + dd] = W[0][(size_t)r * in_features0 + x_col0 + dd];
+            for (int c = 0; c < C; ++c) w1[(size_t)r * in1 + D2 + c] = W[0][(size_t)r * in_features0 + c_col0 + c];
+        }
+        for (int r = 0; r < Dh; ++r) {
+            for (int k = 0; k < hl; ++k) wo[(size_t)(out_row + r) * hl + k] = sgn * W[NH][(size_t)r * hl + k];
+            bo[out_row + r] = sgn * b[NH][r];
+        }
+        Wl[0] = w1; bl[0] = nullptr;
+        for (int l = 1; l < NH; ++l) { Wl[l] = W[l]; bl[l] = b[l]; }
+        Wl[NH] = wo; bl[NH] = bo;
+        rc = ff_mlp_pull_wpack(&pp, Wl, bl, hidden_widths, in1, 0, D2, out + (size_t)half * half_floats);
+    }
+    free(w1); free(wo); free(bo); free(Wl); free(bl);
+    return rc;
+}
+
 // Pair packing: each reference network becomes an ordinary network over the whole state [q | p] (its first layer reads
 // its own half -- p for mlp_q, q for mlp_p -- and has zero columns on the other; its output layer writes its own half,
 // negated for mlp_p, and zero rows on the other), packed by wpack_f32; net A's pack, then net B's.
@@ -758,7 +870,7 @@ extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* 
                                  int x_col0, int c_col0, float* out)
 {
     LaunchDesc d;
-    if (!describe(plan, &d) || d.nets != 2 || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
+    if (!describe(plan, &d) || d.nets != 2 || d.family == kPullSel || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
     const int D2 = plan->dim, Dh = D2 / 2, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
     if (x_col0 < 0 || x_col0 + Dh > in_features0) return FF_ERR_BADARG;
     if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
@@ -815,7 +927,7 @@ extern "C" int ff_mlp_samples_per_workgroup(const ff_mlp_plan_t* plan, int mode)
     int nt, unit;
     int rc = tangents_of_mode(mode, plan->dim, plan->tile, &nt, &unit);
     if (rc) return rc;
-    if (d.family == kPull) return plan->tile / (1 + nt);      // a tile per workgroup
+    if (d.family == kPull || d.family == kPullSel) return plan->tile / (1 + nt);      // a tile per workgroup
     return (d.one_wave ? 4 : 1) * (plan->tile / (1 + nt));      // (the wide catch-all: a tile per workgroup)
 }
 
@@ -961,7 +1073,7 @@ extern "C" int ff_mlp_launch_kind(const ff_mlp_plan_t* plan, int64_t batch, int3
 static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArgs ka, long long spt, bool jac_out, hipStream_t stream)
 {
     const long long batch = ka.batch;
-    if (d.family == kPull) {
+    if (d.family == kPull || d.family == kPullSel) {
         // a wavefront per workgroup and per tile; LDS = stage slots + the slope stash of the tile's samples
         const long long tiles = (batch + spt - 1) / spt;
         const size_t lds = d.record ? rec_lds_bytes(plan, ka.tangent_first)
@@ -1027,6 +1139,7 @@ struct PullIo {
     const float* cotangent_in;
     float* cot_x_out;
     float* cot_cond_out;
+    bool select;               // ff_mlp_ode_launch_pull_select: the plan must be a pull-select plan, and only there may it be one
 };
 
 // What ff_mlp_ode_launch_vjp adds to a launch (NULL: not a products launch).
@@ -1070,7 +1183,9 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
     if (!a || !describe(plan, &d)) return FF_ERR_BADARG;
     if ((pull || vjp || rec || dadj || lgrad) && d.family == kSplit) return FF_ERR_UNSUPPORTED;
     // pull plans launch through their own entries, and only they
-    if ((d.family == kPull) != (pull != nullptr || vjp != nullptr || rec != nullptr || dadj != nullptr || lgrad != nullptr)) return FF_ERR_BADARG;
+    if ((d.family == kPull) != ((pull != nullptr && !pull->select) || vjp != nullptr || rec != nullptr || dadj != nullptr || lgrad != nullptr)) return FF_ERR_BADARG;
+    // pull-select plans through theirs, and only they
+    if ((d.family == kPullSel) != (pull != nullptr && pull->select)) return FF_ERR_BADARG;
     if (rec) {
         // a whole fixed-grid solve of the state that writes every stage state down: a state-only launch's arguments, the pull
         // launch's refusals.  No cotangent columns: no stash, and the tile's columns are all samples
@@ -1175,7 +1290,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
 
     ff::KernelArgs ka = fill_args(plan, a, !d.state_only, nt, unit, tfirst);
     ka.etab_stride = FF_ROW_HDR + d.row_nets * plan->width;
-    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats + (pull || vjp || rec || dadj || lgrad ? pull_layout(plan).total_floats : 0);
+    const size_t wpack_floats = (size_t)d.nets * plan_layout(plan).total_floats +
+                                (pull || vjp || rec || dadj || lgrad ? (size_t)d.nets * pull_layout(plan).total_floats : 0);
     if (wpack_floats * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     if ((size_t)(a->n_evals + 2) * ka.etab_stride * 4 > 0x7fffffffull) return FF_ERR_UNSUPPORTED;
     ka.wpack_floats = (int)wpack_floats;
@@ -1229,7 +1345,14 @@ extern "C" int ff_mlp_ode_launch_push(const ff_mlp_plan_t* plan, const ff_ode_ar
 extern "C" int ff_mlp_ode_launch_pull(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* cotangent_in, float* cot_x_out,
                                       float* cot_cond_out, void* hip_stream)
 {
-    const PullIo io = {cotangent_in, cot_x_out, cot_cond_out};
+    const PullIo io = {cotangent_in, cot_x_out, cot_cond_out, false};
+    return launch_ode(plan, a, nullptr, hip_stream, nullptr, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_pull_select(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* cotangent_in, float* cot_x_out,
+                                             float* cot_cond_out, void* hip_stream)
+{
+    const PullIo io = {cotangent_in, cot_x_out, cot_cond_out, true};
     return launch_ode(plan, a, nullptr, hip_stream, nullptr, &io);
 }
 

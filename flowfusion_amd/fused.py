@@ -565,11 +565,50 @@ class FusedPair(FusedNet):
             raise RuntimeError("select rows need a select plan")
         return self.integrate(x, etab, MODE_STATE, cond=cond, stage_slots=1, plan=plan, **maps)
 
+    def pull_select_plan(self) -> _native.PlanStruct:
+        """The row-select pull-back unit of this pair (ff_mlp_pull_select_plan); NotImplementedError with the envelope if
+        none holds it."""
+        if "pull_select" not in self._plans:
+            self._plans["pull_select"] = _native.make_pull_select_plan(self.dim, self.cond_dim, self.hidden)
+        return self._plans["pull_select"]
+
+    def pullback_select(self, z: torch.Tensor, etab: torch.Tensor, cotangents: torch.Tensor, cond: Optional[torch.Tensor] = None,
+                        want_cond: bool = False, stage_slots: int = 1, in_shift=None, in_scale=None, out_scale=None,
+                        out_shift=None):
+        """The pull-back of K cotangents through select rows, on the row-select pull-back unit (``pull_select_plan``): ``etab``
+        has ITS width (``width(MODE_STATE, pull_select=True)``) and holds the rows of the REVERSED grid of the leapfrog that
+        produced ``z`` [B, 2D].  Returns (z_back [B, 2D], gz [B, K, 2D], gc [B, K, C] or None, status [1]): ``z_back`` the
+        retraced start state, ``gz[b, k] = cotangents[b, k]^T d z[b] / d z_back[b]`` and ``gc`` likewise for ``cond`` as
+        given -- on shear rows the exact transpose of the forward rows.  The affine maps are this launch's own, as
+        ``pullback``'s are."""
+        if not z.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {z.device}); there is no CPU fallback")
+        if z.dim() != 2 or z.shape[1] != self.dim:
+            raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(z.shape)}")
+        dev = z.device
+        plan = self.pull_select_plan()
+        B = z.shape[0]
+        cond = self._pull_cond(cond, B, dev)
+        if cotangents is None or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, self.dim):
+            raise ValueError(f"pullback_select: cotangents [batch, K, {self.dim}]")
+        want = bool(want_cond and self.cond_dim > 0)
+        y, gz, gc, status = torch.ops.flowfusion_amd.mlp_ode_pull_select(
+            f32_on(z, dev), cond, f32_on(cotangents, dev).contiguous(), self.wpack(dev, MODE_STATE, plan), f32_on(etab, dev),
+            f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots), want)
+        return y, gz, (gc if want else None), status
+
     def _param_key(self, device, plan) -> Tuple:
         vers = tuple((p.data_ptr(), p._version) for l in self.linears + self.p_linears for p in (l.weight, l.bias))
-        return (str(device), plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden), vers
+        # (a pull-select plan's buffer holds two pull packs: a key of its own)
+        return (str(device), plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden) + \
+            (("pull_select",) if _native.is_pull_select_plan(plan) else ()), vers
 
     def _pack(self, plan) -> torch.Tensor:
+        if _native.is_pull_select_plan(plan):
+            return _native.pack_pull_select_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
         return _native.pack_pair_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
 
     def cached_table(self, key, device, build):
@@ -601,8 +640,11 @@ class FusedPair(FusedNet):
             self._time_cols = hit
         return hit[1], hit[2]
 
-    def width(self, mode: int = MODE_STATE, select: bool = False) -> int:
-        """First-layer bias words per evaluation row: two networks' worth; one network's on the select plan."""
+    def width(self, mode: int = MODE_STATE, select: bool = False, pull_select: bool = False) -> int:
+        """First-layer bias words per evaluation row: two networks' worth; one network's on the select plan; one network's of
+        the pull-select plan's width with ``pull_select=True`` (its unit may be wider than the pair plan's)."""
+        if pull_select:
+            return int(self.pull_select_plan().width)
         return (1 if select else 2) * int(self.plan(mode).width)
 
     def stage_slots(self, mode: int = MODE_STATE) -> int:

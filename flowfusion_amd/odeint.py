@@ -669,6 +669,112 @@ def solve_leapfrog(front, x, grid, cond=None):
     return y
 
 
+def _leapfrog_pull_checks(front, z, cotangents, cond, num_cotangents):
+    """What ``solve_leapfrog_pull`` refuses before the device is touched, in ``_pull_checks``' style: shapes, K, dtypes,
+    CPU tensors, the envelope.  Returns ``(net, B, D2, K, C)``."""
+    what = "leapfrog pull-backs"
+    if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] % 2 != 0 or z.shape[1] < 2:
+        raise ValueError(f"{what}: z must be a [batch, 2 dim] tensor, the joint state [q | p]")
+    B, D2 = int(z.shape[0]), int(z.shape[1])
+    if callable(cotangents):
+        K = int(num_cotangents)
+        if K < 1:
+            raise ValueError(f"{what}: num_cotangents={num_cotangents}: at least one cotangent per sample")
+    else:
+        if not torch.is_tensor(cotangents) or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, D2) or cotangents.shape[1] < 1:
+            raise ValueError(f"{what}: cotangents must be [{B}, K >= 1, {D2}], got "
+                             f"{tuple(cotangents.shape) if torch.is_tensor(cotangents) else type(cotangents).__name__}")
+        K = int(cotangents.shape[1])
+    if K > _native.MAX_PULL_COTANGENTS:
+        raise ValueError(f"{what}: K={K} cotangents per sample; a sample and its cotangents share the 16 columns "
+                         f"of one tile, so at most {_native.MAX_PULL_COTANGENTS} per call")
+    if cond is not None and (not torch.is_tensor(cond) or cond.dim() != 2 or cond.shape[0] != B):
+        raise ValueError(f"{what}: conditional must be [{B}, cond_dim], got "
+                         f"{tuple(cond.shape) if torch.is_tensor(cond) else type(cond).__name__}")
+    require_fp32(front, z, cond, None if callable(cotangents) else cotangents, what="a leapfrog pull-back solve")
+    _need_gpu(z)
+    try:
+        if not front._fusable():
+            raise NotImplementedError("the model's two networks are outside the compiled two-network shapes (or not a SymplecticMLP "
+                                      "with SiLU)")
+        net = front._net()
+        net.pull_select_plan()
+    except NotImplementedError as e:
+        msg = str(e)
+        raise NotImplementedError(msg if _native.PULL_SELECT_ENVELOPE in msg else
+                                  f"{msg} -- {_native.PULL_SELECT_ENVELOPE}; there is no module-path fallback") from None
+    if D2 != net.dim:
+        raise ValueError(f"{what}: z has {D2} columns, the model's joint state has {net.dim}")
+    C = net.cond_dim
+    if C > 0 and (cond is None or tuple(cond.shape) != (B, C)):
+        raise ValueError(f"{what}: conditional must be [{B}, {C}], got {None if cond is None else tuple(cond.shape)}")
+    if C == 0 and cond is not None:
+        raise ValueError(f"{what}: this model has no conditional inputs")
+    return net, B, D2, K, C
+
+
+def solve_leapfrog_pull(front, z, grid, cotangents, cond=None, return_retrace=False):
+    """Leapfrog pull-backs (extension): K cotangents per sample pulled back through ``solve_leapfrog(front, z, grid, cond)``,
+    exactly.  Returns ``(z_out [B, 2D], gz [B, K, 2D], gc [B, K, C] or None)`` -- and ``retrace [B]`` with ``return_retrace``
+    -- where ``gz[b, k] = cotangents[b, k]^T d z_out[b] / d z[b]`` and ``gc`` likewise for ``cond`` as given.
+
+    A leapfrog row is a shear ``q' = q + w f(p, c, t)``, ``p' = p`` (or the kick, its mirror image); its transpose is
+    ``lambda_q = lambda_q'``, ``lambda_p = lambda_p' + w J_f(p)^T lambda_q'``, ``gamma += w (df/dc)^T lambda_q'``.  The row
+    leaves the network's input half alone, so the backward sweep recomputes ``f(p)`` from the state it holds, un-shears, and
+    takes the slopes for ``J^T`` from that same evaluation: the retracing sweep IS the discrete adjoint, and no stage state
+    is recorded.  Per piece of rows: ``solve_leapfrog`` for ``z_out`` (the existing launch: bitwise what ``sample_leapfrog`` /
+    ``log_prob_leapfrog`` see), then ONE launch of the row-select pull-back unit (``FusedPair.pullback_select``) from
+    ``z_out`` on the table of ``solvers.plan_leapfrog(grid.flip(0))``, which holds bitwise the forward table's times and
+    weights in reverse order.  Rows are cut so that a [rows, K, 2D] buffer stays under ``PROBE_BUFFER_FLOATS`` floats; rows
+    are independent, so any cut gives bitwise the same.
+
+    ``cotangents``: [B, K, 2D].  ``retrace[b] = max_d |z_back - z|``: within rounding by construction (the
+    un-shear subtracts what the forward row added, recomputed from the same input half); it exists to show a non-finite or
+    exploding trajectory.
+
+    Refused before the device is touched: shapes that do not match and K > 15 (ValueError), non-fp32 tensors (TypeError), CPU
+    tensors (RuntimeError), a model outside ``_native.PULL_SELECT_ENVELOPE`` or not on the fused route
+    (NotImplementedError: there is no module-path fallback).  Out of scope: parameter gradients and torch.autograd
+    integration, Euler and dopri5 solves (not shears: they need a record), twins, sharded entry points (rows are
+    independent: slice)."""
+    if callable(cotangents):
+        raise ValueError("leapfrog pull-backs: cotangents must be a [batch, K, 2 dim] tensor")
+    return _solve_leapfrog_pull(front, z, grid, cotangents, cond, return_retrace, 1)
+
+
+def _solve_leapfrog_pull(front, z, grid, cotangents, cond, return_retrace, num_cotangents):
+    """``solve_leapfrog_pull`` whose ``cotangents`` may also be a function ``z_out piece [rows, 2D] -> [rows, num_cotangents,
+    2D]``, evaluated per piece of rows between the two launches: how ``log_prob_leapfrog_grad`` hands over ``-z1``."""
+    net, B, D2, K, C = _leapfrog_pull_checks(front, z, cotangents, cond, num_cotangents)
+    grid = torch.as_tensor(grid).detach().to("cpu", torch.float32).reshape(-1)
+    back = torch.flip(grid, dims=(0,))
+    key = ("leapfrog_pull", tuple(float(v) for v in back)) + front._schedule_key()
+    table = net.cached_table(key, z.device, lambda: front._leapfrog_table(back, pull_select=True))
+    rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D2))
+    pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    outs, backs, gzs, gcs = [], [], [], []
+    evals = 0
+    for r0, r1 in pieces:
+        zo = solve_leapfrog(front, cut(z, r0, r1), grid, cond=cut(cond, r0, r1))
+        evals = front.last_solver_stats["evaluations"]
+        w = cotangents(zo) if callable(cotangents) else cut(cotangents, r0, r1)
+        if callable(cotangents) and (w.dim() != 3 or tuple(w.shape) != (r1 - r0, K, D2)):
+            raise ValueError(f"leapfrog pull-backs: the cotangent function returned {tuple(w.shape)}, expected {(r1 - r0, K, D2)}")
+        zb, gz, gc, _ = net.pullback_select(zo, table, w, cond=cut(cond, r0, r1), want_cond=C > 0, stage_slots=1)
+        outs.append(zo)
+        backs.append(zb)
+        gzs.append(gz)
+        gcs.append(gc)
+    front.last_solver_stats = {"evaluations": evals + int(table.shape[0]), "launches": 2 * len(pieces)}
+    zo, zb, gz = (outs[0], backs[0], gzs[0]) if whole else (torch.cat(outs), torch.cat(backs), torch.cat(gzs))
+    gc = None if C == 0 else (gcs[0] if whole else torch.cat(gcs))
+    if not return_retrace:
+        return zo, gz, gc
+    return zo, gz, gc, (zb - z).abs().amax(dim=1)
+
+
 # ---- extension: the log-density of noisy observations over K noise draws (the front ends' ``log_prob_noisy``) -----------
 OBSERVE_CHUNK_ROWS = 1 << 22        # rows (data points x noise draws) in flight by default on a fixed grid
 

@@ -141,6 +141,85 @@ class SymplecticFlowModel(nn.Module):
         p0 = torch.randn_like(x)
         return self._log_prob_from(x, p0, conditional, method="leapfrog", num_steps=num_steps)
 
+    # -- extensions: derivatives through the leapfrog (odeint.solve_leapfrog_pull).  Methods of their own, as sample_leapfrog /
+    # log_prob_leapfrog are: flow_jvp / flow_jacobian / flow_vjp / log_prob_grad above keep raising -------------------------
+    @torch.no_grad()
+    def sample_leapfrog_vjp(self, z, cotangents, conditional=None, num_steps=1, *, return_retrace=False):
+        """K cotangents per sample pulled back through ``sample_leapfrog``'s map, exactly (the transpose of the discrete
+        leapfrog: every row is a shear, so nothing is recorded).
+
+        ``z`` [B, 2D] is the prior draw (the ``x`` of ``_sample_from``), ``cotangents`` [B, K, D] are in the units of the
+        returned sample, K <= 15.  Returns ``(x [B, D], gz [B, K, 2D], gc [B, K, C] or None)`` -- and ``retrace [B]`` with
+        ``return_retrace``: ``x`` is bitwise ``_sample_from(z, conditional, num_steps, method="leapfrog")``,
+        ``gz[b, k] = cotangents[b, k]^T dx / dz`` and ``gc`` the same with respect to the raw ``conditional`` (the
+        population hyper-parameters), i.e. divided by ``conditional_scale``.  The joint cotangent handed to the launch is
+        ``[w * scale | 0]``.  Two launches per piece of rows; fused route only (``_native.PULL_SELECT_ENVELOPE``), no
+        module-path fallback.  ``retrace``: see ``log_prob_leapfrog_grad``."""
+        if int(num_steps) < 1:
+            raise ValueError(f"num_steps={num_steps}: sample_leapfrog_vjp differentiates at least one leapfrog step")
+        if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] % 2 != 0:
+            raise ValueError("sample_leapfrog_vjp: z must be the prior draw [batch, 2 dim]")
+        B, D = int(z.shape[0]), int(z.shape[1]) // 2
+        if not torch.is_tensor(cotangents) or cotangents.dim() != 3 or tuple(cotangents.shape[::2]) != (B, D) or cotangents.shape[1] < 1:
+            raise ValueError(f"sample_leapfrog_vjp: cotangents must be [{B}, K >= 1, {D}], got "
+                             f"{tuple(cotangents.shape) if torch.is_tensor(cotangents) else type(cotangents).__name__}")
+        cond = self._norm_cond(conditional)
+        w = cotangents if self.scale is None else cotangents * self.scale
+        joint = torch.cat([w, torch.zeros_like(w)], dim=-1)
+        grid = torch.linspace(1.0, 0.0, int(num_steps) + 1, device=z.device).cpu()      # (built as _sample_from builds it)
+        out = odeint.solve_leapfrog_pull(self, z, grid, joint, cond=cond, return_retrace=return_retrace)
+        q, _ = torch.chunk(out[0], 2, dim=-1)
+        x = q * self.scale + self.shift
+        gc = out[2]
+        if gc is not None and self.conditional_scale is not None:
+            gc = gc / self.conditional_scale
+        return (x, out[1], gc) + tuple(out[3:])
+
+    @torch.no_grad()
+    def log_prob_leapfrog_grad(self, x, conditional=None, num_steps=None, *, momentum=None, return_momentum_grad=False,
+                               return_retrace=False):
+        """``log_prob_leapfrog`` and its gradient with respect to ``x`` and the raw ``conditional`` -- what HMC / NUTS,
+        L-BFGS and MAP ask of this model class.  Returns ``(log_p [B], grad_x [B, D], grad_c [B, C] or None)``, then
+        ``grad_momentum [B, D]`` with ``return_momentum_grad`` and ``retrace [B]`` with ``return_retrace``.
+
+        ``momentum=None`` draws ``torch.randn_like(x)`` as ``log_prob_leapfrog`` does; ``log_p`` is bitwise
+        ``_log_prob_from(x, momentum, conditional, method="leapfrog", num_steps=num_steps)``.  The backward launch takes the
+        one cotangent ``-z1`` (the gradient of ``log N(z1)``) through the transpose of the discrete leapfrog: ``grad_x =
+        g_q / scale``, ``grad_momentum = g_p + momentum``, ``grad_c = gamma / conditional_scale`` -- the exact gradient of
+        the returned value at fixed momentum, at any step count (no discretisation error between value and gradient).
+
+        ``retrace[b] = max_d |z_back - z0|``, z0 = [q0 | momentum]: the backward sweep un-shears with the same network
+        evaluation that gave it its slopes, so the retrace is within rounding BY CONSTRUCTION; it says nothing about the
+        step count.  It exists to show a non-finite or exploding trajectory.
+
+        Fused route only (``_native.PULL_SELECT_ENVELOPE``); the gradient of ``log_prob_marginal``, Euler ``sample`` and
+        dopri5 ``log_prob`` pull-backs, parameter gradients and torch.autograd integration are out of scope."""
+        self._check_log_prob_method("leapfrog", num_steps)
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise ValueError("log_prob_leapfrog_grad: x must be a [batch, dim] tensor")
+        if momentum is None:
+            momentum = torch.randn_like(x)
+        elif not torch.is_tensor(momentum) or tuple(momentum.shape) != tuple(x.shape):
+            raise ValueError(f"log_prob_leapfrog_grad: momentum must be {tuple(x.shape)}, got "
+                             f"{tuple(momentum.shape) if torch.is_tensor(momentum) else type(momentum).__name__}")
+        D = int(x.shape[1])
+        q0 = (x - self.shift) / self.scale
+        cond = self._norm_cond(conditional)
+        z0 = torch.cat([q0, momentum], dim=-1)
+        grid = torch.linspace(1.0, 0.0, int(num_steps) + 1).flip(0)                     # (as _solve_forward builds it)
+        out = odeint._solve_leapfrog_pull(self, z0, grid, lambda z1: (-z1)[:, None, :], cond, return_retrace, 1)
+        z1, gz, gc = out[0], out[1][:, 0], out[2]
+        normal = torch.distributions.Normal(0, 1)
+        log_p = normal.log_prob(z1).sum(dim=-1) - normal.log_prob(momentum).sum(dim=-1) - torch.sum(torch.log(self.scale))
+        grad_x = gz[:, :D] / self.scale
+        grad_c = None
+        if gc is not None:
+            grad_c = gc[:, 0] if self.conditional_scale is None else gc[:, 0] / self.conditional_scale
+        res = (log_p, grad_x, grad_c)
+        if return_momentum_grad:
+            res += (gz[:, D:] + momentum,)
+        return res + tuple(out[3:])
+
     # -- with the random draws supplied (tests feed the reference's draws) ----------------------------
     def _norm_cond(self, conditional):
         if conditional is None:
@@ -352,13 +431,18 @@ class SymplecticFlowModel(nn.Module):
         a, b, c1 = self._schedule(plan.t_eval)
         return solvers.build_table(plan, a, b, c1, self._net().width(mode))
 
-    def _leapfrog_table(self, grid):
-        """The select plan's table of ``solvers.plan_leapfrog(grid)``: every row carries the c1 of the network it runs."""
+    def _leapfrog_table(self, grid, pull_select=False):
+        """The select plan's table of ``solvers.plan_leapfrog(grid)``: every row carries the c1 of the network it runs.
+        ``pull_select``: the same rows at the row width of the pull-select plan (its unit may be wider than the pair plan's)."""
         plan = solvers.plan_leapfrog(grid)
         a, b, c1 = self._schedule(plan.t_eval)
         H = self._net().width(MODE_STATE, select=True)
         net_b = (plan.flags & solvers.FLAG_NET_B) != 0
-        return solvers.build_table(plan, a, b, torch.where(net_b[:, None], c1[:, H:], c1[:, :H]), H)
+        own = torch.where(net_b[:, None], c1[:, H:], c1[:, :H])
+        if pull_select:
+            h0 = self._net().hidden[0]
+            return solvers.build_table(plan, a, b, own[:, :h0], self._net().width(MODE_STATE, pull_select=True))
+        return solvers.build_table(plan, a, b, own, H)
 
     def _schedule_key(self):
         """Besides the first layers: the embedding frequencies."""

@@ -560,6 +560,43 @@ int ff_mlp_row_width(const ff_mlp_plan_t* plan);
 #define FF_PAIR_SELECT_KERNEL_BASE 0x20000
 int ff_mlp_pair_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan_out);
 
+/* ---- row-select pull-backs: the transpose of a leapfrog of the symplectic flows (csrc/ff_mlp_pullsel.hpp) ---------------
+ * A leapfrog row is a shear: it moves one half of [q | p] by w f(other half, cond, t).  Its transpose,
+ *     lambda_q = lambda_q',  lambda_p = lambda_p' + w J_f(p)^T lambda_q',  gamma += w (df/dcond)^T lambda_q',
+ * needs only the half the row leaves alone, so the row program of ff_mlp_ode_launch_pull run on the table of the REVERSED grid
+ * (solvers.plan_leapfrog(grid.flip(0)): bitwise the forward table's times and weights in reverse order) retraces the state
+ * from the forward solve's x_out and computes the EXACT discrete adjoint of the forward leapfrog on the way -- nothing is
+ * recorded.  One sibling per pull-back unit (kernel names mlp_pullsel_...), same tile, registers, ring and LDS formula; a row
+ * runs the forward and the transposed network of mlp_p if its flag word has FF_ROW_NET_B, of mlp_q otherwise, and carries
+ * only that network's c1 (row stride FF_ROW_HDR + plan.width; ff_mlp_row_width = plan.width).  Rows may select in any order.
+ *
+ * ff_mlp_pull_select_plan(dim, cond_dim, n_hidden, hidden_widths, plan_out): `dim` is the joint 2D and must be even
+ * (FF_ERR_BADARG); the envelope, preference and depth ceilings are ff_mlp_pull_plan's for that dim -- SiLU, fp32, hidden width
+ * <= 128 with dim <= 16, width <= 256 with dim <= 16 or dim <= 32; cond_dim <= 16 -- else FF_ERR_UNSUPPORTED.  The plan's
+ * kernel_id is FF_PULL_SELECT_KERNEL_BASE + an index (not entries of ff_kernel_count or ff_pull_kernel_count).
+ * ff_plan_kernel_name, ff_mlp_row_width and ff_mlp_samples_per_workgroup accept the plan; every other launch and packer
+ * refuses it with FF_ERR_BADARG (ff_mlp_wpack_floats, ff_mlp_pair_wpack_floats and ff_mlp_pull_wpack_floats return 0).
+ *
+ * ff_mlp_pull_select_wpack takes the arguments of ff_mlp_pair_wpack and writes ff_mlp_pull_select_wpack_floats(plan) = 2 x
+ * ff_mlp_pull_wpack_floats floats: [A_q | B_q | A_p | B_p], each half what ff_mlp_pull_wpack makes of that network embedded in
+ * the joint state as ff_mlp_pair_wpack embeds it (mlp_q: columns on the p half, rows 0..D-1; mlp_p: columns on the q half, rows
+ * D..2D-1, output weights and bias negated).
+ *
+ * ff_mlp_ode_launch_pull_select: the arguments, refusals, LDS bound and status bits of ff_mlp_ode_launch_pull; it refuses every
+ * plan that is not a pull-select plan (FF_ERR_BADARG), as ff_mlp_ode_launch_pull refuses this one.  cot_cond_out accumulates
+ * from both networks.  A leapfrog table names slot 0 only: args->stage_slots = 1 keeps one stage slot in LDS. */
+#define FF_PULL_SELECT_KERNEL_BASE 0xA0000
+int ff_pullsel_kernel_count(void);
+const char* ff_pullsel_kernel_name(int index);
+int ff_mlp_pull_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan_out);
+size_t ff_mlp_pull_select_wpack_floats(const ff_mlp_plan_t* plan);
+int ff_mlp_pull_select_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq,
+                             const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
+                             int x_col0, int c_col0, float* out);
+int ff_mlp_ode_launch_pull_select(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* cotangent_in /* [batch, K, dim] */,
+                                  float* cot_x_out /* [batch, K, dim] */, float* cot_cond_out /* [batch, K, cond_dim] or NULL */,
+                                  void* hip_stream);
+
 /* ---- streaming helpers beside the fused integrator (csrc/ff_aux.hip) --------------------------------- */
 
 /* Noise index reserved for the prior draw of a sample in the counter-based stream (never used by the
