@@ -347,6 +347,14 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_marginal_reduce.restype = L.ff_marginal_reduce_host.restype = ctypes.c_int
     L.ff_marginal_expand.argtypes, L.ff_marginal_expand_host.argtypes = expand + [ctypes.c_void_p], expand
     L.ff_marginal_reduce.argtypes, L.ff_marginal_reduce_host.argtypes = reduce + [ctypes.c_void_p], reduce
+    weigh = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_double,
+             ctypes.c_double] + [ctypes.c_void_p] * 4
+    mgrad = [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                     ctypes.c_void_p]
+    L.ff_marginal_weigh.restype = L.ff_marginal_weigh_host.restype = ctypes.c_int
+    L.ff_marginal_grad_reduce.restype = L.ff_marginal_grad_reduce_host.restype = ctypes.c_int
+    L.ff_marginal_weigh.argtypes, L.ff_marginal_weigh_host.argtypes = weigh + [ctypes.c_void_p], weigh
+    L.ff_marginal_grad_reduce.argtypes, L.ff_marginal_grad_reduce_host.argtypes = mgrad + [ctypes.c_void_p], mgrad
     obs_expand = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                   ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     lme = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
@@ -763,6 +771,98 @@ def marginal_reduce(z1: torch.Tensor, num_momenta: int, seed: int, sample_offset
     if rc != FF_OK:
         raise _err(rc, "ff_marginal_reduce")
     return out
+
+
+def marginal_weigh(z1: torch.Tensor, num_momenta: int, seed: int, sample_offset: int = 0, log_det: float = 0.0,
+                   min_weight: float = 0.0, out: Optional[torch.Tensor] = None, ess: Optional[torch.Tensor] = None):
+    """ff_marginal_weigh: ``(out [B], lw [B K] float64, keep [B K] int32)`` from ``z1`` [B K, 2 D]: ``out`` (and ``ess`` [B],
+    if given) bit for bit what ``marginal_reduce`` writes, every row's log-weight in double, and ``keep`` = 1 where draw k of
+    its point has a normalised weight ``exp(lw - max) / W`` that is > 0 and >= ``min_weight`` (0 <= min_weight < 1); a
+    degenerate point (a NaN among its ``lw``, or all -inf) keeps nothing.  ``out`` is allocated if None.  Device tensors on
+    the current stream; CPU tensors go to ff_marginal_weigh_host."""
+    dev = z1.device
+    K = int(num_momenta)
+    if not 1 <= K <= MAX_MOMENTA:
+        raise ValueError(f"num_momenta={num_momenta}: 1 .. {MAX_MOMENTA} momentum draws per data point")
+    m = float(min_weight)
+    if not 0.0 <= m < 1.0:
+        raise ValueError(f"min_weight={min_weight}: a normalised weight, 0 <= min_weight < 1 (0 keeps every draw of non-zero weight)")
+    if z1.dim() != 2 or z1.shape[0] % K or z1.shape[1] % 2 or z1.shape[1] < 2:
+        raise RuntimeError(f"marginal_weigh: z1 has shape {tuple(z1.shape)}, expected [B * {K}, 2 D]")
+    rows, D2 = z1.shape
+    B = rows // K
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    for t, name in ((out, "out"), (ess, "ess")):
+        if t is not None and t.numel() != B:
+            raise RuntimeError(f"marginal_weigh: {name} has {t.numel()} elements for {B} data points")
+    lw = torch.empty(rows, dtype=torch.float64, device=dev)
+    keep = torch.empty(rows, dtype=torch.int32, device=dev)
+    ptrs = (_chk(z1, "z1", dev), _chk(out, "out", dev), _chk(ess, "ess", dev))
+    if B == 0:
+        return out, lw, keep
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_weigh, L.ff_marginal_weigh_host,
+                    (ptrs[0], B, D2 // 2, K, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), float(log_det), m, ptrs[1],
+                     ptrs[2], lw.data_ptr(), keep.data_ptr()))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_weigh")
+    return out, lw, keep
+
+
+def marginal_grad_reduce(lw: torch.Tensor, row_of: torch.Tensor, gz_rows: torch.Tensor, gc_rows: Optional[torch.Tensor],
+                         num_momenta: int, scale: Optional[torch.Tensor] = None, cond_scale: Optional[torch.Tensor] = None,
+                         grad_x: Optional[torch.Tensor] = None, grad_c: Optional[torch.Tensor] = None):
+    """ff_marginal_grad_reduce: ``(grad_x [B, D], grad_c [B, C] or None)``, the gradient of ``marginal_weigh``'s ``out`` from
+    the kept rows' pull-backs of ``-z1``: ``sum_k wn_k gz_rows[row_of[r K + k]][:D] / scale`` and ``sum_k wn_k
+    gc_rows[row_of[r K + k]] / cond_scale``; ``wn`` the normalised weights of the full sum, recomputed from ``lw`` [B K]
+    float64.  ``row_of`` [B K] int32: the row of a draw in ``gz_rows`` [n, 2 D] / ``gc_rows`` [n, C], < 0 for a draw that is
+    skipped (checked here to stay below n).  ``scale`` [D] / ``cond_scale`` [C]: None for 1.  The outputs are allocated where
+    not given.  Device tensors on the current stream; CPU tensors go to ff_marginal_grad_reduce_host."""
+    dev = lw.device
+    K = int(num_momenta)
+    if not 1 <= K <= MAX_MOMENTA:
+        raise ValueError(f"num_momenta={num_momenta}: 1 .. {MAX_MOMENTA} momentum draws per data point")
+    if lw.dtype != torch.float64 or lw.dim() != 1 or lw.numel() % K or not lw.is_contiguous():
+        raise RuntimeError(f"marginal_grad_reduce: lw must be a contiguous float64 tensor [B * {K}], got {lw.dtype} "
+                           f"{tuple(lw.shape)}")
+    B = lw.numel() // K
+    if gz_rows.dim() != 2 or gz_rows.shape[1] % 2 or gz_rows.shape[1] < 2:
+        raise RuntimeError(f"marginal_grad_reduce: gz_rows has shape {tuple(gz_rows.shape)}, expected [n, 2 D]")
+    n, D = int(gz_rows.shape[0]), int(gz_rows.shape[1]) // 2
+    if gc_rows is not None and (gc_rows.dim() != 2 or gc_rows.shape[0] != n or gc_rows.shape[1] < 1):
+        raise RuntimeError(f"marginal_grad_reduce: gc_rows has shape {tuple(gc_rows.shape)}, expected [{n}, C >= 1]")
+    C = 0 if gc_rows is None else int(gc_rows.shape[1])
+    if row_of.dtype != torch.int32 or row_of.numel() != B * K or not row_of.is_contiguous() or row_of.device != dev:
+        raise RuntimeError(f"marginal_grad_reduce: row_of must be a contiguous int32 tensor of {B * K} elements on {dev}")
+    if B > 0 and int(row_of.max()) >= n:
+        raise RuntimeError(f"marginal_grad_reduce: row_of points at row {int(row_of.max())}, gz_rows has {n} rows")
+    if gc_rows is None:
+        cond_scale = None
+    for t, name, cols in ((scale, "scale", D), (cond_scale, "cond_scale", C)):
+        if t is not None and t.numel() != cols:
+            raise RuntimeError(f"marginal_grad_reduce: {name} has {t.numel()} elements for {cols} columns")
+    if grad_x is None:
+        grad_x = torch.empty(B, D, dtype=torch.float32, device=dev)
+    if grad_c is None and gc_rows is not None:
+        grad_c = torch.empty(B, C, dtype=torch.float32, device=dev)
+    for t, name, cols in ((grad_x, "grad_x", D), (grad_c, "grad_c", C)):
+        if t is not None and t.numel() != B * cols:
+            raise RuntimeError(f"marginal_grad_reduce: {name} has {t.numel()} elements for [{B}, {cols}]")
+    if n == 0:                                              # nothing was kept: no row is read, but the pointer is mandatory
+        gz_rows = torch.zeros(1, 2 * D, dtype=torch.float32, device=dev)
+        gc_rows = None if gc_rows is None else torch.zeros(1, C, dtype=torch.float32, device=dev)
+    ptrs = (_chk(gz_rows, "gz_rows", dev), _chk(gc_rows, "gc_rows", dev), _chk(scale, "scale", dev),
+            _chk(cond_scale, "cond_scale", dev), _chk(grad_x, "grad_x", dev),
+            _chk(grad_c if gc_rows is not None else None, "grad_c", dev))
+    if B == 0:
+        return grad_x, grad_c
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_grad_reduce, L.ff_marginal_grad_reduce_host,
+                    (lw.data_ptr(), row_of.data_ptr(), ptrs[0], ptrs[1], ptrs[2], ptrs[3], B, D, C, K, ptrs[4], ptrs[5]))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_grad_reduce")
+    return grad_x, grad_c
 
 
 def observe_expand(x: torch.Tensor, noise_std: torch.Tensor, num_draws: int, seed: int, sample_offset: int = 0,

@@ -1,6 +1,7 @@
 // ff_marginal.h -- the arithmetic of the K-draw marginal log-density of the symplectic flows, shared by the gfx950
 // kernels (ff_marginal.hip: marginal_expand_kernel / marginal_reduce_kernel) and the host entry points the CPU tests
-// call (ff_marginal_expand_host / ff_marginal_reduce_host, compiled from the host pass of the same file).
+// call (ff_marginal_expand_host / ff_marginal_reduce_host, compiled from the host pass of the same file) -- and, further
+// down, of its gradient (marginal_weigh_kernel / marginal_grad_reduce_kernel and their _host twins).
 //
 // What is restated here, and from where: SymplecticFlowModel.log_prob, flowfusion/symplectic.py:204-253, draws ONE
 // momentum p0 per data point and returns log N(z1) - log N(p0) - sum log scale.  The flow preserves volume in [q | p],
@@ -146,6 +147,42 @@ FF_HD void lse_finish(const Lse& a, int K, double log_det, float* logp, float* e
 #pragma clang fp contract(off)
     *logp = (float)(a.m + log(a.s1) - log((double)K) - log_det);
     if (ess) *ess = (float)(a.s1 * a.s1 / a.s2);
+}
+
+// ---- the gradient of the K-draw marginal (ff_marginal_weigh / ff_marginal_grad_reduce) -------------------------------------
+// With the momenta fixed, L = logsumexp_k lw_k - log K - log_det has dL / d lw_k = wn_k = exp(lw_k - max lw) / W, so its
+// gradients are the wn-weighted sums of the rows' own gradients of lw_k = log N(z1_k) - log N(p0_k): the q half of the
+// pull-back of -z1_k through the solve, and its conditional part.  A draw whose normalised weight is 0, or below the
+// caller's min_weight, adds nothing (at most min_weight |g_k|): it is not KEPT, and its row is never pulled back or read.
+
+// a point without a gradient: a NaN among its lw (s1 is NaN) or none above -inf (s1 = 0)
+FF_HD bool lse_degenerate(const Lse& a) { return !(a.s1 > 0.0); }
+
+// draw k of a point whose merged state is (m, s1) is kept iff its normalised weight is positive and >= min_weight: the
+// rule of observe::keep_draw on the double lw
+FF_HD int32_t keep_weight(double lw, double m, double s1, double min_weight)
+{
+#pragma clang fp contract(off)
+    const double wn = lse_factor(lw, m) / s1;
+    return wn > 0.0 && wn >= min_weight ? 1 : 0;
+}
+
+// the maximum of the lw seen so far (exact in any order) and whether a NaN was among them
+FF_HD void max_add(double& m, int& bad, double lw)
+{
+    bad |= lw != lw;
+    m = lw > m ? lw : m;
+}
+
+// one entry of a gradient: the weighted sum times 1 / W, over the unit of that column (scale[d] / conditional_scale[c];
+// NULL: 1), all in double, rounded to fp32 once.  At K = 1 the sum is the row's own float and W = 1: a division of two
+// floats through double is the correctly rounded fp32 quotient.
+FF_HD float grad_finish(double sum, double rW, const float* unit, int d)
+{
+#pragma clang fp contract(off)
+    double v = sum * rW;
+    if (unit) v = v / (double)unit[d];
+    return (float)v;
 }
 
 // lanes that share one row on the device: the power of two >= ceil(D / 4), at most a wavefront

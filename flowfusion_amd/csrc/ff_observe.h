@@ -125,5 +125,28 @@ FF_HD void noise_add(double (&acc)[4], double w, const float (&z)[4], const floa
     for (int j = 0; j < 4; ++j) acc[j] += w * ((double)z[j] * (double)g[j]);
 }
 
+#if defined(__HIPCC__)
+// ---- what the lane groups of the weighted sums share on the device (ff_observe.hip; ff_marginal.hip: marginal_grad_reduce_kernel)
+// the (up to four) dimensions 4 blk .. of one row, zero beyond D
+__device__ __forceinline__ void load_block(const float* row, int d0, int D, int vec, float (&v)[4])
+{
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    if (vec) {
+        const v4f t = *(const v4f*)(row + d0);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = d0 + j < D ? row[d0 + j] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void group_sum4(double (&acc)[4], int G)
+{
+    for (int off = 1; off < G; off <<= 1)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);       // (a + b == b + a: every lane holds the same bits)
+}
+#endif
+
 } // namespace observe
 } // namespace ff

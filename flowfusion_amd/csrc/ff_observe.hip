@@ -155,25 +155,6 @@ struct ResampleArgs {
     int vec;                        // y and samples move as 16-byte elements
 };
 
-// the (up to four) dimensions 4 blk .. of one row, zero beyond D
-__device__ __forceinline__ void load_block(const float* row, int d0, int D, int vec, float (&v)[4])
-{
-    if (vec) {
-        const v4f t = *(const v4f*)(row + d0);
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = d0 + j < D ? row[d0 + j] : 0.f;
-    }
-}
-
-__device__ __forceinline__ void group_sum4(double (&acc)[4], int G)
-{
-    for (int off = 1; off < G; off <<= 1)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] += __shfl_xor(acc[j], off);       // (a + b == b + a: every lane holds the same bits)
-}
-
 __global__ __launch_bounds__(256) void weighted_resample_kernel(const ResampleArgs a)
 {
     const int G = 1 << a.log_g, K = a.K, D = a.D, M = a.M, nblk = (D + 3) / 4;

@@ -742,14 +742,41 @@ def solve_leapfrog_pull(front, z, grid, cotangents, cond=None, return_retrace=Fa
     return _solve_leapfrog_pull(front, z, grid, cotangents, cond, return_retrace, 1)
 
 
+def _leapfrog_pull_from(front, z_out, grid, cotangents, cond):
+    """The backward half of ``_solve_leapfrog_pull``, for a caller that already holds ``z_out`` = ``solve_leapfrog(front, z,
+    grid, cond)`` [n, 2D] (``log_prob_marginal_grad``: its one forward solve serves the weights and this): the pull-back of
+    ``cotangents`` [n, K, 2D] from ``z_out`` by ``FusedPair.pullback_select`` on the table of the flipped grid -- under
+    ``_solve_leapfrog_pull``'s cache key, its rows cut by the same rule under ``PROBE_BUFFER_FLOATS``.  Returns ``(z_back [n,
+    2D], gz [n, K, 2D], gc [n, K, C] or None)`` and sets ``front.last_solver_stats`` to this half's ``evaluations`` and
+    ``launches``.  Checks nothing: ``_leapfrog_pull_checks`` is the caller's."""
+    net = front._net()
+    n, K, D2 = (int(v) for v in cotangents.shape)
+    C = net.cond_dim
+    grid = torch.as_tensor(grid).detach().to("cpu", torch.float32).reshape(-1)
+    back = torch.flip(grid, dims=(0,))
+    key = ("leapfrog_pull", tuple(float(v) for v in back)) + front._schedule_key()
+    table = net.cached_table(key, z_out.device, lambda: front._leapfrog_table(back, pull_select=True))
+    rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D2))
+    pieces = [(r0, min(n, r0 + rows)) for r0 in range(0, n, rows)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    backs, gzs, gcs = [], [], []
+    for r0, r1 in pieces:
+        zb, gz, gc, _ = net.pullback_select(cut(z_out, r0, r1), table, cut(cotangents, r0, r1), cond=cut(cond, r0, r1),
+                                            want_cond=C > 0, stage_slots=1)
+        backs.append(zb)
+        gzs.append(gz)
+        gcs.append(gc)
+    front.last_solver_stats = {"evaluations": int(table.shape[0]), "launches": len(pieces)}
+    zb, gz = (backs[0], gzs[0]) if whole else (torch.cat(backs), torch.cat(gzs))
+    return zb, gz, (None if C == 0 else (gcs[0] if whole else torch.cat(gcs)))
+
+
 def _solve_leapfrog_pull(front, z, grid, cotangents, cond, return_retrace, num_cotangents):
     """``solve_leapfrog_pull`` whose ``cotangents`` may also be a function ``z_out piece [rows, 2D] -> [rows, num_cotangents,
     2D]``, evaluated per piece of rows between the two launches: how ``log_prob_leapfrog_grad`` hands over ``-z1``."""
     net, B, D2, K, C = _leapfrog_pull_checks(front, z, cotangents, cond, num_cotangents)
     grid = torch.as_tensor(grid).detach().to("cpu", torch.float32).reshape(-1)
-    back = torch.flip(grid, dims=(0,))
-    key = ("leapfrog_pull", tuple(float(v) for v in back)) + front._schedule_key()
-    table = net.cached_table(key, z.device, lambda: front._leapfrog_table(back, pull_select=True))
     rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D2))
     pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
     whole = len(pieces) == 1
@@ -762,12 +789,13 @@ def _solve_leapfrog_pull(front, z, grid, cotangents, cond, return_retrace, num_c
         w = cotangents(zo) if callable(cotangents) else cut(cotangents, r0, r1)
         if callable(cotangents) and (w.dim() != 3 or tuple(w.shape) != (r1 - r0, K, D2)):
             raise ValueError(f"leapfrog pull-backs: the cotangent function returned {tuple(w.shape)}, expected {(r1 - r0, K, D2)}")
-        zb, gz, gc, _ = net.pullback_select(zo, table, w, cond=cut(cond, r0, r1), want_cond=C > 0, stage_slots=1)
+        zb, gz, gc = _leapfrog_pull_from(front, zo, grid, w, cut(cond, r0, r1))        # (a piece is within its cut: one launch)
+        evals += front.last_solver_stats["evaluations"]
         outs.append(zo)
         backs.append(zb)
         gzs.append(gz)
         gcs.append(gc)
-    front.last_solver_stats = {"evaluations": evals + int(table.shape[0]), "launches": 2 * len(pieces)}
+    front.last_solver_stats = {"evaluations": evals, "launches": 2 * len(pieces)}
     zo, zb, gz = (outs[0], backs[0], gzs[0]) if whole else (torch.cat(outs), torch.cat(backs), torch.cat(gzs))
     gc = None if C == 0 else (gcs[0] if whole else torch.cat(gcs))
     if not return_retrace:

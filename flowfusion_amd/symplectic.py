@@ -16,7 +16,8 @@ the other half, so the discrete map preserves volume and ``log_prob_leapfrog(x, 
 launch, no step controller -- is the exact density of what ``sample_leapfrog(shape, num_steps=n)`` applies.
 ``log_prob_marginal`` (extension) averages the importance weights of K momentum draws per data point -- the marginal over
 the momentum that ``log_prob`` estimates from one draw -- with a streaming kernel at each end of the solve
-(csrc/ff_marginal.hip).  Networks outside the compiled pair
+(csrc/ff_marginal.hip); ``log_prob_marginal_grad`` (extension) adds its exact gradient with respect to the data and the
+raw conditional: one forward solve, one backward launch on the rows that carry weight.  Networks outside the compiled pair
 shapes, non-SiLU activations and any other ``model`` with the same ``forward(t, state, conditional)`` are evaluated by
 torch with the stepping in the library (generic.py; ``FusedEnvelopeWarning`` for the first two).  GPU only: CPU tensors
 raise.  The reference draws a tqdm progress bar in ``sample``; this module does not.
@@ -192,8 +193,9 @@ class SymplecticFlowModel(nn.Module):
         evaluation that gave it its slopes, so the retrace is within rounding BY CONSTRUCTION; it says nothing about the
         step count.  It exists to show a non-finite or exploding trajectory.
 
-        Fused route only (``_native.PULL_SELECT_ENVELOPE``); the gradient of ``log_prob_marginal``, Euler ``sample`` and
-        dopri5 ``log_prob`` pull-backs, parameter gradients and torch.autograd integration are out of scope."""
+        Fused route only (``_native.PULL_SELECT_ENVELOPE``); Euler ``sample`` and dopri5 ``log_prob`` pull-backs, parameter
+        gradients and torch.autograd integration are out of scope (the gradient of the K-draw marginal:
+        ``log_prob_marginal_grad``)."""
         self._check_log_prob_method("leapfrog", num_steps)
         if not torch.is_tensor(x) or x.dim() != 2:
             raise ValueError("log_prob_leapfrog_grad: x must be a [batch, dim] tensor")
@@ -350,6 +352,97 @@ class SymplecticFlowModel(nn.Module):
             _native.marginal_reduce(z1, K, seed, first + lo, log_det, out[lo:hi], None if ess is None else ess[lo:hi])
             del z1
         return (out, ess) if return_ess else out
+
+    @torch.no_grad()
+    def log_prob_marginal_grad(self, x, conditional=None, num_momenta=16, *, method="leapfrog", num_steps=None, seed=None,
+                               sample_offset=0, chunk_points=None, min_weight=0.0, return_ess=False):
+        """``log_prob_marginal(..., method="leapfrog")`` and its gradient with respect to ``x`` and the raw ``conditional``
+        (the population hyper-parameters): what a hierarchical fit asks of this model class.  Returns ``(log_p [B], grad_x
+        [B, D], grad_c [B, C] or None)``, then ``ess [B]`` with ``return_ess``; ``log_p`` and ``ess`` are bitwise
+        ``log_prob_marginal(x, conditional, num_momenta, method="leapfrog", num_steps=num_steps, seed=seed,
+        sample_offset=sample_offset, return_ess=True)``.
+
+        With the momenta ``p_k`` of the counter-based stream fixed, ``lw_k = log N(z1_k) - log N(p_k)`` and ``wn_k = exp(lw_k -
+        max lw) / W`` (double), the gradient of ``logsumexp_k lw_k - log K - sum log scale`` is ``sum_k wn_k g_q,k / scale`` for
+        ``x`` and ``sum_k wn_k gamma_k / conditional_scale`` for ``conditional``, ``(g_q,k | g_p,k)`` and ``gamma_k`` the
+        pull-back of the one cotangent ``-z1_k`` through the transpose of the discrete leapfrog (``g_p`` is not needed: the
+        momenta are constants of the estimate) -- the exact gradient of the returned value at that seed, at any step count.
+
+        Per chunk of points (the chunk rule and the seed rule of ``log_prob_marginal``): ff_marginal_expand -> ONE forward
+        ``solve_leapfrog`` of the rows -> ff_marginal_weigh (``log_p``, ``ess``, the rows' ``lw`` in double and which rows are
+        kept) -> the kept rows of ``z1`` and the conditional gathered in order -> ``odeint._leapfrog_pull_from`` from ``z1``
+        itself (no second forward solve) -> ff_marginal_grad_reduce.  Draw k is kept iff ``wn_k > 0`` and ``wn_k >=
+        min_weight``; the sums take the weights of the FULL ``W``, not renormalised, so ``min_weight`` = m > 0 truncates the
+        gradient by at most ``K m max |grad lw|``.  A point with a NaN among its ``lw``, or with ``W = 0``, has NaN gradients.
+        Rows and points are independent: any ``chunk_points``, and any slice of the batch at its ``sample_offset``, gives
+        bitwise the same.  ``self.last_marginal_grad_stats``: ``rows`` (B K), ``rows_kept`` (what reached the backward
+        launch) and ``launches`` (``{"forward", "backward"}``: one each per piece of rows).
+
+        Refused before the device is touched, in this order: ``num_momenta``, ``min_weight``, ``chunk_points`` (ValueError);
+        a ``method`` other than ``"leapfrog"`` (ValueError); ``num_steps`` missing or < 1 (ValueError); then every refusal of
+        the leapfrog pull-backs (``odeint._leapfrog_pull_checks``).  Fused route only (``_native.PULL_SELECT_ENVELOPE``), no
+        module-path fallback; adaptive, Euler and dopri5 marginals, a momentum gradient, parameter gradients and torch.autograd
+        integration are out of scope."""
+        K = int(num_momenta)
+        if not 1 <= K <= _native.MAX_MOMENTA:
+            raise ValueError(f"num_momenta={num_momenta}: 1 .. {_native.MAX_MOMENTA} momentum draws per data point")
+        m = float(min_weight)
+        if not 0.0 <= m < 1.0:
+            raise ValueError(f"min_weight={min_weight}: a normalised weight, 0 <= min_weight < 1 (0 keeps every draw of non-zero "
+                             "weight)")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
+        if method != "leapfrog":
+            raise ValueError(f"log_prob_marginal_grad: method={method!r}: Euler and dopri5 rows are not shears, so their pull-back "
+                             "needs a record of the stage states, which the two-network kernels do not keep; use "
+                             "method=\"leapfrog\" with num_steps (every row a shear: the exact gradient of the value it returns)")
+        self._check_log_prob_method("leapfrog", num_steps)
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise ValueError("log_prob_marginal_grad: x must be a [batch, dim] tensor")
+        B, D = int(x.shape[0]), int(x.shape[1])
+        # (shapes, dtypes and devices only: the raw conditional and an unwritten joint state stand in for the rows)
+        _, _, _, _, C = odeint._leapfrog_pull_checks(self, x.new_empty((B, 2 * D)), lambda z1: None, conditional, 1)
+        chunk = max(1, self.MARGINAL_CHUNK_ROWS // K) if chunk_points is None else int(chunk_points)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed, first = int(seed), int(sample_offset)
+        x = x.contiguous()
+        cond = self._norm_cond(conditional)
+        cond = None if cond is None else cond.contiguous()
+        log_det = 0.0 if self.scale is None else float(torch.log(self.scale.double()).sum())
+        scale = _native.f32_on(self.scale, x.device)
+        cscale = _native.f32_on(self.conditional_scale, x.device) if C > 0 else None
+        new = lambda cols: torch.empty(B, cols, dtype=torch.float32, device=x.device)
+        out, ess = new(1).view(B), (new(1).view(B) if return_ess else None)
+        gx, gcond = new(D), (new(C) if C > 0 else None)
+        grid = torch.linspace(1.0, 0.0, int(num_steps) + 1).flip(0)                     # (as _solve_forward builds it)
+        kept = forward = backward = 0
+        for lo in range(0, B, chunk):
+            hi = min(B, lo + chunk)
+            z0, ck = _native.marginal_expand(x[lo:hi], K, seed, first + lo, self.shift, self.scale,
+                                             None if cond is None else cond[lo:hi])
+            z1 = self._solve_forward(z0, ck, None, None, "leapfrog", None, num_steps)
+            forward += int(self.last_solver_stats["launches"])
+            del z0
+            _, lw, keep = _native.marginal_weigh(z1, K, seed, first + lo, log_det, m, out[lo:hi],
+                                                 None if ess is None else ess[lo:hi])
+            rows = torch.nonzero(keep).view(-1)                 # the kept rows in order: row_of is their rank
+            n = int(rows.numel())
+            row_of = torch.where(keep > 0, torch.cumsum(keep, 0, dtype=torch.int32) - 1, -1).to(torch.int32)
+            if n == 0:
+                gz, gc = z1.new_zeros(0, 2 * D), (None if C == 0 else z1.new_zeros(0, C))
+            else:
+                take = lambda t: None if t is None else (t if n == t.shape[0] else t.index_select(0, rows))
+                zk = take(z1)
+                _, gz, gc = odeint._leapfrog_pull_from(self, zk, grid, (-zk)[:, None, :], take(ck))
+                backward += int(self.last_solver_stats["launches"])
+                gz, gc = gz[:, 0], (None if gc is None else gc[:, 0])
+                del zk
+            kept += n
+            _native.marginal_grad_reduce(lw, row_of, gz, gc, K, scale, cscale, gx[lo:hi], None if gcond is None else gcond[lo:hi])
+            del z1, ck, lw, keep, gz, gc
+        self.last_marginal_grad_stats = {"rows": B * K, "rows_kept": kept, "launches": {"forward": forward, "backward": backward}}
+        return (out, gx, gcond) + ((ess,) if return_ess else ())
 
     # -- what odeint.solve asks of a front end -------------------------------------------------------
     def _layers(self):

@@ -729,6 +729,60 @@ int ff_marginal_expand_host(const float* x, const float* shift, const float* sca
 int ff_marginal_reduce_host(const float* z1, int64_t B, int32_t D, int32_t K, uint64_t seed, int64_t sample_offset,
                             double log_det, float* out_logp, float* out_ess);
 
+/* ---- the gradient of the K-draw marginal log-density (csrc/ff_marginal.hip, csrc/ff_marginal.h) ---------------------
+ *
+ * With the momenta fixed (the counter-based stream), L[r] = logsumexp_k lw_k - log K - log_det of ff_marginal_reduce has
+ * dL / d lw_k = wn_k, the normalised weight of draw k, and lw_k = log N(z1_k) - log N(p0_k) depends on x and the
+ * conditional through z1_k alone: its gradient is the pull-back of the one cotangent -z1_k through the solve (whatever
+ * computes it; the library's: ff_mlp_ode_launch_pull_select on the flipped leapfrog table), (g_q,k | g_p,k) for the joint
+ * state and gamma_k for the normalised conditional.  Per data point r, in double:
+ *     w_k = exp(lw_k - max_k lw),   W = sum_k w_k,   wn_k = w_k / W
+ *     grad_x[r][d] = (sum_k w_k g_q,kd / W) / scale[d]
+ *     grad_c[r][c] = (sum_k w_k gamma_kc / W) / cond_scale[c]
+ * the exact gradient of L with respect to x and the raw conditional; g_p is not read (the momenta are constants of the
+ * estimate).  The sums run over KEPT draws only, with the weights of the full W:
+ * ff_marginal_weigh:  ff_marginal_reduce -- its lanes, units, log-sum-exp states and butterflies: out_logp and out_ess are
+ *   its results bit for bit -- that also stores every row's lw_k in double (lw_out [B K]) and, once the point's merged
+ *   state is in every lane, keep[r K + k] = (wn_k > 0 && wn_k >= min_weight) ? 1 : 0 with wn_k = exp(lw_k - m) / s1 in
+ *   double: the rule of ff_observe_keep.  A lane re-reads only the lw_out entries it stored itself: one kernel, no fence.
+ *   0 <= min_weight < 1; 0 keeps every draw of non-zero weight.  A skipped draw would have added wn_k g_k: the
+ *   truncation is at most sum_skipped wn_k |g_k| <= K min_weight max |g|.  A degenerate point (a NaN among its lw, or all
+ *   -inf: W = 0) keeps nothing.  z1 [B K][2 D]; out_logp [B]; out_ess [B] or NULL; lw_out [B K] double; keep [B K] int32.
+ *   FF_ERR_BADARG: the cases of ff_marginal_reduce (z1 or out_logp NULL; B < 0; D < 1; K outside 1 .. 4096); lw_out or
+ *   keep NULL; min_weight outside [0, 1).
+ * ff_marginal_grad_reduce:  row_of [B K] int32 says where the pull-back of draw (r, k) lies: row row_of[r K + k] of
+ *   gz_rows [n][2 D] and gc_rows [n][C], or < 0 for a draw that was not kept -- no row of it is read and it adds nothing (the
+ *   order-preserving compaction of keep: cumsum(keep) - 1 where kept; every entry must be below n).  The q half of a gz row
+ *   is read in place (row stride 2 D: no slice copy).  gc_rows may be NULL (C, cond_scale and grad_c are then ignored);
+ *   scale [D] and cond_scale [C] may be NULL (1).  A lane group of lanes_per_point(K) lanes with contiguous segments of
+ *   draws, as ff_observe_grad_reduce: the weights recomputed from the double lw, one block of four dimensions at a time
+ *   accumulated over the lane's draws in index order and merged by the fixed butterfly, times the double 1 / W (one
+ *   division per point), over scale[d] (cond_scale[c]) in double, rounded to fp32 once.  A degenerate point writes NaN to
+ *   both gradients.  K = 1 with a finite lw: grad_x is the correctly rounded fp32 quotient g_q / scale (a division of two
+ *   floats through double rounds once), grad_c likewise.  16-byte accesses on gz_rows (gc_rows) where they are 16-byte
+ *   aligned and D % 4 == 0 (C % 4 == 0), a scalar body otherwise.
+ *   FF_ERR_BADARG, before anything is enqueued: lw, row_of, gz_rows or grad_x NULL; B < 0; D < 1; K outside 1 .. 4096;
+ *   gc_rows given with C < 1 or grad_c NULL.
+ * A data point's results are fixed by (K, D) and its own data, not by B, its position or the launch: chunks (sample_offset
+ * + first point of the chunk) and shards give bitwise the same.  DEVICE pointers, enqueued on hip_stream; B == 0 is FF_OK
+ * without a launch.  The _host twins run the same header arithmetic on HOST pointers: ff_marginal_weigh_host with rows and
+ * units in index order (lw agrees to double rounding; the normals through libm), ff_marginal_grad_reduce_host in the
+ * device's own order of additions (given the same lw the two differ only where libm's exp and the device's differ in the
+ * last bit of a double).
+ */
+int ff_marginal_weigh(const float* z1, int64_t B, int32_t D, int32_t K, uint64_t seed, int64_t sample_offset,
+                      double log_det, double min_weight, float* out_logp, float* out_ess, double* lw_out, int32_t* keep,
+                      void* hip_stream);
+int ff_marginal_grad_reduce(const double* lw, const int32_t* row_of, const float* gz_rows, const float* gc_rows,
+                            const float* scale, const float* cond_scale, int64_t B, int32_t D, int32_t C, int32_t K,
+                            float* grad_x, float* grad_c, void* hip_stream);
+int ff_marginal_weigh_host(const float* z1, int64_t B, int32_t D, int32_t K, uint64_t seed, int64_t sample_offset,
+                           double log_det, double min_weight, float* out_logp, float* out_ess, double* lw_out,
+                           int32_t* keep);
+int ff_marginal_grad_reduce_host(const double* lw, const int32_t* row_of, const float* gz_rows, const float* gc_rows,
+                                 const float* scale, const float* cond_scale, int64_t B, int32_t D, int32_t C, int32_t K,
+                                 float* grad_x, float* grad_c);
+
 /* ---- log-density of noisy observations over K noise draws (csrc/ff_observe.hip, csrc/ff_observe.h) ------------------
  *
  * Every log-density of the reference (ScoreModel.log_prob diffusion.py:756-815, ODEFlow.log_prob flow.py:386-438, the
