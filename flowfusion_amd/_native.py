@@ -96,6 +96,7 @@ STATUS_NOISE_ROW = 4                                        # FF_STATUS_NOISE_RO
 MAX_PUSH_TANGENTS = 15                                      # tangent columns beside the value column of a 16-column tile
 PULL_KERNEL_BASE = 0x50000                                  # FF_PULL_KERNEL_BASE
 PULL_SELECT_KERNEL_BASE = 0xA0000                           # FF_PULL_SELECT_KERNEL_BASE
+PUSH_SELECT_KERNEL_BASE = 0xB0000                           # FF_PUSH_SELECT_KERNEL_BASE
 MAX_PULL_COTANGENTS = 15                                    # cotangent columns beside the value column of a 16-column tile
 VJP_KERNEL_BASE = 0x60000                                   # FF_VJP_KERNEL_BASE
 MAX_VJP_SEEDS = 15                                          # seed columns beside the value column of a 16-column tile
@@ -300,6 +301,18 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_mlp_pull_select_wpack.argtypes = [ctypes.POINTER(PlanStruct)] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
     L.ff_mlp_ode_launch_pull_select.restype = ctypes.c_int
     L.ff_mlp_ode_launch_pull_select.argtypes = L.ff_mlp_ode_launch_pull.argtypes
+    L.ff_pushsel_kernel_count.restype = ctypes.c_int
+    L.ff_pushsel_kernel_name.restype = ctypes.c_char_p
+    L.ff_pushsel_kernel_name.argtypes = [ctypes.c_int]
+    L.ff_mlp_push_select_plan.restype = ctypes.c_int
+    L.ff_mlp_push_select_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_push_select_wpack_floats.restype = ctypes.c_size_t
+    L.ff_mlp_push_select_wpack_floats.argtypes = [ctypes.POINTER(PlanStruct)]
+    L.ff_mlp_push_select_wpack.restype = ctypes.c_int
+    L.ff_mlp_push_select_wpack.argtypes = [ctypes.POINTER(PlanStruct)] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p]
+    L.ff_mlp_ode_launch_push_select.restype = ctypes.c_int
+    L.ff_mlp_ode_launch_push_select.argtypes = L.ff_mlp_ode_launch_push.argtypes
     L.ff_vjp_kernel_count.restype = ctypes.c_int
     L.ff_vjp_kernel_name.restype = ctypes.c_char_p
     L.ff_vjp_kernel_name.argtypes = [ctypes.c_int]
@@ -592,7 +605,7 @@ def make_pull_select_plan(dim: int, cond_dim: int, hidden: List[int]) -> PlanStr
 
 
 def is_pull_select_plan(plan: PlanStruct) -> bool:
-    return int(plan.kernel_id) >= PULL_SELECT_KERNEL_BASE
+    return PULL_SELECT_KERNEL_BASE <= int(plan.kernel_id) < PUSH_SELECT_KERNEL_BASE
 
 
 def pack_pull_select_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[int], x_col0: int, c_col0: int) -> torch.Tensor:
@@ -613,6 +626,50 @@ def pack_pull_select_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[
                                     x_col0, c_col0, out.data_ptr())
     if rc != FF_OK:
         raise _err(rc, "ff_mlp_pull_select_wpack")
+    return out
+
+
+PUSH_SELECT_ENVELOPE = ("the row-select push-forward kernels (sample_leapfrog_jvp / sample_leapfrog_jacobian) hold two SiLU networks "
+                        "of one shape in f32 with hidden widths up to 256, joint states [q | p] of up to 32 dimensions (16 per half) "
+                        "and up to 16 conditional inputs, and up to 15 tangents per sample")
+
+
+def make_push_select_plan(dim: int, cond_dim: int, hidden: List[int]) -> PlanStruct:
+    """ff_mlp_push_select_plan: the row-select push-forward unit for a joint state of ``dim`` = 2D dimensions
+    (NotImplementedError with the envelope if none holds it)."""
+    p = PlanStruct()
+    arr = (ctypes.c_int * len(hidden))(*hidden)
+    rc = lib().ff_mlp_push_select_plan(dim, cond_dim, len(hidden), arr, ctypes.byref(p))
+    if rc == FF_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"no gfx950 row-select push-forward kernel for a joint state of {dim} dimensions, cond_dim={cond_dim}, "
+                                  f"units={hidden}: {PUSH_SELECT_ENVELOPE}")
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_push_select_plan")
+    return p
+
+
+def is_push_select_plan(plan: PlanStruct) -> bool:
+    return int(plan.kernel_id) >= PUSH_SELECT_KERNEL_BASE
+
+
+def pack_push_select_weights(plan: PlanStruct, q_layers, p_layers, hidden: List[int], x_col0: int, c_col0: int) -> torch.Tensor:
+    """ff_mlp_push_select_wpack on host copies of the two networks' nn.Linear parameters: two forward packs, mlp_q's then
+    mlp_p's; returns the packed CPU tensor."""
+    L = lib()
+    n = L.ff_mlp_push_select_wpack_floats(ctypes.byref(plan))
+    out = torch.empty(n, dtype=torch.float32)
+    keep, ptrs = [], []
+    for layers in (q_layers, p_layers):
+        ws = [f32_on(l.weight, "cpu") for l in layers]
+        bs = [f32_on(l.bias, "cpu") for l in layers]
+        keep += ws + bs
+        ptrs.append((ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws]))
+        ptrs.append((ctypes.c_void_p * len(bs))(*[b.data_ptr() for b in bs]))
+    hw = (ctypes.c_int * len(hidden))(*hidden)
+    rc = L.ff_mlp_push_select_wpack(ctypes.byref(plan), ptrs[0], ptrs[1], ptrs[2], ptrs[3], hw, int(q_layers[0].weight.shape[1]),
+                                    x_col0, c_col0, out.data_ptr())
+    if rc != FF_OK:
+        raise _err(rc, "ff_mlp_push_select_wpack")
     return out
 
 
@@ -1267,10 +1324,11 @@ def _row_ptrs(t: torch.Tensor) -> ctypes.Array:
 
 
 def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Tensor] = None, push=None, pull=None, vjp=None,
-                record=None, discrete=None, logp_grad=None, pull_select=None, **fields) -> None:
-    """The one launch of the eleven ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
+                record=None, discrete=None, logp_grad=None, pull_select=None, push_select=None, **fields) -> None:
+    """The one launch of the twelve ops below, on torch's current stream of ``dev``: ff_mlp_ode_launch,
     ff_mlp_ode_launch_probes where the op allocated a ``per_probe`` [B, K] buffer, ff_mlp_ode_launch_push with
-    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])``, ff_mlp_ode_launch_pull with
+    ``push = (cond_tangents [B, K, C] or None, tangent_out [B, K, D])`` (ff_mlp_ode_launch_push_select with the same pair as
+    ``push_select``, on a push-select plan), ff_mlp_ode_launch_pull with
     ``pull = (cotangents [B, K, D], cot_x_out [B, K, D], cot_cond_out [B, K, C] or None)``, or ff_mlp_ode_launch_vjp with
     ``vjp = (seeds, seed_row_stride, prod_out [n_evals, B, K, D])``, ff_mlp_ode_launch_record with ``record = record_out
     [n_evals, B, D]``, or ff_mlp_ode_launch_pull_discrete with ``discrete = (record [n_evals, B, D], cotangents [B, K, D],
@@ -1313,6 +1371,10 @@ def _launch_ode(p: PlanStruct, dev, tensors: dict, per_probe: Optional[torch.Ten
             rc = lib().ff_mlp_ode_launch_pull(ctypes.byref(p), ctypes.byref(a), _chk(pull[0], "cotangents", dev),
                                               _chk(pull[1], "cot_x_out", dev), _chk(pull[2], "cot_cond_out", dev),
                                               ctypes.c_void_p(stream))
+        elif push_select is not None:       # (push's pair, on a push-select plan)
+            what = "ff_mlp_ode_launch_push_select"
+            rc = lib().ff_mlp_ode_launch_push_select(ctypes.byref(p), ctypes.byref(a), _chk(push_select[0], "cond_tangents", dev),
+                                                     _chk(push_select[1], "tangent_out", dev), ctypes.c_void_p(stream))
         elif push is not None:
             what = "ff_mlp_ode_launch_push"
             rc = lib().ff_mlp_ode_launch_push(ctypes.byref(p), ctypes.byref(a), _chk(push[0], "cond_tangents", dev),
@@ -1460,6 +1522,59 @@ def mlp_ode_push(x: torch.Tensor, cond: Optional[torch.Tensor], tangents: Option
 
 
 @mlp_ode_push.register_fake
+def _(x, cond, tangents, cond_tangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, unit, tangent_first,
+      tangent_count):
+    return (torch.empty_like(x), x.new_empty(x.shape[0], int(tangent_count), x.shape[1]),
+            torch.empty(1, dtype=torch.int32, device=x.device))
+
+
+@torch.library.custom_op("flowfusion_amd::mlp_ode_push_select", mutates_args=())
+def mlp_ode_push_select(x: torch.Tensor, cond: Optional[torch.Tensor], tangents: Optional[torch.Tensor],
+                        cond_tangents: Optional[torch.Tensor], wpack: torch.Tensor, etab: torch.Tensor,
+                        in_shift: Optional[torch.Tensor], in_scale: Optional[torch.Tensor], out_scale: Optional[torch.Tensor],
+                        out_shift: Optional[torch.Tensor], plan: List[int], unit: bool, tangent_first: int,
+                        tangent_count: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fused push-forward through select rows (ff_mlp_ode_launch_push_select) over the rows ``etab`` of a leapfrog grid, from
+    the joint state ``x`` [B, 2D]: returns what ``mlp_ode_push`` returns -- (final state [B, 2D], tangent_out [B, K, 2D], status
+    [1]) -- with ``tangent_out[b, k] = d x_out[b] / d (x[b], cond[b]) . (v_k, c_k)``, the derivative of the discrete leapfrog.
+    ``unit`` / ``tangents`` / ``cond_tangents`` as there.  ``wpack``: the push-select plan's two forward packs
+    (``pack_push_select_weights``)."""
+    if not x.is_cuda:
+        raise RuntimeError("flowfusion_amd::mlp_ode_push_select needs tensors on the GPU (there is no CPU path)")
+    dev = x.device
+    p = _plan_from_words(plan)
+    if not is_push_select_plan(p):
+        raise RuntimeError("flowfusion_amd::mlp_ode_push_select needs a push-select plan")
+    B, D = x.shape
+    K = int(tangent_count)
+    if D != p.dim:
+        raise RuntimeError(f"state has {D} columns, plan was made for {p.dim}")
+    if K < 1:
+        raise RuntimeError(f"tangent_count={tangent_count}: at least one tangent per sample")
+    x_out = torch.empty_like(x)
+    t_out = torch.empty(B, K, D, dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B == 0:
+        return x_out, t_out, status
+    if cond is not None and tuple(cond.shape) != (B, p.cond_dim):
+        raise RuntimeError(f"cond has shape {tuple(cond.shape)}, expected {(B, p.cond_dim)}")
+    if unit and (tangents is not None or cond_tangents is not None):
+        raise RuntimeError("unit tangents take no tangent buffers")
+    if tangents is not None and tuple(tangents.shape) != (B, K, D):
+        raise RuntimeError(f"tangents has shape {tuple(tangents.shape)}, expected {(B, K, D)}")
+    if cond_tangents is not None and tuple(cond_tangents.shape) != (B, K, p.cond_dim):
+        raise RuntimeError(f"cond_tangents has shape {tuple(cond_tangents.shape)}, expected {(B, K, p.cond_dim)}")
+    if etab.shape[1] != 32 + row_width(p):
+        raise RuntimeError("evaluation table width does not match the plan")
+    _launch_ode(p, dev, {"x_in": x, "cond": cond, "probe": tangents, "wpack": wpack, "etab": etab,
+                         "in_shift": in_shift, "in_scale": in_scale, "out_scale": out_scale, "out_shift": out_shift},
+                push_select=(cond_tangents, t_out), x_out=x_out.data_ptr(), status=status.data_ptr(), batch=B,
+                n_evals=etab.shape[0], mode=MODE_EXACT if unit else MODE_HUTCH, tangent_first=tangent_first if unit else 0,
+                tangent_count=K, stage_slots=_slots_hint(plan))
+    return x_out, t_out, status
+
+
+@mlp_ode_push_select.register_fake
 def _(x, cond, tangents, cond_tangents, wpack, etab, in_shift, in_scale, out_scale, out_shift, plan, unit, tangent_first,
       tangent_count):
     return (torch.empty_like(x), x.new_empty(x.shape[0], int(tangent_count), x.shape[1]),

@@ -134,6 +134,18 @@ def _push_name(tile, h, d, c, wps, ring) -> str:
     return f"mlp_push_m{tile}_h{h}_d{d}_c{c}_w{wps}"
 
 
+# Row-select push-forward units (ff_mlp_pushsel.hpp; ff_mlp_push_select_plan): the push-forward row program on tables whose rows
+# choose between the two networks of a symplectic flow -- the derivative of a leapfrog, sample_leapfrog_jvp /
+# sample_leapfrog_jacobian.  One sibling per push-forward unit, same tile, registers, occupancy and ring; two forward packs in
+# the weight stream.  A family of its own (g_pushsel_kernels, FF_PUSH_SELECT_KERNEL_BASE); each wavefront owns its tile, as in
+# the push units, so there is no test-only skew variant.
+PUSH_SELECT_INSTANCES = list(PUSH_INSTANCES)
+
+
+def _pushsel_name(tile, h, d, c, wps, ring) -> str:
+    return _push_name(tile, h, d, c, wps, ring).replace("mlp_push_", "mlp_pushsel_", 1)
+
+
 # Pull-back units (ff_mlp_pull.hpp; ff_mlp_pull_plan): the continuous adjoint of a fixed-grid solve on cotangent columns --
 # flow_vjp.  (TILE, H, DREGS, CREGS, WPS, RING): the three push-forward shapes, SiLU, fp32.  ONE wavefront per workgroup (the
 # slope stash of a tile takes up to 32 KiB of LDS at 4 x 256, four tiles do not share 64 KiB), so WPS is 1 and the occupancy is
@@ -297,6 +309,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     PUSH_INSTANCES = push if push is not None else globals()["PUSH_INSTANCES"]
     PULL_INSTANCES = pull if pull is not None else globals()["PULL_INSTANCES"]
     PULL_SELECT = [] if pull is not None else globals()["PULL_SELECT_INSTANCES"]        # (the test variants carry none)
+    PUSH_SELECT = [] if push is not None else globals()["PUSH_SELECT_INSTANCES"]        # (nor of these)
     GEN.mkdir(parents=True, exist_ok=True)
     tf = lambda t: "true" if t else "false"
     # every launcher of the library: (name, header, kernel expression) -> a translation unit, a declaration, a table cell
@@ -340,7 +353,10 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     # the row-select pull-back siblings
     pullsels = [(_pullsel_name(*i), "ff_mlp_pullsel.hpp", f"mlp_pullsel_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[5]}>") for i in PULL_SELECT]
     files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 64, "ff_pullsel_registry.h")) for name, header, expr in pullsels]
-    units = units + pulls + vjps + dadjs + lgrads + pullsels
+    # the row-select push-forward siblings: four wavefronts per workgroup, as the push units
+    pushsels = [(_pushsel_name(*i), "ff_mlp_pushsel.hpp", f"mlp_pushsel_kernel<{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, {i[5]}>") for i in PUSH_SELECT]
+    files += [_write(GEN / f"{name}.hip", _launcher_unit(name, header, expr, 256, "ff_pushsel_registry.h")) for name, header, expr in pushsels]
+    units = units + pulls + vjps + dadjs + lgrads + pullsels + pushsels
     decls = "\n".join(f"int launch_{name}(const KernelArgs*, unsigned, unsigned, hipStream_t);" for name, _, _ in units)
     have = {name for name, _, _ in units}
     fn = lambda name: f"launch_{name}" if name in have else "nullptr"      # a table cell: the launcher, if the library has it
@@ -388,6 +404,9 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
     pullsel_rows = ",\n".join(
         f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pullsel_name(*i)}, "{_pullsel_name(*i)}"}}' for i in PULL_SELECT
     ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the row-select pull-back units)
+    pushsel_rows = ",\n".join(
+        f'    {{{i[0]}, {i[1]}, {i[2]}, {i[3]}, {i[4]}, launch_{_pushsel_name(*i)}, "{_pushsel_name(*i)}"}}' for i in PUSH_SELECT
+    ) or '    {0, 0, 0, 0, 0, nullptr, ""}'      # (nor the row-select push-forward units)
     table = f"""// generated by flowfusion_amd/build.py -- do not edit
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
@@ -395,6 +414,7 @@ def _gen_sources(gen: Path | None = None, instances=None, wide=None, split=None,
 #include "ff_dadj_registry.h"
 #include "ff_lgrad_registry.h"
 #include "ff_pullsel_registry.h"
+#include "ff_pushsel_registry.h"
 namespace ff {{
 {decls}
 const KernelEntry g_kernels[] = {{
@@ -437,6 +457,10 @@ const PullKernelEntry g_pullsel_kernels[] = {{
 {pullsel_rows}
 }};
 const int g_n_pullsel_kernels = {len(PULL_SELECT)};
+const PushKernelEntry g_pushsel_kernels[] = {{
+{pushsel_rows}
+}};
+const int g_n_pushsel_kernels = {len(PUSH_SELECT)};
 }}
 """
     files.append(_write(GEN / "ff_table.cpp", table))
@@ -465,7 +489,7 @@ def _cost(src: Path) -> float:
         return 95 if "_t1" in n else 55
     if "_h512_" in n:
         return 12 if "_coop" in n else (90 if "_t1" in n else 58)
-    if n.startswith("mlp_push_"):
+    if n.startswith("mlp_push_") or n.startswith("mlp_pushsel_"):
         return 16 if "_h256_" in n else 6
     if n.startswith("mlp_pullsel_") or n.startswith("mlp_pull_") or n.startswith("mlp_vjp_") or n.startswith("mlp_dadj_") or n.startswith("mlp_lgrad_"):
         return 40 if "_h256_" in n else 15

@@ -9,6 +9,7 @@
 #include "ff_registry.h"
 #include "ff_pull_registry.h"
 #include "ff_pullsel_registry.h"
+#include "ff_pushsel_registry.h"
 #include "ff_vjp_registry.h"
 #include "ff_dadj_registry.h"
 #include "ff_lgrad_registry.h"
@@ -162,7 +163,7 @@ extern "C" int ff_mlp_plan_prec(int dim, int cond_dim, int n_hidden, const int* 
 // ---- what a plan launches, as data ------------------------------------------------------------------------------------
 // describe() validates a plan once and says everything the code below needs to know about its family: the launcher,
 // ff_mlp_launch_kind and the small queries read the description and never ask which family they serve.
-enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush, kPull, kPullSel };
+enum PlanFamily { kF32 = 1, kSplit, kPair, kSelect, kPush, kPull, kPullSel, kPushSel };
 
 struct LaunchDesc {
     PlanFamily family;
@@ -195,6 +196,13 @@ extern const PullKernelEntry g_pullsel_kernels[] __attribute__((weak));
 extern const int g_n_pullsel_kernels __attribute__((weak));
 }
 static int n_pullsel_kernels() { return &ff::g_n_pullsel_kernels ? ff::g_n_pullsel_kernels : 0; }
+
+// The row-select push-forward table: weak for the same reason.
+namespace ff {
+extern const PushKernelEntry g_pushsel_kernels[] __attribute__((weak));
+extern const int g_n_pushsel_kernels __attribute__((weak));
+}
+static int n_pushsel_kernels() { return &ff::g_n_pushsel_kernels ? ff::g_n_pushsel_kernels : 0; }
 
 static bool shape_ok(const ff_mlp_plan_t* p, int tile, int H, int dregs, int cregs)
 {
@@ -239,6 +247,18 @@ static bool describe(const ff_mlp_plan_t* p, LaunchDesc* d)
         d->tangents = k.tangents; d->nets = 1; d->row_nets = 1;
         d->exchange = k.launch ? 2 : 1;
         d->max_aux = FF_MAX_AUX; d->takes_k1 = true; d->empty_batch_first = true;
+        return true;
+    }
+    if (p->kernel_id >= FF_PUSH_SELECT_KERNEL_BASE) {
+        // row-select push-forward units (ff_mlp_pushsel.hpp): the push units' geometry over a joint state [q | p]; the packed
+        // weights are two forward packs, a row of the table carries the c1 of the one network it runs
+        const int index = p->kernel_id - FF_PUSH_SELECT_KERNEL_BASE;
+        if (index >= n_pushsel_kernels()) return false;
+        const ff::PushKernelEntry& k = ff::g_pushsel_kernels[index];
+        if (!k.launch || !shape_ok(p, k.tile, k.H, k.dregs, k.cregs) || p->activation != FF_ACT_SILU || p->dim % 2 != 0) return false;
+        d->family = kPushSel; d->name = k.name; d->one_wave = k.launch;
+        twin_line(d, k.wps);
+        d->tangents = 1; d->nets = 2; d->row_nets = 1; d->exchange = 2;
         return true;
     }
     if (p->kernel_id >= FF_PULL_SELECT_KERNEL_BASE) {
@@ -348,7 +368,7 @@ namespace ff {
 bool plan_steps_adaptively(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
-    return describe(plan, &d) && d.family != kSelect && d.family != kPush && d.family != kPull && d.family != kPullSel;
+    return describe(plan, &d) && d.family != kSelect && d.family != kPush && d.family != kPull && d.family != kPullSel && d.family != kPushSel;
 }
 }
 
@@ -389,6 +409,39 @@ extern "C" int ff_mlp_push_plan(int dim, int cond_dim, int n_hidden, const int* 
     if (best < 0) return FF_ERR_UNSUPPORTED;
     const ff::PushKernelEntry& k = ff::g_push_kernels[best];
     return fill_plan(plan, dim, cond_dim, n_hidden, k.H, k.dregs, k.cregs, FF_PUSH_KERNEL_BASE + best, k.tile, FF_ACT_SILU);
+}
+
+extern "C" int ff_pushsel_kernel_count(void) { return n_pushsel_kernels(); }
+
+extern "C" const char* ff_pushsel_kernel_name(int index)
+{
+    return index >= 0 && index < n_pushsel_kernels() ? ff::g_pushsel_kernels[index].name : NULL;
+}
+
+// the push plan of the joint state (one envelope, one preference), carried over to the sibling unit
+extern "C" int ff_mlp_push_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan)
+{
+    if (!plan || !hidden_widths || dim < 2 || dim % 2 != 0 || cond_dim < 0 || n_hidden < 1) return FF_ERR_BADARG;
+    const int rc = ff_mlp_push_plan(dim, cond_dim, n_hidden, hidden_widths, FF_ACT_SILU, FF_PREC_F32, plan);
+    if (rc != FF_OK) return rc;
+    const ff::PushKernelEntry& k = ff::g_push_kernels[plan->kernel_id - FF_PUSH_KERNEL_BASE];
+    bool found = false;
+    for (int i = 0; i < n_pushsel_kernels() && !found; ++i) {
+        const ff::PushKernelEntry& s = ff::g_pushsel_kernels[i];
+        if (s.launch && s.tile == k.tile && s.H == k.H && s.dregs == k.dregs && s.cregs == k.cregs) {
+            plan->kernel_id = FF_PUSH_SELECT_KERNEL_BASE + i;
+            found = true;
+        }
+    }
+    if (!found) { memset(plan, 0, sizeof(*plan)); return FF_ERR_UNSUPPORTED; }
+    return FF_OK;
+}
+
+// two forward packs back to back: mlp_q's, then mlp_p's
+extern "C" size_t ff_mlp_push_select_wpack_floats(const ff_mlp_plan_t* plan)
+{
+    LaunchDesc d;
+    return describe(plan, &d) && d.family == kPushSel ? 2 * plan_layout(plan).total_floats : 0;
 }
 
 extern "C" int ff_pull_kernel_count(void) { return ff::g_n_pull_kernels; }
@@ -542,7 +595,7 @@ extern "C" int ff_mlp_pair_plan(int dim, int cond_dim, int n_hidden, const int* 
 extern "C" size_t ff_mlp_pair_wpack_floats(const ff_mlp_plan_t* plan)
 {
     LaunchDesc d;
-    return describe(plan, &d) && d.nets == 2 && d.family != kPullSel ? 2 * plan_layout(plan).total_floats : 0;
+    return describe(plan, &d) && d.nets == 2 && d.family != kPullSel && d.family != kPushSel ? 2 * plan_layout(plan).total_floats : 0;
 }
 
 extern "C" size_t ff_mlp_wpack_floats(const ff_mlp_plan_t* plan)
@@ -862,6 +915,20 @@ extern "C" int ff_mlp_pull_select_wpack(const ff_mlp_plan_t* plan, const float* 
     return rc;
 }
 
+// Push-select packing (ff_mlp_pushsel.hpp): two forward packs, each network embedded in the whole joint state [q | p] and packed
+// exactly as ff_mlp_pair_wpack embeds and packs it.
+static int pair_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq, const float* const* Wp,
+                      const float* const* bp, const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out);
+
+extern "C" int ff_mlp_push_select_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq,
+                                        const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
+                                        int x_col0, int c_col0, float* out)
+{
+    LaunchDesc d;
+    if (!describe(plan, &d) || d.family != kPushSel) return FF_ERR_BADARG;
+    return pair_wpack(plan, Wq, bq, Wp, bp, hidden_widths, in_features0, x_col0, c_col0, out);
+}
+
 // Pair packing: each reference network becomes an ordinary network over the whole state [q | p] (its first layer reads
 // its own half -- p for mlp_q, q for mlp_p -- and has zero columns on the other; its output layer writes its own half,
 // negated for mlp_p, and zero rows on the other), packed by wpack_f32; net A's pack, then net B's.
@@ -870,7 +937,15 @@ extern "C" int ff_mlp_pair_wpack(const ff_mlp_plan_t* plan, const float* const* 
                                  int x_col0, int c_col0, float* out)
 {
     LaunchDesc d;
-    if (!describe(plan, &d) || d.nets != 2 || d.family == kPullSel || !Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
+    if (!describe(plan, &d) || d.nets != 2 || d.family == kPullSel || d.family == kPushSel) return FF_ERR_BADARG;
+    return pair_wpack(plan, Wq, bq, Wp, bp, hidden_widths, in_features0, x_col0, c_col0, out);
+}
+
+// (the plan is one of two networks: the callers have looked)
+static int pair_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq, const float* const* Wp,
+                      const float* const* bp, const int* hidden_widths, int in_features0, int x_col0, int c_col0, float* out)
+{
+    if (!Wq || !bq || !Wp || !bp || !hidden_widths || !out) return FF_ERR_BADARG;
     const int D2 = plan->dim, Dh = D2 / 2, C = plan->cond_dim, H = plan->width, NH = plan->n_hidden;
     if (x_col0 < 0 || x_col0 + Dh > in_features0) return FF_ERR_BADARG;
     if (C > 0 && (c_col0 < 0 || c_col0 + C > in_features0)) return FF_ERR_BADARG;
@@ -1105,7 +1180,7 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
         if (t.cond) t.cond += row0 * C;
         if (t.probe) t.probe += row0 * D * (t.unit_tangents ? 1 : t.n_tangent);       // Hutchinson probes: [batch, n_tangent, dim]
         if (t.dlogp_probe_out) t.dlogp_probe_out += row0 * t.n_tangent;                // per-probe divergences: [batch, n_tangent]
-        if (d.family == kPush) {
+        if (d.family == kPush || d.family == kPushSel) {
             // (push plans have no twin today, so they never get here; a cooperative push unit would.  Their two pointers share
             // the places of dlogp_out and noise: ff_kernel_args.h)
             if (t.cond_tangent) t.cond_tangent += row0 * t.n_tangent * C;              // [batch, n_tangent, cond_dim]
@@ -1132,6 +1207,7 @@ static int enqueue(const LaunchDesc& d, const ff_mlp_plan_t* plan, ff::KernelArg
 struct PushIo {
     const float* cond_tangent;
     float* tangent_out;
+    bool select;               // ff_mlp_ode_launch_push_select: the plan must be a push-select plan, and only there may it be one
 };
 
 // What ff_mlp_ode_launch_pull adds to a launch (NULL: not a pull launch).
@@ -1172,7 +1248,7 @@ struct LgradIo {
     float* grad_cond_out;
 };
 
-// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push, ff_mlp_ode_launch_pull,
+// ff_mlp_ode_launch (probe_out == NULL), ff_mlp_ode_launch_probes, ff_mlp_ode_launch_push(_select), ff_mlp_ode_launch_pull(_select),
 // ff_mlp_ode_launch_vjp, ff_mlp_ode_launch_record, ff_mlp_ode_launch_pull_discrete and ff_mlp_ode_launch_logp_grad: one argument
 // check, one launch path
 static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* probe_out, void* hip_stream, const PushIo* push = nullptr,
@@ -1242,7 +1318,8 @@ static int launch_ode(const ff_mlp_plan_t* plan, const ff_ode_args* a, float* pr
         if (pull_lds_bytes(plan, a->tangent_count, ns) > kPullLdsLimit) return FF_ERR_UNSUPPORTED;      // the stash does not fit
     }
     if (push && d.family == kSplit) return FF_ERR_UNSUPPORTED;
-    if ((d.family == kPush) != (push != nullptr)) return FF_ERR_BADARG;      // push plans launch through their own entry, and only they
+    if ((d.family == kPush) != (push != nullptr && !push->select)) return FF_ERR_BADARG;      // push plans launch through their own entry, and only they
+    if ((d.family == kPushSel) != (push != nullptr && push->select)) return FF_ERR_BADARG;    // push-select plans through theirs, and only they
     if (push) {
         // whole fixed-grid solves of the state and its tangents: nothing of the divergence side, no attempt launches, no noise
         if (!push->tangent_out || a->mode == FF_MODE_STATE || a->tangent_count < 0) return FF_ERR_BADARG;
@@ -1338,7 +1415,14 @@ extern "C" int ff_mlp_ode_launch_probes(const ff_mlp_plan_t* plan, const ff_ode_
 extern "C" int ff_mlp_ode_launch_push(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* cond_tangent, float* tangent_out,
                                       void* hip_stream)
 {
-    const PushIo io = {cond_tangent, tangent_out};
+    const PushIo io = {cond_tangent, tangent_out, false};
+    return launch_ode(plan, a, nullptr, hip_stream, &io);
+}
+
+extern "C" int ff_mlp_ode_launch_push_select(const ff_mlp_plan_t* plan, const ff_ode_args* a, const float* cond_tangent, float* tangent_out,
+                                             void* hip_stream)
+{
+    const PushIo io = {cond_tangent, tangent_out, true};
     return launch_ode(plan, a, nullptr, hip_stream, &io);
 }
 

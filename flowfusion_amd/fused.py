@@ -600,15 +600,60 @@ class FusedPair(FusedNet):
             _native.plan_words(plan, stage_slots), want)
         return y, gz, (gc if want else None), status
 
+    def push_select_plan(self) -> _native.PlanStruct:
+        """The row-select push-forward unit of this pair (ff_mlp_push_select_plan); NotImplementedError with the envelope if
+        none holds it."""
+        if "push_select" not in self._plans:
+            self._plans["push_select"] = _native.make_push_select_plan(self.dim, self.cond_dim, self.hidden)
+        return self._plans["push_select"]
+
+    def pushforward_select(self, z: torch.Tensor, etab: torch.Tensor, tangents: Optional[torch.Tensor] = None,
+                           cond: Optional[torch.Tensor] = None, cond_tangents: Optional[torch.Tensor] = None,
+                           unit: Optional[Tuple[int, int]] = None, stage_slots: int = 1, in_shift=None, in_scale=None,
+                           out_scale=None, out_shift=None):
+        """K tangents per sample pushed through select rows, on the row-select push-forward unit (``push_select_plan``):
+        ``etab`` has ITS width (``width(MODE_STATE, push_select=True)``) and holds the rows of a leapfrog grid.  Returns
+        (z_out [B, 2D], dz [B, K, 2D], status [1]): ``z_out`` the state ``integrate_select`` gives on the same rows,
+        ``dz[b, k] = d z_out[b] / d (z[b], cond[b]) . (tangents[b, k], cond_tangents[b, k])``, the exact derivative of the
+        discrete leapfrog (either part may be None = zero), or with ``unit = (first, count)`` its columns for the unit vectors
+        ``first .. first + count - 1`` of the combined space [0, 2D + C).  The affine maps act on tangents by their linear
+        parts, as ``pushforward``'s do; ``cond`` and ``cond_tangents`` are taken as given."""
+        if not z.is_cuda:
+            raise RuntimeError(
+                "flowfusion_amd integrates on the GPU only: move the model and its inputs to 'cuda' "
+                f"(got a tensor on {z.device}); there is no CPU fallback")
+        if z.dim() != 2 or z.shape[1] != self.dim:
+            raise ValueError(f"expected a [batch, {self.dim}] state, got {tuple(z.shape)}")
+        dev = z.device
+        plan = self.push_select_plan()
+        cond = self._pull_cond(cond, z.shape[0], dev)
+        if unit is not None:
+            first, K = int(unit[0]), int(unit[1])
+            tangents = cond_tangents = None
+        else:
+            first = 0
+            given = tangents if tangents is not None else cond_tangents
+            if given is None or given.dim() != 3:
+                raise ValueError("pushforward_select: tangents [batch, K, dim] and / or cond_tangents [batch, K, cond_dim], or "
+                                 "unit=(first, count)")
+            K = int(given.shape[1])
+        return torch.ops.flowfusion_amd.mlp_ode_push_select(
+            f32_on(z, dev), cond, f32_on(tangents, dev), f32_on(cond_tangents, dev), self.wpack(dev, MODE_STATE, plan),
+            f32_on(etab, dev), f32_on(in_shift, dev), f32_on(in_scale, dev), f32_on(out_scale, dev), f32_on(out_shift, dev),
+            _native.plan_words(plan, stage_slots), unit is not None, first, K)
+
     def _param_key(self, device, plan) -> Tuple:
         vers = tuple((p.data_ptr(), p._version) for l in self.linears + self.p_linears for p in (l.weight, l.bias))
-        # (a pull-select plan's buffer holds two pull packs: a key of its own)
+        # (a pull-select plan's buffer holds two pull packs, a push-select plan's two forward packs of ITS unit: keys of their own)
         return (str(device), plan.tile, plan.width, plan.dregs, plan.cregs, plan.n_hidden) + \
-            (("pull_select",) if _native.is_pull_select_plan(plan) else ()), vers
+            (("pull_select",) if _native.is_pull_select_plan(plan) else ()) + \
+            (("push_select",) if _native.is_push_select_plan(plan) else ()), vers
 
     def _pack(self, plan) -> torch.Tensor:
         if _native.is_pull_select_plan(plan):
             return _native.pack_pull_select_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
+        if _native.is_push_select_plan(plan):
+            return _native.pack_push_select_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
         return _native.pack_pair_weights(plan, self.linears, self.p_linears, self.hidden, self.x_col0, self.c_col0)
 
     def cached_table(self, key, device, build):
@@ -640,11 +685,14 @@ class FusedPair(FusedNet):
             self._time_cols = hit
         return hit[1], hit[2]
 
-    def width(self, mode: int = MODE_STATE, select: bool = False, pull_select: bool = False) -> int:
+    def width(self, mode: int = MODE_STATE, select: bool = False, pull_select: bool = False, push_select: bool = False) -> int:
         """First-layer bias words per evaluation row: two networks' worth; one network's on the select plan; one network's of
-        the pull-select plan's width with ``pull_select=True`` (its unit may be wider than the pair plan's)."""
+        the pull-select / push-select plan's width with ``pull_select=True`` / ``push_select=True`` (their units may be wider
+        than the pair plan's)."""
         if pull_select:
             return int(self.pull_select_plan().width)
+        if push_select:
+            return int(self.push_select_plan().width)
         return (1 if select else 2) * int(self.plan(mode).width)
 
     def stage_slots(self, mode: int = MODE_STATE) -> int:

@@ -803,6 +803,132 @@ def _solve_leapfrog_pull(front, z, grid, cotangents, cond, return_retrace, num_c
     return zo, gz, gc, (zb - z).abs().amax(dim=1)
 
 
+def _leapfrog_push_checks(front, z, tangents, cond, cond_tangents, unit):
+    """What ``solve_leapfrog_push`` refuses before the device is touched, in ``_leapfrog_pull_checks``' style and order:
+    shapes, the tangents and K, dtypes, CPU tensors, the envelope, the conditional against the model.  Returns
+    ``(net, B, D2, K, C)``."""
+    what = "leapfrog push-forwards"
+    if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] % 2 != 0 or z.shape[1] < 2:
+        raise ValueError(f"{what}: z must be a [batch, 2 dim] tensor, the joint state [q | p]")
+    B, D2 = int(z.shape[0]), int(z.shape[1])
+    shape_of = lambda t: tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+    if cond is not None and (not torch.is_tensor(cond) or cond.dim() != 2 or cond.shape[0] != B):
+        raise ValueError(f"{what}: conditional must be [{B}, cond_dim], got {shape_of(cond)}")
+    if tangents is not None and (not torch.is_tensor(tangents) or tangents.dim() != 3 or tuple(tangents.shape[::2]) != (B, D2)):
+        raise ValueError(f"{what}: tangents must be [{B}, K >= 1, {D2}], got {shape_of(tangents)}")
+    if cond_tangents is not None and (not torch.is_tensor(cond_tangents) or cond_tangents.dim() != 3 or cond is None or
+                                      tuple(cond_tangents.shape[::2]) != (B, int(cond.shape[1]))):
+        raise ValueError(f"{what}: conditional_tangents must be [{B}, K >= 1, cond_dim] beside a conditional, got "
+                         f"{shape_of(cond_tangents)}")
+    if tangents is not None and cond_tangents is not None and tangents.shape[1] != cond_tangents.shape[1]:
+        raise ValueError(f"{what}: tangents and conditional_tangents hold {tangents.shape[1]} and {cond_tangents.shape[1]} "
+                         "tangents per sample")
+    if unit is not None:
+        if tangents is not None or cond_tangents is not None:
+            raise ValueError(f"{what}: unit tangents take no tangent tensors")
+        first, K = int(unit[0]), int(unit[1])
+        span = D2 + (0 if cond is None else int(cond.shape[1]))
+        if first < 0 or K < 1 or first + K > span:
+            raise ValueError(f"{what}: unit tangents [{first}, {first + K}) outside [0, {span})")
+    else:
+        if tangents is None and cond_tangents is None:
+            raise ValueError(f"{what}: tangents [batch, K, 2 dim] and / or conditional_tangents [batch, K, cond_dim]")
+        K = int((tangents if tangents is not None else cond_tangents).shape[1])
+        if K < 1:
+            raise ValueError(f"{what}: at least one tangent per sample")
+    if K > _native.MAX_PUSH_TANGENTS:
+        raise ValueError(f"{what}: K={K} tangents per sample; a sample and its tangents share the 16 columns "
+                         f"of one tile, so at most {_native.MAX_PUSH_TANGENTS} per call")
+    require_fp32(front, z, cond, tangents, cond_tangents, what="a leapfrog push-forward solve")
+    _need_gpu(z)
+    try:
+        if not front._fusable():
+            raise NotImplementedError("the model's two networks are outside the compiled two-network shapes (or not a SymplecticMLP "
+                                      "with SiLU)")
+        net = front._net()
+        net.push_select_plan()
+    except NotImplementedError as e:
+        msg = str(e)
+        raise NotImplementedError(msg if _native.PUSH_SELECT_ENVELOPE in msg else
+                                  f"{msg} -- {_native.PUSH_SELECT_ENVELOPE}; there is no module-path fallback") from None
+    if D2 != net.dim:
+        raise ValueError(f"{what}: z has {D2} columns, the model's joint state has {net.dim}")
+    C = net.cond_dim
+    if C > 0 and (cond is None or tuple(cond.shape) != (B, C)):
+        raise ValueError(f"{what}: conditional must be [{B}, {C}], got {None if cond is None else tuple(cond.shape)}")
+    if C == 0 and cond is not None:
+        raise ValueError(f"{what}: this model has no conditional inputs")
+    return net, B, D2, K, C
+
+
+def solve_leapfrog_push(front, z, grid, tangents=None, cond=None, cond_tangents=None, unit=None):
+    """Leapfrog push-forwards (extension): K tangents per sample pushed through ``solve_leapfrog(front, z, grid, cond)``,
+    exactly.  Returns ``(z_out [B, 2D], dz [B, K, 2D])`` with ``dz[b, k] = d z_out[b] / d (z[b], cond[b]) . (tangents[b, k],
+    cond_tangents[b, k])`` -- forward mode through the SAME shears, so the derivative of the discrete leapfrog map on ANY
+    leapfrog grid: ``linspace(1, 0, n + 1)`` is the sampler's direction, its flip the log-density's.  ``tangents``
+    [B, K, 2D] / ``cond_tangents`` [B, K, C]: either may be None (zero); ``unit = (first, count)`` instead of both: the unit
+    vectors ``first .. first + count - 1`` of the combined space [0, 2D + C).  ``cond`` and ``cond_tangents`` are the
+    networks' (normalised) conditional inputs.
+
+    A leapfrog row is a shear ``q' = q + w f(p, c, t)``, ``p' = p`` (or the kick, its mirror image); its forward-mode form
+    is ``dq' = dq + w (J_f(p) dp + df/dc dc)``, ``dp' = dp``.  ONE launch of the row-select push-forward unit per piece of rows
+    (``FusedPair.pushforward_select``) on the table of ``solvers.plan_leapfrog(grid)`` at that unit's row width: the K
+    tangents of a sample ride in K columns of its tile beside its value column, K <= 15, and nothing is stashed, so there is
+    no depth ceiling.  ``z_out`` is bitwise ``solve_leapfrog``'s: the value column runs the row-select kernel's FMA chains
+    wherever that kernel works on the 16-column tile; for the networks it serves on its 32-column tile (hidden widths up to
+    64) ``z_out`` comes from a ``solve_leapfrog`` launch of its own.  Rows are cut by ``solve_push``'s rule (a [rows, K, 2D]
+    buffer stays under ``PROBE_BUFFER_FLOATS`` floats); rows are independent, so any cut gives bitwise the same.
+
+    Refused before the device is touched: shapes that do not match, no tangents at all and K > 15 (ValueError), non-fp32
+    tensors (TypeError), CPU tensors (RuntimeError), a model outside ``_native.PUSH_SELECT_ENVELOPE`` or not on the fused
+    route (NotImplementedError: there is no module-path fallback).  Out of scope: parameter gradients and torch.autograd
+    integration, Euler and dopri5 solves, twins, sharded entry points (rows are independent: slice)."""
+    return _solve_leapfrog_push(front, z, grid, tangents, cond, cond_tangents, unit, None)
+
+
+def _solve_leapfrog_push(front, z, grid, tangents, cond, cond_tangents, unit, cond_tangent_scale):
+    """``solve_leapfrog_push`` for a front end that normalised ``cond`` on the host: after the checks, ``cond_tangents /
+    cond_tangent_scale`` (a tensor or None), as ``solve_push`` does."""
+    net, B, D2, K, C = _leapfrog_push_checks(front, z, tangents, cond, cond_tangents, unit)
+    if cond_tangent_scale is not None and cond_tangents is not None:
+        cond_tangents = cond_tangents / cond_tangent_scale
+    grid = torch.as_tensor(grid).detach().to("cpu", torch.float32).reshape(-1)
+    key = ("leapfrog_push", tuple(float(v) for v in grid)) + front._schedule_key()
+    table = net.cached_table(key, z.device, lambda: front._leapfrog_table(grid, push_select=True))
+    own_state = int(net.plan(MODE_STATE, select=True).tile) == int(net.push_select_plan().tile)
+    rows = max(1, (PROBE_BUFFER_FLOATS - 1) // (K * D2))
+    pieces = [(r0, min(B, r0 + rows)) for r0 in range(0, B, rows)] or [(0, 0)]
+    whole = len(pieces) == 1
+    cut = lambda t, r0, r1: t if (whole or t is None) else t[r0:r1]
+    outs, dzs = [], []
+    for r0, r1 in pieces:
+        zo, dz, _ = net.pushforward_select(cut(z, r0, r1), table, tangents=cut(tangents, r0, r1), cond=cut(cond, r0, r1),
+                                           cond_tangents=cut(cond_tangents, r0, r1),
+                                           unit=None if unit is None else (int(unit[0]), K), stage_slots=1)
+        if not own_state:
+            zo = solve_leapfrog(front, cut(z, r0, r1), grid, cond=cut(cond, r0, r1))
+        outs.append(zo)
+        dzs.append(dz)
+    front.last_solver_stats = {"evaluations": int(table.shape[0]), "launches": (1 if own_state else 2) * len(pieces)}
+    return (outs[0], dzs[0]) if whole else (torch.cat(outs), torch.cat(dzs))
+
+
+def solve_leapfrog_push_jacobian(front, z, grid, cond=None):
+    """The whole Jacobian of the leapfrog map from ``solve_leapfrog_push`` with unit tangents: ``(z_out [B, 2D], J_z
+    [B, 2D, 2D], J_c [B, 2D, C] or None)``, ``J_z[b, i, j] = d z_out_i / d z_j``, ``J_c[b, i, j] = d z_out_i / d cond_j``, in
+    ceil((2D + C) / 15) launches per piece of rows; ``z_out`` is the first launch's (every launch computes the same one, bit
+    for bit)."""
+    D2 = int(z.shape[1]) if torch.is_tensor(z) and z.dim() == 2 else 0
+    C = 0 if cond is None or not torch.is_tensor(cond) or cond.dim() != 2 else int(cond.shape[1])
+    zo, cols = None, []
+    for first in range(0, max(D2 + C, 1), _native.MAX_PUSH_TANGENTS):
+        zk, dz = solve_leapfrog_push(front, z, grid, cond=cond, unit=(first, min(_native.MAX_PUSH_TANGENTS, D2 + C - first)))
+        zo = zk if zo is None else zo
+        cols.append(dz)
+    J = torch.cat(cols, dim=1).transpose(1, 2).contiguous()          # [B, 2D, 2D + C]: column j = the derivative along unit j
+    return zo, J[:, :, :D2].contiguous(), (J[:, :, D2:].contiguous() if C > 0 else None)
+
+
 # ---- extension: the log-density of noisy observations over K noise draws (the front ends' ``log_prob_noisy``) -----------
 OBSERVE_CHUNK_ROWS = 1 << 22        # rows (data points x noise draws) in flight by default on a fixed grid
 

@@ -222,6 +222,58 @@ class SymplecticFlowModel(nn.Module):
             res += (gz[:, D:] + momentum,)
         return res + tuple(out[3:])
 
+    # -- extensions: forward-mode derivatives through the leapfrog (odeint.solve_leapfrog_push).  Methods of their own again:
+    # flow_jvp / flow_jacobian above keep raising ------------------------------------------------------------------------------
+    def _leapfrog_push_front_checks(self, name, z, conditional, num_steps, tangents=None, conditional_tangents=None, unit=None):
+        """What both push-forward methods refuse, in one order, before anything is computed: ``num_steps``, the prior draw's
+        shape, then everything ``odeint.solve_leapfrog_push`` refuses (the raw conditional has the normalised one's shape and
+        dtype, so the checks see it as it is; the launch re-checks the normalised tensors).  Returns D."""
+        if int(num_steps) < 1:
+            raise ValueError(f"num_steps={num_steps}: {name} differentiates at least one leapfrog step")
+        if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] % 2 != 0 or z.shape[1] < 2:
+            raise ValueError(f"{name}: z must be the prior draw [batch, 2 dim]")
+        odeint._leapfrog_push_checks(self, z, tangents, conditional, conditional_tangents, unit)
+        return int(z.shape[1]) // 2
+
+    @torch.no_grad()
+    def sample_leapfrog_jvp(self, z, tangents=None, conditional=None, conditional_tangents=None, num_steps=1):
+        """K tangents per sample pushed through ``sample_leapfrog``'s map, exactly (forward mode through the discrete
+        leapfrog): the sensitivity of a sample to its prior draw and to the raw ``conditional`` (the population
+        hyper-parameters) -- what a Fisher forecast or a delta-method error bar asks of this model class.
+
+        ``z`` [B, 2D] is the prior draw (the ``x`` of ``_sample_from``); ``tangents`` [B, K, 2D] are in its units,
+        ``conditional_tangents`` [B, K, C] in the units of the raw ``conditional`` (divided by ``conditional_scale`` on the
+        way in); either may be None (zero), K <= 15.  Returns ``(x [B, D], dx [B, K, D])``: ``x`` is bitwise
+        ``_sample_from(z, conditional, num_steps, method="leapfrog")``, ``dx[b, k] = dx / d(z, conditional) . (tangents[b, k],
+        conditional_tangents[b, k])`` in the units of the sample (``dq * scale``).  One launch per piece of rows; fused route
+        only (``_native.PUSH_SELECT_ENVELOPE``), no module-path fallback, no depth ceiling."""
+        D = self._leapfrog_push_front_checks("sample_leapfrog_jvp", z, conditional, num_steps, tangents, conditional_tangents)
+        cond = self._norm_cond(conditional)
+        grid = torch.linspace(1.0, 0.0, int(num_steps) + 1, device=z.device).cpu()      # (built as _sample_from builds it)
+        zo, dz = odeint._solve_leapfrog_push(self, z, grid, tangents, cond, conditional_tangents, None, self.conditional_scale)
+        q, _ = torch.chunk(zo, 2, dim=-1)
+        return q * self.scale + self.shift, dz[:, :, :D] * self.scale
+
+    @torch.no_grad()
+    def sample_leapfrog_jacobian(self, z, conditional=None, num_steps=1):
+        """The whole Jacobian of ``sample_leapfrog``'s map: ``(x [B, D], J_z [B, D, 2D], J_c [B, D, C] or None)``,
+        ``J_z[b, i, j] = dx_i / dz_j`` and ``J_c[b, i, j] = dx_i / d conditional_j`` for the raw ``conditional``, from unit
+        tangents in ceil((2D + C) / 15) launches per piece of rows (``sample_leapfrog_vjp`` needs D cotangents for the same:
+        see README for which route to use when).  ``x`` is bitwise ``_sample_from(z, conditional, num_steps,
+        method="leapfrog")``."""
+        D = self._leapfrog_push_front_checks("sample_leapfrog_jacobian", z, conditional, num_steps, unit=(0, 1))
+        cond = self._norm_cond(conditional)
+        grid = torch.linspace(1.0, 0.0, int(num_steps) + 1, device=z.device).cpu()
+        zo, Jz, Jc = odeint.solve_leapfrog_push_jacobian(self, z, grid, cond=cond)
+        q, _ = torch.chunk(zo, 2, dim=-1)
+        scale = self.scale if self.scale.dim() == 0 else self.scale[:, None]
+        Jz = Jz[:, :D] * scale
+        if Jc is not None:
+            Jc = Jc[:, :D] * scale
+            if self.conditional_scale is not None:
+                Jc = Jc / self.conditional_scale
+        return q * self.scale + self.shift, Jz, Jc
+
     # -- with the random draws supplied (tests feed the reference's draws) ----------------------------
     def _norm_cond(self, conditional):
         if conditional is None:
@@ -524,17 +576,19 @@ class SymplecticFlowModel(nn.Module):
         a, b, c1 = self._schedule(plan.t_eval)
         return solvers.build_table(plan, a, b, c1, self._net().width(mode))
 
-    def _leapfrog_table(self, grid, pull_select=False):
+    def _leapfrog_table(self, grid, pull_select=False, push_select=False):
         """The select plan's table of ``solvers.plan_leapfrog(grid)``: every row carries the c1 of the network it runs.
-        ``pull_select``: the same rows at the row width of the pull-select plan (its unit may be wider than the pair plan's)."""
+        ``pull_select`` / ``push_select``: the same rows at the row width of the pull-select / push-select plan (their units may
+        be wider than the pair plan's)."""
         plan = solvers.plan_leapfrog(grid)
         a, b, c1 = self._schedule(plan.t_eval)
         H = self._net().width(MODE_STATE, select=True)
         net_b = (plan.flags & solvers.FLAG_NET_B) != 0
         own = torch.where(net_b[:, None], c1[:, H:], c1[:, :H])
-        if pull_select:
+        if pull_select or push_select:
             h0 = self._net().hidden[0]
-            return solvers.build_table(plan, a, b, own[:, :h0], self._net().width(MODE_STATE, pull_select=True))
+            return solvers.build_table(plan, a, b, own[:, :h0],
+                                       self._net().width(MODE_STATE, pull_select=pull_select, push_select=push_select))
         return solvers.build_table(plan, a, b, own, H)
 
     def _schedule_key(self):

@@ -597,6 +597,45 @@ int ff_mlp_ode_launch_pull_select(const ff_mlp_plan_t* plan, const ff_ode_args* 
                                   float* cot_x_out /* [batch, K, dim] */, float* cot_cond_out /* [batch, K, cond_dim] or NULL */,
                                   void* hip_stream);
 
+/* ---- row-select push-forwards: the derivative of a leapfrog of the symplectic flows (csrc/ff_mlp_pushsel.hpp) ------------
+ * The forward-mode form of a leapfrog row (a shear of [q | p]) is
+ *     dq' = dq + w (J_f(p) dp + df/dcond dcond),   dp' = dp          (or the kick, its mirror image),
+ * which is the stage algebra of ff_mlp_ode_launch_push on a select row (a_e = 0): K tangent columns beside every value column
+ * run through the row's network, and the select pack's structural zeros leave the other half of every tangent bitwise alone.
+ * One launch over the rows of solvers.plan_leapfrog(grid) returns the state of ff_mlp_pair_select_plan's launch on the same
+ * rows (bit for bit at hidden widths 128 and 256) and tangent_out = d x_out / d (x_in, cond) . tangent, the derivative of the
+ * discrete map -- on the forward grid the sampler's, on the flipped grid the log-density direction's.  One sibling per
+ * push-forward unit (kernel names mlp_pushsel_...), same tile, registers, occupancy and ring; a row runs mlp_p's pack if its
+ * flag word has FF_ROW_NET_B, mlp_q's otherwise, and carries only that network's c1 (row stride FF_ROW_HDR + plan.width;
+ * ff_mlp_row_width = plan.width).  Rows may select in any order.
+ *
+ * ff_mlp_push_select_plan(dim, cond_dim, n_hidden, hidden_widths, plan_out): `dim` is the joint 2D and must be even
+ * (FF_ERR_BADARG); the envelope and preference are ff_mlp_push_plan's for that dim -- SiLU, fp32, hidden width <= 128 with
+ * dim <= 16, width <= 256 with dim <= 16 or dim <= 32; cond_dim <= 16 -- else FF_ERR_UNSUPPORTED.  The plan's kernel_id is
+ * FF_PUSH_SELECT_KERNEL_BASE + an index (not entries of ff_kernel_count or ff_push_kernel_count).  ff_plan_kernel_name,
+ * ff_mlp_row_width and ff_mlp_samples_per_workgroup accept the plan; every other launch and packer refuses it with
+ * FF_ERR_BADARG (ff_mlp_wpack_floats, ff_mlp_pair_wpack_floats and the pull packers' sizes return 0).
+ *
+ * ff_mlp_push_select_wpack takes the arguments of ff_mlp_pair_wpack and writes ff_mlp_push_select_wpack_floats(plan) floats:
+ * two forward packs back to back, each what ff_mlp_wpack makes of that network embedded in the joint state as
+ * ff_mlp_pair_wpack embeds it (mlp_q: columns on the p half, rows 0..D-1; mlp_p: columns on the q half, rows D..2D-1, output
+ * weights and bias negated).
+ *
+ * ff_mlp_ode_launch_push_select: the arguments, modes (FF_MODE_HUTCH: tangents as given in args->probe [batch, K, dim] and
+ * cond_tangent [batch, K, cond_dim], NULL = zero; FF_MODE_EXACT: the unit vectors tangent_first .. + tangent_count - 1 of
+ * [0, dim + cond_dim)), refusals and status bits of ff_mlp_ode_launch_push; it refuses every plan that is not a push-select
+ * plan (FF_ERR_BADARG), as ff_mlp_ode_launch_push refuses this one. */
+#define FF_PUSH_SELECT_KERNEL_BASE 0xB0000
+int ff_pushsel_kernel_count(void);
+const char* ff_pushsel_kernel_name(int index);
+int ff_mlp_push_select_plan(int dim, int cond_dim, int n_hidden, const int* hidden_widths, ff_mlp_plan_t* plan_out);
+size_t ff_mlp_push_select_wpack_floats(const ff_mlp_plan_t* plan);
+int ff_mlp_push_select_wpack(const ff_mlp_plan_t* plan, const float* const* Wq, const float* const* bq,
+                             const float* const* Wp, const float* const* bp, const int* hidden_widths, int in_features0,
+                             int x_col0, int c_col0, float* out);
+int ff_mlp_ode_launch_push_select(const ff_mlp_plan_t* plan, const ff_ode_args* args, const float* cond_tangent /* [batch, K, cond_dim] or NULL */,
+                                  float* tangent_out /* [batch, K, dim] */, void* hip_stream);
+
 /* ---- streaming helpers beside the fused integrator (csrc/ff_aux.hip) --------------------------------- */
 
 /* Noise index reserved for the prior draw of a sample in the counter-based stream (never used by the
