@@ -386,6 +386,16 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_observe_grad_reduce.restype = L.ff_observe_grad_reduce_host.restype = ctypes.c_int
     L.ff_observe_keep.argtypes, L.ff_observe_keep_host.argtypes = obs_keep + [ctypes.c_void_p], obs_keep
     L.ff_observe_grad_reduce.argtypes, L.ff_observe_grad_reduce_host.argtypes = grad_reduce + [ctypes.c_void_p], grad_reduce
+    mobs_expand = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 3 + \
+                  [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64,
+                   ctypes.c_void_p, ctypes.c_void_p]
+    mobs_grad = [ctypes.c_void_p] * 7 + [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.ff_marginal_observe_expand.restype = L.ff_marginal_observe_expand_host.restype = ctypes.c_int
+    L.ff_marginal_observe_grad_reduce.restype = L.ff_marginal_observe_grad_reduce_host.restype = ctypes.c_int
+    L.ff_marginal_observe_expand.argtypes, L.ff_marginal_observe_expand_host.argtypes = mobs_expand + [ctypes.c_void_p], mobs_expand
+    L.ff_marginal_observe_grad_reduce.argtypes, L.ff_marginal_observe_grad_reduce_host.argtypes = \
+        mobs_grad + [ctypes.c_void_p], mobs_grad
     L.ff_mlp_ode_adaptive.restype = ctypes.c_int
     L.ff_mlp_ode_adaptive.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.POINTER(AdaptConfig),
                                       ctypes.POINTER(AdaptBuffers), ctypes.c_double, ctypes.c_double, ctypes.c_int32,
@@ -1105,6 +1115,114 @@ def observe_grad_reduce(lp: torch.Tensor, row_of: torch.Tensor, gx_rows: torch.T
                      int(sample_offset), ptrs[4], ptrs[5], ptrs[6]))
     if rc != FF_OK:
         raise _err(rc, "ff_observe_grad_reduce")
+    return grad_x, grad_c, grad_noise_std
+
+
+def _std_stride(noise_std: torch.Tensor, B: int, D: int, what: str) -> int:
+    """std_row_stride of a ``noise_std`` [D] (0) or [B, D] (D)."""
+    if tuple(noise_std.shape) == (D,):
+        return 0
+    if tuple(noise_std.shape) == (B, D):
+        return D
+    raise RuntimeError(f"{what}: noise_std has shape {tuple(noise_std.shape)}, expected [{D}] or [{B}, {D}]")
+
+
+def marginal_observe_expand(x: torch.Tensor, noise_std: torch.Tensor, num_draws: int, seed: int, sample_offset: int = 0,
+                            shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                            cond: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """ff_marginal_observe_expand: (z0 [B K, 2 D], cond_out [B K, C] or None) from ``x`` [B, D]: row r K + k is
+    [((x[r] - noise_std[r] * z_k) - shift) / scale | momentum k] and the (already normalised) ``cond[r]``, noise draw k and
+    momentum k both of global row sample_offset + r (noise indices OBS_NOISE_BASE + k and MOMENTUM_NOISE_BASE + k).
+    ``noise_std``: [D] (one vector for every row) or [B, D].  Device tensors on the current stream; CPU tensors go to
+    ff_marginal_observe_expand_host."""
+    dev = x.device
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise RuntimeError(f"marginal_observe_expand: x has shape {tuple(x.shape)}, expected [B, D >= 1]")
+    B, D = x.shape
+    K = int(num_draws)
+    if not 1 <= K <= min(MAX_MOMENTA, MAX_OBS_DRAWS):
+        raise ValueError(f"num_draws={num_draws}: 1 .. {min(MAX_MOMENTA, MAX_OBS_DRAWS)} joint draws per data point")
+    stride = _std_stride(noise_std, B, D, "marginal_observe_expand")
+    for t, name in ((shift, "shift"), (scale, "scale")):
+        if t is not None and t.numel() != D:
+            raise RuntimeError(f"marginal_observe_expand: {name} has {t.numel()} elements, x has {D} columns")
+    if cond is not None and (cond.dim() != 2 or cond.shape[0] != B or cond.shape[1] < 1):
+        raise RuntimeError(f"marginal_observe_expand: cond has shape {tuple(cond.shape)}, expected [{B}, C >= 1]")
+    C = 0 if cond is None else int(cond.shape[1])
+    z0 = torch.empty(B * K, 2 * D, dtype=torch.float32, device=dev)
+    cond_out = None if cond is None else torch.empty(B * K, C, dtype=torch.float32, device=dev)
+    ptrs = (_chk(x, "x", dev), _chk(noise_std, "noise_std", dev), _chk(shift, "shift", dev), _chk(scale, "scale", dev),
+            _chk(cond, "cond", dev))
+    if B == 0:
+        return z0, cond_out
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_observe_expand, L.ff_marginal_observe_expand_host,
+                    (ptrs[0], ptrs[1], stride, ptrs[2], ptrs[3], ptrs[4], B, D, C, K, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                     int(sample_offset), z0.data_ptr(), 0 if cond is None else cond_out.data_ptr()))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_observe_expand")
+    return z0, cond_out
+
+
+def marginal_observe_grad_reduce(lw: torch.Tensor, row_of: torch.Tensor, gz_rows: torch.Tensor, gc_rows: Optional[torch.Tensor],
+                                 noise_std: torch.Tensor, num_draws: int, seed: int, sample_offset: int = 0,
+                                 scale: Optional[torch.Tensor] = None, cond_scale: Optional[torch.Tensor] = None,
+                                 want_noise_grad: bool = True, grad_x: Optional[torch.Tensor] = None,
+                                 grad_c: Optional[torch.Tensor] = None, grad_noise_std: Optional[torch.Tensor] = None):
+    """ff_marginal_observe_grad_reduce: ``(grad_x [B, D], grad_c [B, C] or None, grad_noise_std [B, D] or None)``:
+    ``grad_x`` and ``grad_c`` bit for bit what ``marginal_grad_reduce`` writes for the same ``lw`` [B K] float64, ``row_of``
+    [B K] int32, ``gz_rows`` [n, 2 D], ``gc_rows`` [n, C], ``scale`` and ``cond_scale``, and ``grad_noise_std = -sum_k wn_k z_k
+    gz_rows[row_of[r K + k]][:D] / scale`` with the noise draws regenerated from ``seed`` and global row ``sample_offset + r``.
+    ``noise_std`` [D] or [B, D] as ``marginal_observe_expand`` took it (its values are not read).  ``row_of`` is checked here
+    to stay below n.  The outputs are allocated where not given.  Device tensors on the current stream; CPU tensors go to
+    ff_marginal_observe_grad_reduce_host."""
+    dev = lw.device
+    K = int(num_draws)
+    what = "marginal_observe_grad_reduce"
+    if not 1 <= K <= min(MAX_MOMENTA, MAX_OBS_DRAWS):
+        raise ValueError(f"num_draws={num_draws}: 1 .. {min(MAX_MOMENTA, MAX_OBS_DRAWS)} joint draws per data point")
+    if lw.dtype != torch.float64 or lw.dim() != 1 or lw.numel() % K or not lw.is_contiguous():
+        raise RuntimeError(f"{what}: lw must be a contiguous float64 tensor [B * {K}], got {lw.dtype} {tuple(lw.shape)}")
+    B = lw.numel() // K
+    if gz_rows.dim() != 2 or gz_rows.shape[1] % 2 or gz_rows.shape[1] < 2:
+        raise RuntimeError(f"{what}: gz_rows has shape {tuple(gz_rows.shape)}, expected [n, 2 D]")
+    n, D = int(gz_rows.shape[0]), int(gz_rows.shape[1]) // 2
+    if gc_rows is not None and (gc_rows.dim() != 2 or gc_rows.shape[0] != n or gc_rows.shape[1] < 1):
+        raise RuntimeError(f"{what}: gc_rows has shape {tuple(gc_rows.shape)}, expected [{n}, C >= 1]")
+    C = 0 if gc_rows is None else int(gc_rows.shape[1])
+    if row_of.dtype != torch.int32 or row_of.numel() != B * K or not row_of.is_contiguous() or row_of.device != dev:
+        raise RuntimeError(f"{what}: row_of must be a contiguous int32 tensor of {B * K} elements on {dev}")
+    if B > 0 and int(row_of.max()) >= n:
+        raise RuntimeError(f"{what}: row_of points at row {int(row_of.max())}, gz_rows has {n} rows")
+    stride = _std_stride(noise_std, B, D, what)
+    if gc_rows is None:
+        cond_scale = None
+    for t, name, cols in ((scale, "scale", D), (cond_scale, "cond_scale", C)):
+        if t is not None and t.numel() != cols:
+            raise RuntimeError(f"{what}: {name} has {t.numel()} elements for {cols} columns")
+    if grad_x is None:
+        grad_x = torch.empty(B, D, dtype=torch.float32, device=dev)
+    if grad_c is None and gc_rows is not None:
+        grad_c = torch.empty(B, C, dtype=torch.float32, device=dev)
+    if grad_noise_std is None and want_noise_grad:
+        grad_noise_std = torch.empty(B, D, dtype=torch.float32, device=dev)
+    for t, name, cols in ((grad_x, "grad_x", D), (grad_c, "grad_c", C), (grad_noise_std, "grad_noise_std", D)):
+        if t is not None and t.numel() != B * cols:
+            raise RuntimeError(f"{what}: {name} has {t.numel()} elements for [{B}, {cols}]")
+    if n == 0:                                              # nothing was kept: no row is read, but the pointer is mandatory
+        gz_rows = torch.zeros(1, 2 * D, dtype=torch.float32, device=dev)
+        gc_rows = None if gc_rows is None else torch.zeros(1, C, dtype=torch.float32, device=dev)
+    ptrs = (_chk(gz_rows, "gz_rows", dev), _chk(gc_rows, "gc_rows", dev), _chk(scale, "scale", dev),
+            _chk(cond_scale, "cond_scale", dev), _chk(noise_std, "noise_std", dev), _chk(grad_x, "grad_x", dev),
+            _chk(grad_c if gc_rows is not None else None, "grad_c", dev), _chk(grad_noise_std, "grad_noise_std", dev))
+    if B == 0:
+        return grad_x, grad_c, grad_noise_std
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_observe_grad_reduce, L.ff_marginal_observe_grad_reduce_host,
+                    (lw.data_ptr(), row_of.data_ptr(), ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], stride, B, D, C, K,
+                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset), ptrs[5], ptrs[6], ptrs[7]))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_observe_grad_reduce")
     return grad_x, grad_c, grad_noise_std
 
 

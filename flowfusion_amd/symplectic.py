@@ -17,7 +17,9 @@ launch, no step controller -- is the exact density of what ``sample_leapfrog(sha
 ``log_prob_marginal`` (extension) averages the importance weights of K momentum draws per data point -- the marginal over
 the momentum that ``log_prob`` estimates from one draw -- with a streaming kernel at each end of the solve
 (csrc/ff_marginal.hip); ``log_prob_marginal_grad`` (extension) adds its exact gradient with respect to the data and the
-raw conditional: one forward solve, one backward launch on the rows that carry weight.  Networks outside the compiled pair
+raw conditional: one forward solve, one backward launch on the rows that carry weight.  ``log_prob_marginal_noisy`` / ``log_prob_marginal_noisy_grad`` (extensions) are
+the same two for an observation with known Gaussian errors: the noise is drawn jointly with the momentum
+(csrc/ff_marginal_observe.hip at the two ends, the same launches between), and the gradient gains ``noise_std``.  Networks outside the compiled pair
 shapes, non-SiLU activations and any other ``model`` with the same ``forward(t, state, conditional)`` are evaluated by
 torch with the stepping in the library (generic.py; ``FusedEnvelopeWarning`` for the first two).  GPU only: CPU tensors
 raise.  The reference draws a tqdm progress bar in ``sample``; this module does not.
@@ -372,20 +374,32 @@ class SymplecticFlowModel(nn.Module):
         if not 1 <= K <= _native.MAX_MOMENTA:
             raise ValueError(f"num_momenta={num_momenta}: 1 .. {_native.MAX_MOMENTA} momentum draws per data point")
         self._check_log_prob_method(method, num_steps)
-        B = int(x.shape[0])
+        chunk = self._marginal_chunk(int(x.shape[0]), K, method, chunk_points, "num_momenta")
+        return self._marginal_value(x, None, conditional, K, atol, rtol, method, num_steps, options, seed, sample_offset, chunk,
+                                    return_ess)
+
+    def _marginal_chunk(self, B, K, method, chunk_points, draws):
+        """Data points per chunk of ``log_prob_marginal`` / ``log_prob_marginal_noisy`` (``method`` already checked): the whole
+        batch under an adaptive method, where ``chunk_points`` raises; ``draws``: the caller's name for K."""
         if method != "leapfrog" and method not in solvers.FIXED_METHODS:
             if chunk_points is not None:
                 raise ValueError(f"chunk_points with method={method!r}: an adaptive solve takes its step size from the error "
-                                 "norm of the whole batch, so chunks would change every row's steps; all B * num_momenta rows "
+                                 f"norm of the whole batch, so chunks would change every row's steps; all B * {draws} rows "
                                  "are one solve.  method='leapfrog' with num_steps (a fixed grid) processes chunks with "
                                  "bitwise the same result")
-            chunk = max(B, 1)
-        elif chunk_points is None:
-            chunk = max(1, self.MARGINAL_CHUNK_ROWS // K)
-        else:
-            chunk = int(chunk_points)
-            if chunk < 1:
-                raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
+            return max(B, 1)
+        if chunk_points is None:
+            return max(1, self.MARGINAL_CHUNK_ROWS // K)
+        chunk = int(chunk_points)
+        if chunk < 1:
+            raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
+        return chunk
+
+    def _marginal_value(self, x, std, conditional, K, atol, rtol, method, num_steps, options, seed, sample_offset, chunk,
+                        return_ess):
+        """The chunk loop of ``log_prob_marginal`` (``std`` None: ff_marginal_expand) and ``log_prob_marginal_noisy`` (``std``
+        the tensor of ``odeint.noise_std_tensor``: ff_marginal_observe_expand): expand -> solve -> ff_marginal_reduce."""
+        B = int(x.shape[0])
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
         seed, first = int(seed), int(sample_offset)
@@ -397,8 +411,12 @@ class SymplecticFlowModel(nn.Module):
         ess = torch.empty(B, dtype=torch.float32, device=x.device) if return_ess else None
         for lo in range(0, B, chunk):
             hi = min(B, lo + chunk)
-            z0, ck = _native.marginal_expand(x[lo:hi], K, seed, first + lo, self.shift, self.scale,
-                                             None if cond is None else cond[lo:hi])
+            ck = None if cond is None else cond[lo:hi]
+            if std is None:
+                z0, ck = _native.marginal_expand(x[lo:hi], K, seed, first + lo, self.shift, self.scale, ck)
+            else:
+                z0, ck = _native.marginal_observe_expand(x[lo:hi], std if std.dim() == 1 else std[lo:hi], K, seed, first + lo,
+                                                         _native.f32_on(self.shift, x.device), _native.f32_on(self.scale, x.device), ck)
             z1 = self._solve_forward(z0, ck, atol, rtol, method, options, num_steps)
             del z0
             _native.marginal_reduce(z1, K, seed, first + lo, log_det, out[lo:hi], None if ess is None else ess[lo:hi])
@@ -454,6 +472,20 @@ class SymplecticFlowModel(nn.Module):
         B, D = int(x.shape[0]), int(x.shape[1])
         # (shapes, dtypes and devices only: the raw conditional and an unwritten joint state stand in for the rows)
         _, _, _, _, C = odeint._leapfrog_pull_checks(self, x.new_empty((B, 2 * D)), lambda z1: None, conditional, 1)
+        out, gx, gcond, ess, _, stats = self._marginal_grad_chunks(x, None, conditional, K, m, num_steps, seed, sample_offset,
+                                                                   chunk_points, C, return_ess, False)
+        self.last_marginal_grad_stats = stats
+        return (out, gx, gcond) + ((ess,) if return_ess else ())
+
+    def _marginal_grad_chunks(self, x, std, conditional, K, m, num_steps, seed, sample_offset, chunk_points, C, return_ess,
+                              return_noise_grad):
+        """The chunk loop of ``log_prob_marginal_grad`` (``std`` None: ff_marginal_expand, ff_marginal_grad_reduce) and
+        ``log_prob_marginal_noisy_grad`` (``std`` the tensor of ``odeint.noise_std_tensor``: ff_marginal_observe_expand, and
+        ff_marginal_observe_grad_reduce where the gradient with respect to it is wanted), everything checked by the caller:
+        expand -> one forward ``solve_leapfrog`` -> ff_marginal_weigh -> the kept rows gathered -> one
+        ``odeint._leapfrog_pull_from`` from ``z1`` itself -> reduce.  Returns ``(log_p, grad_x, grad_c or None, ess or None,
+        grad_noise_std or None, stats)``."""
+        B, D = int(x.shape[0]), int(x.shape[1])
         chunk = max(1, self.MARGINAL_CHUNK_ROWS // K) if chunk_points is None else int(chunk_points)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
@@ -463,16 +495,22 @@ class SymplecticFlowModel(nn.Module):
         cond = None if cond is None else cond.contiguous()
         log_det = 0.0 if self.scale is None else float(torch.log(self.scale.double()).sum())
         scale = _native.f32_on(self.scale, x.device)
+        shift = None if std is None else _native.f32_on(self.shift, x.device)
         cscale = _native.f32_on(self.conditional_scale, x.device) if C > 0 else None
         new = lambda cols: torch.empty(B, cols, dtype=torch.float32, device=x.device)
         out, ess = new(1).view(B), (new(1).view(B) if return_ess else None)
         gx, gcond = new(D), (new(C) if C > 0 else None)
+        gstd = new(D) if (std is not None and return_noise_grad) else None
         grid = torch.linspace(1.0, 0.0, int(num_steps) + 1).flip(0)                     # (as _solve_forward builds it)
         kept = forward = backward = 0
         for lo in range(0, B, chunk):
             hi = min(B, lo + chunk)
-            z0, ck = _native.marginal_expand(x[lo:hi], K, seed, first + lo, self.shift, self.scale,
-                                             None if cond is None else cond[lo:hi])
+            ck = None if cond is None else cond[lo:hi]
+            std_c = None if std is None else (std if std.dim() == 1 else std[lo:hi])
+            if std is None:
+                z0, ck = _native.marginal_expand(x[lo:hi], K, seed, first + lo, self.shift, self.scale, ck)
+            else:
+                z0, ck = _native.marginal_observe_expand(x[lo:hi], std_c, K, seed, first + lo, shift, scale, ck)
             z1 = self._solve_forward(z0, ck, None, None, "leapfrog", None, num_steps)
             forward += int(self.last_solver_stats["launches"])
             del z0
@@ -491,10 +529,98 @@ class SymplecticFlowModel(nn.Module):
                 gz, gc = gz[:, 0], (None if gc is None else gc[:, 0])
                 del zk
             kept += n
-            _native.marginal_grad_reduce(lw, row_of, gz, gc, K, scale, cscale, gx[lo:hi], None if gcond is None else gcond[lo:hi])
+            if gstd is None:
+                _native.marginal_grad_reduce(lw, row_of, gz, gc, K, scale, cscale, gx[lo:hi],
+                                             None if gcond is None else gcond[lo:hi])
+            else:
+                _native.marginal_observe_grad_reduce(lw, row_of, gz, gc, std_c, K, seed, first + lo, scale, cscale, True,
+                                                     gx[lo:hi], None if gcond is None else gcond[lo:hi], gstd[lo:hi])
             del z1, ck, lw, keep, gz, gc
-        self.last_marginal_grad_stats = {"rows": B * K, "rows_kept": kept, "launches": {"forward": forward, "backward": backward}}
-        return (out, gx, gcond) + ((ess,) if return_ess else ())
+        stats = {"rows": B * K, "rows_kept": kept, "launches": {"forward": forward, "backward": backward}}
+        return out, gx, gcond, ess, gstd, stats
+
+    # -- extension: the marginal of NOISY observations, K joint (noise, momentum) draws per point -------------------------------
+    # Names of their own: ``log_prob_noisy`` / ``posterior_noisy`` / ``log_prob_noisy_grad`` of the single-network classes
+    # wrap a model's own log-density; here the noise draw joins the momentum draw of the marginal itself.
+    def _marginal_noisy_front_checks(self, what, x, noise_std, num_draws, chunk_points, method, num_steps, grad, min_weight=0.0):
+        """What both noisy-marginal methods refuse before the device is touched, in one order: ``num_draws``, ``min_weight``,
+        ``chunk_points``; the gradient's ``method``; ``num_steps``; ``x``; ``noise_std``.  Returns ``(K, min_weight, std)``."""
+        K = int(num_draws)
+        if not 1 <= K <= _native.MAX_MOMENTA:
+            raise ValueError(f"num_draws={num_draws}: 1 .. {_native.MAX_MOMENTA} joint (noise, momentum) draws per data point")
+        m = float(min_weight)
+        if not 0.0 <= m < 1.0:
+            raise ValueError(f"min_weight={min_weight}: a normalised weight, 0 <= min_weight < 1 (0 keeps every draw of non-zero "
+                             "weight)")
+        if chunk_points is not None and int(chunk_points) < 1:
+            raise ValueError(f"chunk_points={chunk_points}: at least one data point per chunk")
+        if grad and method != "leapfrog":
+            raise ValueError(f"{what}: method={method!r}: Euler and dopri5 rows are not shears, so their pull-back "
+                             "needs a record of the stage states, which the two-network kernels do not keep; use "
+                             "method=\"leapfrog\" with num_steps (every row a shear: the exact gradient of the value it returns)")
+        self._check_log_prob_method(method, num_steps)
+        if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError(f"{what}: x must be a [batch, dim] float32 tensor")
+        return K, m, odeint.noise_std_tensor(noise_std, x)
+
+    @torch.no_grad()
+    def log_prob_marginal_noisy(self, x, noise_std, conditional=None, num_draws=16, atol=1e-5, rtol=1e-5, *, method="dopri5",
+                                num_steps=None, options=None, seed=None, sample_offset=0, chunk_points=None, return_ess=False):
+        """The log-density of a NOISY observation ``x = x_true + n``, ``n ~ N(0, diag noise_std^2)``, as the marginal over
+        noise and momentum, from ``num_draws`` = K joint draws per point: ``log_p [B]`` (``(log_p, ess)`` with ``return_ess``).
+
+        Draw k of point r is the noise ``z_k`` and the momentum ``p_k`` of the counter-based stream, both keyed by ``seed`` and
+        the global row ``sample_offset + r`` (noise indices FF_OBS_NOISE_BASE + k and FF_MOMENTUM_NOISE_BASE + k); its row
+        starts at ``[((x - noise_std z_k) - shift) / scale | p_k]`` (ff_marginal_observe_expand).  The flow preserves volume
+        in [q | p], so ``p_obs(x | noise_std) = E_{z,p}[N(z1) / N(p)] / prod scale`` and the estimate is ``logsumexp_k(log
+        N(z1_k) - log N(p_k)) - log K - sum log scale``: ff_marginal_reduce, unchanged.  ``noise_std``: [B, D], [D] or a
+        scalar, in the units of ``x``, finite and >= 0 (``odeint.noise_std_tensor``); with ``noise_std = 0`` the result is
+        bitwise ``log_prob_marginal`` at the same seed.  The loop, chunk rule, seed rule and adaptive rule are
+        ``log_prob_marginal``'s: on a fixed grid (``method="leapfrog"`` with ``num_steps``) any ``chunk_points`` and any slice
+        of the batch at its ``sample_offset`` give bitwise the same; an adaptive method solves all B K rows at once and
+        ``chunk_points`` raises."""
+        K, _, std = self._marginal_noisy_front_checks("log_prob_marginal_noisy", x, noise_std, num_draws, chunk_points, method,
+                                                      num_steps, False)
+        chunk = self._marginal_chunk(int(x.shape[0]), K, method, chunk_points, "num_draws")
+        return self._marginal_value(x, std, conditional, K, atol, rtol, method, num_steps, options, seed, sample_offset, chunk,
+                                    return_ess)
+
+    @torch.no_grad()
+    def log_prob_marginal_noisy_grad(self, x, noise_std, conditional=None, num_draws=16, *, method="leapfrog", num_steps=None,
+                                     seed=None, sample_offset=0, chunk_points=None, min_weight=0.0, return_ess=False,
+                                     return_noise_grad=False):
+        """``log_prob_marginal_noisy(..., method="leapfrog")`` and its gradient with respect to the observation ``x``, the raw
+        ``conditional`` (the population hyper-parameters) and, with ``return_noise_grad``, ``noise_std``: what a hierarchical
+        fit of data with error bars differentiates.  Returns ``(log_p [B], grad_x [B, D], grad_c [B, C] or None)``, then
+        ``ess [B]`` with ``return_ess``, then ``grad_noise_std [B, D]`` with ``return_noise_grad`` (per object and dimension,
+        whatever the layout of ``noise_std``); ``log_p`` and ``ess`` are bitwise the value method's.
+
+        With the draws fixed, ``wn_k = exp(lw_k - max lw) / W`` (double) and ``(g_q,k | g_p,k)``, ``gamma_k`` the pull-back of
+        the one cotangent ``-z1_k`` through the transposed leapfrog: ``grad_x = sum_k wn_k g_q,k / scale``, ``grad_c = sum_k
+        wn_k gamma_k / conditional_scale``, ``grad_noise_std = -sum_k wn_k z_k g_q,k / scale`` -- the exact gradient of the
+        returned value at that seed, at any step count.  Per chunk of points: ff_marginal_observe_expand -> ONE forward
+        ``solve_leapfrog`` -> ff_marginal_weigh -> the kept rows gathered in order -> ONE ``odeint._leapfrog_pull_from`` from
+        ``z1`` itself -> ff_marginal_grad_reduce, or ff_marginal_observe_grad_reduce with ``return_noise_grad`` (the same
+        ``grad_x`` and ``grad_c`` bit for bit).  ``min_weight``, the kept rows, degenerate points and the independence of
+        chunks and slices are ``log_prob_marginal_grad``'s; with ``noise_std = 0`` every output it shares with that method is
+        bitwise that method's.  ``self.last_marginal_noisy_grad_stats``: ``rows`` (B K), ``rows_kept`` and ``launches``
+        (``{"forward", "backward"}``).
+
+        Refused before the device is touched, in this order: ``num_draws``, ``min_weight``, ``chunk_points`` (ValueError); a
+        ``method`` other than ``"leapfrog"`` (ValueError); ``num_steps`` missing or < 1; ``x`` not [B, D] float32;
+        ``noise_std`` (shape, finite, >= 0); then every refusal of the leapfrog pull-backs
+        (``odeint._leapfrog_pull_checks``).  Fused route only (``_native.PULL_SELECT_ENVELOPE``), no module-path fallback;
+        adaptive, Euler and dopri5 gradients, a momentum gradient, a posterior, parameter gradients and torch.autograd
+        integration are out of scope."""
+        K, m, std = self._marginal_noisy_front_checks("log_prob_marginal_noisy_grad", x, noise_std, num_draws, chunk_points,
+                                                      method, num_steps, True, min_weight)
+        B, D = int(x.shape[0]), int(x.shape[1])
+        # (shapes, dtypes and devices only: the raw conditional and an unwritten joint state stand in for the rows)
+        _, _, _, _, C = odeint._leapfrog_pull_checks(self, x.new_empty((B, 2 * D)), lambda z1: None, conditional, 1)
+        out, gx, gcond, ess, gstd, stats = self._marginal_grad_chunks(x, std, conditional, K, m, num_steps, seed, sample_offset,
+                                                                      chunk_points, C, return_ess, return_noise_grad)
+        self.last_marginal_noisy_grad_stats = stats
+        return (out, gx, gcond) + ((ess,) if return_ess else ()) + ((gstd,) if return_noise_grad else ())
 
     # -- what odeint.solve asks of a front end -------------------------------------------------------
     def _layers(self):

@@ -945,6 +945,64 @@ int ff_observe_grad_reduce_host(const float* lp, const int32_t* row_of, const fl
                                 const float* noise_std, int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K,
                                 uint64_t seed, int64_t sample_offset, float* grad_x, float* grad_c, float* grad_noise_std);
 
+/* ---- marginal log-density of NOISY observations under a symplectic flow, and its gradient ----------------------------
+ * (csrc/ff_marginal_observe.hip, csrc/ff_marginal_observe.h)
+ *
+ * An observation xhat = x + n, n ~ N(0, diag(sigma^2)), of a symplectic flow, whose own density is a marginal over the
+ * momentum.  The flow preserves volume in [q | p], so with JOINT draws (z_k, p_k) per data point
+ *     p_obs(xhat | sigma) = E_{z, p}[N(Phi(z0)) / N(p)] / prod scale,   z0 = [((xhat - sigma z) - shift) / scale | p]
+ *     lw_k = log N(z1_k) - log N(p_k),   L[r] = logsumexp_k lw_k - log K - sum log scale
+ * Both draws of (r, k) are keyed by the seed and the GLOBAL row g = sample_offset + r: the noise under the noise index
+ * FF_OBS_NOISE_BASE + k, the momentum under FF_MOMENTUM_NOISE_BASE + k.  L[r] is what ff_marginal_reduce / ff_marginal_weigh
+ * compute on such rows (they regenerate p_k under the same keys); these two kernels are the other two ends.
+ * 1 <= K <= 4096 (FF_MAX_OBS_DRAWS and the momentum range alike).
+ *
+ * ff_marginal_observe_expand:  t = fl(noise_std[r std_row_stride + d] * z_kd),  y = fl(x[r][d] - t)      (no fused multiply-add)
+ *                              z0[r K + k][0 : D]   = fl(fl(y - shift[d]) / scale[d])
+ *                              z0[r K + k][D : 2 D] = z(seed, sample_offset + r, FF_MOMENTUM_NOISE_BASE + k, d)
+ *                              cond_out[r K + k]    = cond[r]
+ *   y is bit for bit ff_observe_expand's row, the q half ff_marginal_expand's formula applied to it, the p half and cond_out
+ *   bit for bit ff_marginal_expand(x, K)'s; with noise_std = 0 the whole output is ff_marginal_expand(x, K)'s.  (The
+ *   composition ff_observe_expand -> ff_marginal_expand(K = 1) keys every momentum by the EXPANDED row instead.)
+ *   x [B][D]; noise_std [D] (std_row_stride = 0) or [B][D] (std_row_stride = D); shift, scale [D] or NULL; cond [B][C] or
+ *   NULL (C and cond_out are then ignored); z0 [B K][2 D]; cond_out [B K][C].  One pass, write-only beyond x, noise_std and
+ *   cond; 16-byte accesses where x, noise_std, z0 are 16-byte aligned and D % 4 == 0 (cond, cond_out and C likewise, on
+ *   their own), a scalar body with the same arithmetic in the same order otherwise.
+ *   FF_ERR_BADARG, before anything is enqueued: the cases of both parents -- x, noise_std or z0 NULL; B < 0; D < 1; K
+ *   outside 1 .. 4096; std_row_stride neither 0 nor D; cond given with C < 1 or cond_out NULL.
+ * ff_marginal_observe_grad_reduce:  ff_marginal_grad_reduce -- its lanes, segments, order of additions and butterfly: grad_x
+ *   and grad_c are its results bit for bit on the same inputs -- that in the same pass forms
+ *     grad_noise_std[r][d] = -(sum_kept w_k z_kd g_q,kd / W) / scale[d],   z_kd = z(seed, sample_offset + r, FF_OBS_NOISE_BASE + k, d)
+ *   the gradient of L with respect to sigma, per object and dimension whatever the layout of noise_std (dq0 / d sigma =
+ *   -z / scale at any sigma: the values of noise_std are not read, only checked as ff_observe_grad_reduce checks them).  z is
+ *   regenerated from the stream; the product z g (exact) and the sums are in double, the result is rounded to fp32 once.  A
+ *   skipped draw's row is never read.  grad_noise_std may be NULL; gc_rows may be NULL (C, cond_scale and grad_c are then
+ *   ignored); scale and cond_scale may be NULL (1).  A degenerate point (a NaN among its lw, or all -inf) writes NaN to all
+ *   three gradients.  K = 1 with a finite lw: grad_noise_std is -z g / scale rounded once.
+ *   FF_ERR_BADARG, before anything is enqueued: lw, row_of, gz_rows, noise_std or grad_x NULL; B < 0; D < 1; K outside
+ *   1 .. 4096; std_row_stride neither 0 nor D; gc_rows given with C < 1 or grad_c NULL.
+ * A data point's results are fixed by (K, D) and its own data, not by B, its position or the launch: chunks (sample_offset
+ * + first point of the chunk) and shards give bitwise the same.  DEVICE pointers, enqueued on hip_stream; B == 0 is FF_OK
+ * without a launch.  The _host twins run the same header arithmetic on HOST pointers: the normals through libm (they agree
+ * with the device's to rounding, not bit for bit), ff_marginal_observe_grad_reduce_host in the device's own order of
+ * additions, as ff_marginal_grad_reduce_host.
+ */
+int ff_marginal_observe_expand(const float* x, const float* noise_std, int32_t std_row_stride, const float* shift,
+                               const float* scale, const float* cond, int64_t B, int32_t D, int32_t C, int32_t K,
+                               uint64_t seed, int64_t sample_offset, float* z0, float* cond_out, void* hip_stream);
+int ff_marginal_observe_grad_reduce(const double* lw, const int32_t* row_of, const float* gz_rows, const float* gc_rows,
+                                    const float* scale, const float* cond_scale, const float* noise_std,
+                                    int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K, uint64_t seed,
+                                    int64_t sample_offset, float* grad_x, float* grad_c, float* grad_noise_std,
+                                    void* hip_stream);
+int ff_marginal_observe_expand_host(const float* x, const float* noise_std, int32_t std_row_stride, const float* shift,
+                                    const float* scale, const float* cond, int64_t B, int32_t D, int32_t C, int32_t K,
+                                    uint64_t seed, int64_t sample_offset, float* z0, float* cond_out);
+int ff_marginal_observe_grad_reduce_host(const double* lw, const int32_t* row_of, const float* gz_rows, const float* gc_rows,
+                                         const float* scale, const float* cond_scale, const float* noise_std,
+                                         int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K, uint64_t seed,
+                                         int64_t sample_offset, float* grad_x, float* grad_c, float* grad_noise_std);
+
 /* ---- Hutch++ / XTrace divergence estimates from recorded Jacobians (csrc/ff_trace.hip, csrc/ff_trace_est.h) ----
  *
  * Replaces the two estimator branches of ScoreModel.forward, diffusion.py:336-400 (Hutch++) and :402-481 (XTrace), for
