@@ -396,6 +396,11 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.ff_marginal_observe_expand.argtypes, L.ff_marginal_observe_expand_host.argtypes = mobs_expand + [ctypes.c_void_p], mobs_expand
     L.ff_marginal_observe_grad_reduce.argtypes, L.ff_marginal_observe_grad_reduce_host.argtypes = \
         mobs_grad + [ctypes.c_void_p], mobs_grad
+    mobs_resample = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                     ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64] + [ctypes.c_void_p] * 4
+    L.ff_marginal_observe_resample.restype = L.ff_marginal_observe_resample_host.restype = ctypes.c_int
+    L.ff_marginal_observe_resample.argtypes, L.ff_marginal_observe_resample_host.argtypes = \
+        mobs_resample + [ctypes.c_void_p], mobs_resample
     L.ff_mlp_ode_adaptive.restype = ctypes.c_int
     L.ff_mlp_ode_adaptive.argtypes = [ctypes.POINTER(PlanStruct), ctypes.POINTER(OdeArgs), ctypes.POINTER(AdaptConfig),
                                       ctypes.POINTER(AdaptBuffers), ctypes.c_double, ctypes.c_double, ctypes.c_int32,
@@ -1224,6 +1229,57 @@ def marginal_observe_grad_reduce(lw: torch.Tensor, row_of: torch.Tensor, gz_rows
     if rc != FF_OK:
         raise _err(rc, "ff_marginal_observe_grad_reduce")
     return grad_x, grad_c, grad_noise_std
+
+
+def marginal_observe_resample(x: torch.Tensor, noise_std: torch.Tensor, lw: torch.Tensor, num_draws: int, num_samples: int,
+                              seed: int, sample_offset: int = 0, samples: Optional[torch.Tensor] = None,
+                              index: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None,
+                              var: Optional[torch.Tensor] = None):
+    """ff_marginal_observe_resample: ``(samples [B, M, D], index [B, M] int32, mean [B, D], var [B, D])``, the posterior of
+    every observation ``x`` [B, D] from the K = ``num_draws`` joint draws of its noisy marginal: M = ``num_samples``
+    multinomial draws of the candidates ``x[r] - noise_std[r] * z_k`` by the weights ``exp(lw - max lw)`` (``lw`` [B K]
+    float64, ``marginal_weigh``'s), and their weighted mean and variance, in double.  No particle buffer: the candidates are
+    regenerated from ``seed`` and global row ``sample_offset + r`` (noise indices OBS_NOISE_BASE + k), the uniforms are
+    ``weighted_resample``'s.  ``noise_std``: [D] or [B, D], as ``marginal_observe_expand`` took it.  The outputs are allocated
+    where not given.  Device tensors on the current stream; CPU tensors go to ff_marginal_observe_resample_host."""
+    dev = x.device
+    what = "marginal_observe_resample"
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise RuntimeError(f"{what}: x has shape {tuple(x.shape)}, expected [B, D >= 1]")
+    B, D = x.shape
+    K, M = int(num_draws), int(num_samples)
+    if not 1 <= K <= min(MAX_MOMENTA, MAX_OBS_DRAWS):
+        raise ValueError(f"num_draws={num_draws}: 1 .. {min(MAX_MOMENTA, MAX_OBS_DRAWS)} joint draws per data point")
+    if not 0 <= M <= MAX_OBS_SAMPLES:
+        raise ValueError(f"num_samples={num_samples}: 0 .. {MAX_OBS_SAMPLES} posterior draws per data point")
+    stride = _std_stride(noise_std, B, D, what)
+    if lw.dtype != torch.float64 or lw.dim() != 1 or lw.numel() != B * K or not lw.is_contiguous() or lw.device != dev:
+        raise RuntimeError(f"{what}: lw must be a contiguous float64 tensor [{B} * {K}] on {dev}, got {lw.dtype} "
+                           f"{tuple(lw.shape)} on {lw.device}")
+    if samples is None:
+        samples = torch.empty(B, M, D, dtype=torch.float32, device=dev)
+    if index is None:
+        index = torch.empty(B, M, dtype=torch.int32, device=dev)
+    if mean is None:
+        mean = torch.empty(B, D, dtype=torch.float32, device=dev)
+    if var is None:
+        var = torch.empty(B, D, dtype=torch.float32, device=dev)
+    for t, name, n in ((samples, "samples", B * M * D), (index, "index", B * M), (mean, "mean", B * D), (var, "var", B * D)):
+        if t.numel() != n:
+            raise RuntimeError(f"{what}: {name} has {t.numel()} elements, expected {n}")
+    if index.dtype != torch.int32 or index.device != dev or not index.is_contiguous():
+        raise RuntimeError(f"{what}: index must be a contiguous int32 tensor on {dev}")
+    ptrs = (_chk(x, "x", dev), _chk(noise_std, "noise_std", dev), _chk(samples, "samples", dev), _chk(mean, "mean", dev),
+            _chk(var, "var", dev))
+    if B == 0:
+        return samples, index, mean, var
+    L = lib()
+    rc = _on_stream(dev, L.ff_marginal_observe_resample, L.ff_marginal_observe_resample_host,
+                    (ptrs[0], ptrs[1], stride, lw.data_ptr(), B, D, K, M, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset),
+                     ptrs[2], index.data_ptr(), ptrs[3], ptrs[4]))
+    if rc != FF_OK:
+        raise _err(rc, "ff_marginal_observe_resample")
+    return samples, index, mean, var
 
 
 def trace_kind_and_probes(kind: str, probes):

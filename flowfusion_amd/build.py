@@ -473,6 +473,7 @@ const int g_n_pushsel_kernels = {len(PUSH_SELECT)};
     files.append(CSRC / "ff_probe.hip")
     files.append(CSRC / "ff_observe.hip")
     files.append(CSRC / "ff_marginal_observe.hip")
+    files.append(CSRC / "ff_marginal_posterior.hip")
     return files
 
 

@@ -467,3 +467,76 @@ def symplectic_log_prob_sharded(model, x: Optional[torch.Tensor] = None, conditi
         local = model._log_prob_from(rows, p0, cond, atol, rtol, method=method,
                                      **({} if num_steps is None else {"num_steps": num_steps}))
     return _finish(local, n, group, gather)
+
+
+def _noise_std_args(noise_std, local_noise_std, local_x):
+    """The refusals every noisy sharded entry point shares (``log_prob_noisy_sharded``'s rules)."""
+    if local_noise_std is not None and (noise_std is not None or local_x is None):
+        raise ValueError("local_noise_std holds this rank's [rows, dim] of a per-object noise_std: it goes with local_x and "
+                         "excludes `noise_std` (which then is a [dim] vector or a scalar, the same on every rank)")
+    if local_noise_std is None and noise_std is None:
+        raise ValueError("pass noise_std (or local_noise_std with local_x)")
+
+
+def symplectic_log_prob_marginal_noisy_sharded(model, x: Optional[torch.Tensor] = None, noise_std=None,
+                                               conditional: Optional[torch.Tensor] = None, *,
+                                               local_x: Optional[torch.Tensor] = None,
+                                               local_noise_std: Optional[torch.Tensor] = None, n_total: Optional[int] = None,
+                                               local_conditional: Optional[torch.Tensor] = None, seed: int = 0,
+                                               num_draws: int = 16, group=None, gather: bool = True,
+                                               global_control: bool = True, return_ess: bool = False, atol: float = 1e-5,
+                                               rtol: float = 1e-5, method: str = "dopri5", num_steps: Optional[int] = None):
+    """``SymplecticFlowModel.log_prob_marginal_noisy`` of a [B, D] batch of observations over all ranks; ONE all-gather of the
+    [B] result at the end.  ``x`` / ``local_x`` / ``noise_std`` / ``local_noise_std`` / ``n_total`` / ``conditional`` /
+    ``local_conditional`` exactly as ``log_prob_noisy_sharded`` takes them: the full tensors, every rank slicing its rows of the
+    contiguous balanced shards, or this rank's rows already; a [B, D] ``noise_std`` is cut like ``x``, a [D] vector or a scalar
+    is replicated.  The joint (noise, momentum) draws are keyed by ``seed`` and the GLOBAL row (``sample_offset`` = the rank's
+    first row).  ``method="leapfrog"`` with ``num_steps``: a fixed grid -- no collective but the final gather,
+    ``global_control`` is ignored, ranks without rows are fine and a row's result is bitwise independent of the world size.
+    Under an adaptive ``method`` (the default) every rank's ``local * K`` rows are one solve whose step size comes from the
+    error norm of the WHOLE expanded batch (``global_step_control``; every rank needs at least one row),
+    ``global_control=False``: from the rank's own rows.  ``return_ess=True``: ``(log_p, ess)``, the two gathered as the columns
+    of one [rows, 2] tensor -- still one all-gather; with ``gather=False`` ``((log_p, ess), (lo, hi))``.  More than one rank
+    over RCCL has not been run on hardware, like everything else multi-rank here."""
+    _noise_std_args(noise_std, local_noise_std, local_x)
+    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
+    std = _local_noise_std(noise_std, local_noise_std, local_x, lo, hi)
+    with _step_control(n, group, global_control, method):
+        local = model.log_prob_marginal_noisy(rows, std, cond, int(num_draws), atol, rtol, method=method, num_steps=num_steps,
+                                              seed=int(seed), sample_offset=lo, return_ess=return_ess)
+    return _finish(tuple(local) if return_ess else local, n, group, gather)
+
+
+def symplectic_posterior_marginal_noisy_sharded(model, x: Optional[torch.Tensor] = None, noise_std=None,
+                                                conditional: Optional[torch.Tensor] = None, *,
+                                                local_x: Optional[torch.Tensor] = None,
+                                                local_noise_std: Optional[torch.Tensor] = None, n_total: Optional[int] = None,
+                                                local_conditional: Optional[torch.Tensor] = None, seed: int = 0,
+                                                num_draws: int = 16, num_samples: int = 1, group=None, gather: bool = True,
+                                                global_control: bool = True, atol: float = 1e-5, rtol: float = 1e-5,
+                                                method: str = "dopri5", num_steps: Optional[int] = None):
+    """``SymplecticFlowModel.posterior_marginal_noisy`` of a [B, D] batch of observations over all ranks: a ``NoisyPosterior``
+    of the whole batch on every rank -- with ``gather=False`` ``(NoisyPosterior of this rank's rows, (lo, hi))``.  The batch
+    arguments, the keying of the joint draws and the resampling uniforms by ``seed`` and the GLOBAL row, and the step control
+    of an adaptive ``method``: exactly ``symplectic_log_prob_marginal_noisy_sharded``; with ``method="leapfrog"`` every row of
+    every field is bitwise independent of the number of ranks, and ranks without rows are fine.  ONE all-gather: the fields
+    travel as the columns of one [rows, M D + 2 D + 2 + M] fp32 tensor (samples, mean, var, log_prob, ess, index -- indices up
+    to 4095 and -1 are exact in fp32), as in ``posterior_noisy_sharded``, and come back in their own shapes and dtypes."""
+    _noise_std_args(noise_std, local_noise_std, local_x)
+    from .odeint import NoisyPosterior
+    M = int(num_samples)
+    n, lo, hi, rows, cond = _local_batch(x, local_x, n_total, conditional, local_conditional, group)
+    std = _local_noise_std(noise_std, local_noise_std, local_x, lo, hi)
+    with _step_control(n, group, global_control, method):
+        post = model.posterior_marginal_noisy(rows, std, cond, int(num_draws), M, atol, rtol, method=method,
+                                              num_steps=num_steps, seed=int(seed), sample_offset=lo)
+    k, D = hi - lo, int(rows.shape[1])
+    local = torch.cat([post.samples.reshape(k, M * D), post.mean, post.var, post.log_prob.reshape(k, 1),
+                       post.ess.reshape(k, 1), post.index.to(torch.float32)], dim=1)
+    res = _finish(local, n, group, gather)
+    packed, span = res if not gather else (res, None)
+    rows_out = packed.shape[0]
+    samples, mean, var, lp, ess, index = torch.split(packed, [M * D, D, D, 1, 1, M], dim=1)
+    post = NoisyPosterior(samples.reshape(rows_out, M, D), lp.reshape(rows_out), ess.reshape(rows_out), mean.contiguous(),
+                          var.contiguous(), index.to(torch.int32))
+    return post if gather else (post, span)

@@ -622,6 +622,70 @@ class SymplecticFlowModel(nn.Module):
         self.last_marginal_noisy_grad_stats = stats
         return (out, gx, gcond) + ((ess,) if return_ess else ()) + ((gstd,) if return_noise_grad else ())
 
+    @torch.no_grad()
+    def posterior_marginal_noisy(self, x, noise_std, conditional=None, num_draws=16, num_samples=1, atol=1e-5, rtol=1e-5, *,
+                                 method="dopri5", num_steps=None, options=None, seed=None, sample_offset=0, chunk_points=None):
+        """The per-object posterior ``p(x_true | x, noise_std) ~ p(x_true) N(x; x_true, diag noise_std^2)`` of NOISY
+        observations ``x`` [B, D], from the ``num_draws`` = K joint draws that ``log_prob_marginal_noisy`` makes and drops: an
+        ``odeint.NoisyPosterior(samples [B, M, D], log_prob [B], ess [B], mean [B, D], var [B, D], index [B, M])``.
+
+        Candidate k of point r is ``y_k = x - noise_std z_k`` and its weight ``w_k = N(z1_k) / N(p_k)``.  The flow preserves
+        volume in [q | p], so ``w_k`` is an unbiased ONE-MOMENTUM estimate of ``p(y_k)``, not ``p(y_k)`` itself: the K rows are
+        a pseudo-marginal, self-normalised importance sample of the posterior (the momentum is integrated out by the same
+        average that integrates out the noise).  ``samples`` are M = ``num_samples`` multinomial draws of the candidates by
+        their weights, in the units of ``x``; ``index`` [B, M] int32 says which candidate each is; ``mean`` -- the de-noised
+        ("shrunk") value of each object under the learned population -- and ``var`` are the weighted mean and variance of the
+        candidates, in double; ``log_prob`` and ``ess`` are bitwise ``log_prob_marginal_noisy(..., return_ess=True)`` at the same
+        seed.
+
+        The samples are a RESAMPLE of K particles: only as many distinct points as the effective sample size allows.  Read
+        ``ess`` before trusting ``samples``, and raise ``num_draws``, not ``num_samples``, to get more of them.
+
+        Arguments, chunk rule, seed rule and adaptive rule are ``log_prob_marginal_noisy``'s.  Per chunk of points:
+        ff_marginal_observe_expand -> the solve of ``log_prob`` -> ff_marginal_weigh with ``min_weight = 0`` (``log_prob``,
+        ``ess`` and the rows' ``lw`` in double) -> ff_marginal_observe_resample, which regenerates the candidates from the
+        counter-based stream instead of reading a particle buffer (uniforms under the same ``seed`` and global row,
+        FF_OBS_RESAMPLE_NOISE_INDEX).  On a fixed grid (``method="leapfrog"`` with ``num_steps``) every field is bitwise
+        independent of ``chunk_points`` and of slicing the batch at its ``sample_offset``; an adaptive method solves all B K
+        rows at once and ``chunk_points`` raises.  A point with a NaN among its ``lw``, or with no draw above -inf, has
+        ``index = -1`` and NaN in ``samples``, ``mean`` and ``var``.
+
+        Refused before the device is touched, in this order: ``num_draws``, ``num_samples`` (0 .. 4096), ``chunk_points``
+        (ValueError); ``method`` / ``num_steps``; ``x`` not [B, D] float32; ``noise_std`` (shape, finite, >= 0).  A posterior over
+        the momentum, gradients of the posterior and MCMC refinement of low-ESS objects are out of scope."""
+        M = int(num_samples)
+        # (a bad num_draws is the front checks' to refuse, first)
+        if 1 <= int(num_draws) <= _native.MAX_MOMENTA and not 0 <= M <= _native.MAX_OBS_SAMPLES:
+            raise ValueError(f"num_samples={num_samples}: 0 .. {_native.MAX_OBS_SAMPLES} posterior draws per data point")
+        K, _, std = self._marginal_noisy_front_checks("posterior_marginal_noisy", x, noise_std, num_draws, chunk_points, method,
+                                                      num_steps, False)
+        B, D = int(x.shape[0]), int(x.shape[1])
+        chunk = self._marginal_chunk(B, K, method, chunk_points, "num_draws")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed, first = int(seed), int(sample_offset)
+        x = x.contiguous()
+        cond = self._norm_cond(conditional)
+        cond = None if cond is None else cond.contiguous()
+        log_det = 0.0 if self.scale is None else float(torch.log(self.scale.double()).sum())
+        shift, scale = _native.f32_on(self.shift, x.device), _native.f32_on(self.scale, x.device)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x.device)
+        out, ess, mean, var, samples = new(B), new(B), new(B, D), new(B, D), new(B, M, D)
+        index = torch.empty(B, M, dtype=torch.int32, device=x.device)
+        for lo in range(0, B, chunk):
+            hi = min(B, lo + chunk)
+            std_c = std if std.dim() == 1 else std[lo:hi]
+            z0, ck = _native.marginal_observe_expand(x[lo:hi], std_c, K, seed, first + lo, shift, scale,
+                                                     None if cond is None else cond[lo:hi])
+            z1 = self._solve_forward(z0, ck, atol, rtol, method, options, num_steps)
+            del z0, ck
+            _, lw, _ = _native.marginal_weigh(z1, K, seed, first + lo, log_det, 0.0, out[lo:hi], ess[lo:hi])
+            del z1
+            _native.marginal_observe_resample(x[lo:hi], std_c, lw, K, M, seed, first + lo, samples[lo:hi], index[lo:hi],
+                                              mean[lo:hi], var[lo:hi])
+            del lw
+        return odeint.NoisyPosterior(samples, out, ess, mean, var, index)
+
     # -- what odeint.solve asks of a front end -------------------------------------------------------
     def _layers(self):
         m = self.model

@@ -1003,6 +1003,45 @@ int ff_marginal_observe_grad_reduce_host(const double* lw, const int32_t* row_of
                                          int32_t std_row_stride, int64_t B, int32_t D, int32_t C, int32_t K, uint64_t seed,
                                          int64_t sample_offset, float* grad_x, float* grad_c, float* grad_noise_std);
 
+/* ---- per-object posteriors from the K joint draws of the noisy marginal --------------------------------------------------
+ * (csrc/ff_marginal_posterior.hip, csrc/ff_marginal_posterior.h)
+ *
+ * The joint draw (z_k, p_k) of data point r carries the weight w_k = N(z1_k) / N(p_k) = exp(lw_k): the flow preserves volume,
+ * so w_k is an unbiased one-momentum estimate of p(xhat - sigma z_k), and the K candidates y_k = xhat - sigma z_k with these
+ * weights are a pseudo-marginal, self-normalised importance sample of p(x | xhat, sigma) ~ p(x) N(xhat; x, diag sigma^2).
+ * ff_marginal_observe_resample is ff_weighted_resample on them, with two differences: the log-weights are the DOUBLE lw of
+ * ff_marginal_weigh, and there is no particle buffer -- every candidate is regenerated from the counter-based stream where
+ * it is needed, as ff_marginal_observe_grad_reduce regenerates z.  Per data point r, in double:
+ *     w_k = exp(lw[r K + k] - max_k lw)  (1 for the maximum itself),   W = sum_k w_k
+ *     y_k[d]          = fl(x[r][d] - fl(noise_std[r std_row_stride + d] * z_kd)),
+ *                       z_kd = z(seed, sample_offset + r, FF_OBS_NOISE_BASE + k, d): bit for bit ff_observe_expand's row
+ *     index[r][m]     = the smallest k of positive weight with sum_{j <= k} w_j > u_m W  (strict; u_m of
+ *                       ff_weighted_resample: FF_OBS_RESAMPLE_NOISE_INDEX, global row sample_offset + r)
+ *     samples[r][m][] = y_index[r][m], regenerated, in the units of x
+ *     mean[r][d]      = sum_k w_k y_kd / W
+ *     var[r][d]       = sum_k w_k (y_kd - mean_d)^2 / W   (about the double mean, a second pass: never negative)
+ *   x [B][D]; noise_std [D] (std_row_stride = 0) or [B][D] (std_row_stride = D); lw [B K] double; samples [B][M][D]; index
+ *   [B][M]; mean, var [B][D].  Each of the four outputs may be NULL (samples and index are ignored when M == 0); mean and var
+ *   are rounded to fp32 once (the double sums times the double 1 / W: one division per point).  The lanes, segments, scan,
+ *   targets, fallback and order of additions are ff_weighted_resample's: given the same particles and weights (lw that fp32
+ *   holds exactly, y = ff_observe_expand's rows) all four outputs are its results bit for bit.  A point is degenerate if any
+ *   of its lw is NaN, or if none is above -inf: index = -1, NaN in samples, mean and var.  K = 1 with a finite lw: index 0,
+ *   every sample and the mean are y_0, var = 0.  16-byte stores on samples where it is 16-byte aligned and D % 4 == 0 (x and
+ *   noise_std are read likewise, on their own), a scalar body with the same arithmetic otherwise.
+ *   FF_ERR_BADARG, before anything is enqueued: x, noise_std or lw NULL; B < 0; D < 1; K outside 1 .. 4096; M outside
+ *   0 .. FF_MAX_OBS_SAMPLES; std_row_stride neither 0 nor D; all four outputs NULL.  B == 0 is FF_OK without a launch.
+ * A data point's results are fixed by (K, D) and its own data, not by B, its position or the launch: chunks (sample_offset
+ * + first point of the chunk) and shards give bitwise the same.  DEVICE pointers, enqueued on hip_stream; the _host twin runs
+ * the same header arithmetic on HOST pointers with the draws in index order (the same uniforms bit for bit; the normals
+ * through libm; sums agree to double rounding).
+ */
+int ff_marginal_observe_resample(const float* x, const float* noise_std, int32_t std_row_stride, const double* lw,
+                                 int64_t B, int32_t D, int32_t K, int32_t M, uint64_t seed, int64_t sample_offset,
+                                 float* samples, int32_t* index, float* mean, float* var, void* hip_stream);
+int ff_marginal_observe_resample_host(const float* x, const float* noise_std, int32_t std_row_stride, const double* lw,
+                                      int64_t B, int32_t D, int32_t K, int32_t M, uint64_t seed, int64_t sample_offset,
+                                      float* samples, int32_t* index, float* mean, float* var);
+
 /* ---- Hutch++ / XTrace divergence estimates from recorded Jacobians (csrc/ff_trace.hip, csrc/ff_trace_est.h) ----
  *
  * Replaces the two estimator branches of ScoreModel.forward, diffusion.py:336-400 (Hutch++) and :402-481 (XTrace), for
